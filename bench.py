@@ -2,9 +2,15 @@
 """
 bench.py -- SQP-RTI OCP solves/sec on synthetic batches (BASELINE.json metric).
 
-  python bench.py [--config {2,3,4,5}] [--scaling {weak,strong}] --gpus N --steps K --warmup W
+  python bench.py [--config {2,3,4,5}] [--scaling {weak,strong}] --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: launched by torch.distributed.run, one rank per GPU; the batch is sharded by scenario GROUP, every rank solves
    its own share, and the result slab is gathered to rank 0 over RCCL each step: one collective per step.)
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the kernel time between the events
+around each solve, the roofline of the timed region). Everything else the line can carry -- the host-visible, one-stream,
+repeated-batch and natural-order legs, the interior point kernel timed on its own, N = 38, the other configurations and the coupled
+SNMPC OCP, the CPU baseline and the parity against it -- runs with --full only (N = 1; the --no-* options still skip single legs).
+--dump-outputs DIR: after the timed steps, what the last of them computed goes to DIR/<name>.npy as float64 (`timed_outputs`).
 
 A "step" = one pass of the hot path over one batch, inputs resident in HBM before the timed region:
   config 2 (default; BASELINE configs[1], the configuration the metric is quoted on): cold start + one SQP real-time
@@ -23,13 +29,13 @@ previous one finish (a batch is only four rounds of resident wavefronts: run one
 every batch's tail). At N = 1 the line also carries the same loop on ONE capsule / ONE stream (`value_single_stream`: the
 roofline block and the per-kernel times are taken from that leg, where a launch has the chip to itself), the repeated-batch
 figure (the same batch every step: the longest-first dispatch then has exact history, `value_repeated_batch`) and the
-natural-order figure (`config.kernel_ms_natural_order`).
+natural-order figure (`config.kernel_ms_natural_order`) -- with --full.
 
 --scaling weak (default): every rank owns the config's per-GPU share (global batch = N x share).
 --scaling strong: a fixed global batch (--global-batch, default 8 x the per-GPU share = the BASELINE multi-GPU size of
                   configs 4 / 5) is cut into N group-aligned shards.
 
-Prints ONE JSON line on rank 0. At N = 1 the line also carries the CPU baseline (the oracle on the host cores).
+Prints ONE JSON line on rank 0. At N = 1 with --full the line also carries the CPU baseline (the oracle on the host cores).
 The control flow below (`run`) is backend-agnostic: tests/test_host_logic.py drives it on CPU with gloo, world size 2 and a
 stand-in solver.
 """
@@ -156,10 +162,17 @@ def parse_args(argv=None):
                     help="let the capsule read every step's resident batch (x0, yref) in place (tum_ocp_bind_device) instead of copying it "
                          "device-to-device into the capsule's own arrays inside the timed region (tum_ocp_put_device, the default and what "
                          "rounds 1-5 report; measured difference 4.037 vs 4.032 M solves/s, profiles/r05_bind_inputs.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (N=1 only): host-visible, one-stream, repeated-batch and natural-order legs, "
+                         "the interior point kernel on its own, N = 38, configs 3 / 4 / 5 and the coupled SNMPC OCP, the CPU baseline and "
+                         "the parity against it; the --no-* options below skip single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (status, qp_iter, cost, X, U, ...) to DIR/<name>.npy "
+                         "as float64, at most 64 MB in all (a fixed seeded sample of the instances beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-legs", action="store_true", help="skip the host-visible legs (N=1 only)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the bounded legs of configs 3 / 4 / 5 and the coupled SNMPC OCP that the default N=1 line carries as `other_configs`")
+                    help="skip the bounded legs of configs 3 / 4 / 5 and the coupled SNMPC OCP that the --full N=1 line carries as `other_configs`")
     ap.add_argument("--no-schedule-legs", action="store_true",
                     help="skip the repeated-batch, natural-order and N = 38 legs (N=1 only)")
     return ap.parse_args(argv)
@@ -284,6 +297,7 @@ class Job:
     # ---- one step; `marks`: list that receives (solve_begin, solve_end)* and (gather_begin, gather_end) clock marks
     def step(self, marks=None, fresh=None):
         slot, s = self.ring.acquire()
+        self.last_slot = slot
         if self.cuda and self.S > 1:
             with self.torch.cuda.stream(self.streams[slot]):      # (events, the reduction and the gather follow the capsule's stream)
                 self._step(slot, s, marks, fresh)
@@ -375,13 +389,50 @@ class Job:
         return float(np.mean([self.clock.ms(m[2 * self.spp], m[2 * self.spp + 1]) for m in marks]))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def timed_outputs(job):
+    """What the last step of the timed loop computed, as the caller of that path receives it: status, qp_iter, cost and the iterate
+    X, U of every instance of the capsule that ran the step (config 3: with the PCE mean / variance of x_1 of every scenario group;
+    config 5: of the step's second solve), and on a job of several ranks the summary of every instance (u0, cost, status, qp_iter)
+    as the rooted gather delivered it to rank 0. float64 host copies by file name."""
+    s = job.ring[job.last_slot]
+    X, U = s.get_iterate()
+    out = {"status": s.get_stats("status"), "qp_iter": s.get_stats("qp_iter"), "cost": np.atleast_1d(s.get_cost()), "X": X, "U": U}
+    if job.nmom:
+        mom = job.slabs[job.last_slot][job.B * 5:job.B * 5 + 2 * job.P * 8].cpu().numpy().reshape(2, job.P, 8)
+        out["pce_mean_x1"], out["pce_var_x1"] = mom[0], mom[1]
+    if job.gather is not None:
+        allf = job.gather.all_f.cpu().numpy()[:, 0]
+        out["gathered_summary"] = np.concatenate([allf[r, :sharding_size(job, r) * 5].reshape(-1, 5) for r in range(job.world)])
+    return {k: np.asarray(v, dtype=np.float64) for k, v in out.items() if v is not None}
+
+
+def write_outputs(path, arrays, limit=DUMP_MAX_BYTES):
+    """arrays -> path/<name>.npy. Beyond `limit` bytes in all, every array keeps the same fraction of its rows, a fixed seeded sample
+    (the sorted row indices go to <name>_rows.npy): the same arguments give the same files."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    frac = min(1.0, (limit - 4096 * 2 * len(arrays)) / total)
+    for name, a in arrays.items():
+        if frac < 1.0 and len(a) > 1:
+            idx = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(frac * len(a))), replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run(args, torch, dist, dev, world, rank, local_rank, solver_factory, workload=None, extra_legs=True):
-    """The benchmark proper. Returns (result dict, job) on rank 0 (None elsewhere)."""
+    """The benchmark proper. Returns (result dict, job) on rank 0 (None elsewhere). The legs behind the timed loop run with --full only."""
     job = Job(args, torch, dist, dev, world, rank, local_rank, solver_factory, workload)
     N, cid, B, spp, S = job.N, job.cid, job.B, job.spp, job.S
+    extra_legs = extra_legs and bool(getattr(args, "full", False))
     for i in range(args.warmup):
         job.step(fresh=None if args.same_batch else i)
     elapsed, marks = job.timed(args.steps, fresh=not args.same_batch)
+    if rank == 0 and getattr(args, "dump_outputs", None):      # (before any further leg runs on the same capsules)
+        write_outputs(args.dump_outputs, timed_outputs(job))
     rank_elapsed = list(job.rank_elapsed)
     kern_ms = job.solve_ms(marks)             # device time between the events around a solve (S > 1: shared with other batches)
     gat_ms = job.gather_ms(marks)
@@ -571,6 +622,7 @@ def sharding_size(job, r):
 def n38_leg(args, torch, dev, solver_factory):
     """"also report N = 38" (the reference's own horizon, Tp = 3.04 s): fresh-batch rate of config 2 at N = 38."""
     a = argparse.Namespace(**vars(args)); a.horizon = 38; a.config = 2; a.batch = None; a.scaling = "weak"; a.no_schedule_legs = True
+    a.dump_outputs = None
     res = run(a, torch, None, dev, 1, 0, dev.index or 0, solver_factory, extra_legs=False)
     out, _ = res
     return {"N": 38, "value": out["value"], "ms_per_step": out["ms_per_step"], "streams": out["config"]["streams"],
@@ -650,7 +702,7 @@ def other_configs_legs(args, torch, dev, solver_factory, steps=8, warmup=3):
     for cid in (3, 4, 5):
         try:
             a = argparse.Namespace(**vars(args)); a.config = cid; a.batch = None; a.scaling = "weak"; a.steps = steps; a.warmup = warmup
-            a.no_schedule_legs = True; a.no_host_legs = True
+            a.no_schedule_legs = True; a.no_host_legs = True; a.dump_outputs = None
             o, job = run(a, torch, None, dev, 1, 0, dev.index or 0, solver_factory, extra_legs=False)
             out[str(cid)] = {"value": o["value"], "ms_per_step": o["ms_per_step"], "batch": o["config"]["batch_per_gpu"],
                              "solves_per_step": o["config"]["solves_per_step"], "steps": steps, "streams": o["config"]["streams"],
@@ -754,12 +806,13 @@ def main(argv=None):
                          "torch.distributed.run" if launched else "single process")
         if stand_in is not None:
             out["data"] = "stand-in solver on CPU / gloo (control-flow test, not a measurement)"
-        gpu_legs = stand_in is None and world == 1
+        out["full"] = args.full
+        gpu_legs = stand_in is None and world == 1 and args.full
         if gpu_legs and not args.no_schedule_legs and args.horizon != 38 and args.config == 2:
             out["n38"] = n38_leg(args, torch, dev, factory)
         if gpu_legs and not args.no_other_configs and args.config == 2 and args.horizon == 40 and not args.same_batch:
             out["other_configs"] = other_configs_legs(args, torch, dev, factory)
-        if not args.no_cpu_baseline and world == 1 and stand_in is None:
+        if gpu_legs and not args.no_cpu_baseline:
             x0, yref = job.host[0]
             cb, u_ref = cpu_baseline(job.N, x0, yref, job.s.cfg)
             out["cpu_baseline"] = cb

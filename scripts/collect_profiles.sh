@@ -3,14 +3,14 @@
 # the kernel-variant A/B. Outputs under gpurun_out/final/ ; scripts/ingest_profiles.py <tag> then copies the summaries into
 # profiles/<tag>_*. Every step runs under `timeout` and with stdin closed.
 # The profiled command is `bench.py --streams 1` (one capsule, one stream: a launch has the chip to itself and the per-kernel
-# averages are what the `roofline` block of the default bench line quotes from its own one-stream leg); the default command
+# averages are what the `roofline` block of the --full bench line quotes from its own one-stream leg); the default command
 # deals the steps to three streams, where launches of consecutive batches overlap.
 set -u
 OUT=gpurun_out/final; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 T="timeout 300"
 P="python bench.py --streams 1 --no-cpu-baseline --no-schedule-legs --no-other-configs"
-$T python bench.py --steps 20 --warmup 3 2>/dev/null < /dev/null | grep metric > $OUT/bench.json
+$T python bench.py --full --steps 20 --warmup 3 2>/dev/null < /dev/null | grep metric > $OUT/bench.json
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $P --steps 20 --warmup 3 > $OUT/stats_bench.log 2>&1 < /dev/null
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats3 -o s -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-schedule-legs --no-other-configs > /dev/null 2>&1 < /dev/null
 $T rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_rep -o s -- $P --same-batch --steps 20 --warmup 3 > /dev/null 2>&1 < /dev/null
@@ -23,7 +23,7 @@ for c in 3 4 5; do
   $T rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_c$c -o p -- $P --config $c --steps 2 --warmup 1 > /dev/null 2>&1 < /dev/null
 done
 for k in pipeline fused; do $T python scripts/phase_profile.py 4096 $k 2>&1 < /dev/null | grep -v amdgpu >> $OUT/phase_cycles.txt; done
-for c in 3 4 5; do $T python bench.py --config $c --steps 10 --no-other-configs 2>/dev/null < /dev/null | grep metric >> $OUT/configs.jsonl; done
+for c in 3 4 5; do $T python bench.py --full --config $c --steps 10 --no-other-configs 2>/dev/null < /dev/null | grep metric >> $OUT/configs.jsonl; done
 for b in 1 512 4096 16384; do B=$b $T python scripts/pipe_check.py fused pipeline pipeline4 2>&1 < /dev/null | grep -E "^fused|^pipeline" | sed "s/^/batch $b: /" >> $OUT/kernel_variants.txt; done
 for S in 1 2 3 4 5 6 8; do $T python bench.py --steps 20 --warmup 3 --streams $S --no-cpu-baseline --no-schedule-legs --no-other-configs 2>/dev/null < /dev/null | grep metric | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('streams',d['config']['streams'],'value %.3f M solves/s'%(d['value']/1e6),'ms/step %.3f'%d['ms_per_step'])" >> $OUT/streams.txt; done
 $T python scripts/snmpc_bench.py 2>&1 < /dev/null | grep -v amdgpu.ids > $OUT/snmpc_bench.txt

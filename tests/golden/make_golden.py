@@ -20,6 +20,7 @@ DATA (inputs + expected outputs), never reference source:
                       generate_disturbances for every distribution type, in sim_step's draw order; LonLatDeviations / postprocess_yaw pairs
   closed_loop_<t>_<n>.npz   first n steps of the 26 logged closed loops of one track (plant states, inputs, predictions)
   closed_loop_<t>_full_sub<k>.npz   the complete 5499-step loops, every k-th plant state + per-loop statistics
+  log_file_<t>_<k>.npz   one logged loop's _baseline/F/<t>/<k>.npz as Logger.save_logs wrote it (every key, full length)
 
 Reference call sites reproduced by the replay protocol:
   get_baseline_performances.py:101-131 (loop), Utils/SimulationMode_main_class.py:106-156
@@ -328,8 +329,18 @@ def make_disturbances():
     np.savez_compressed(os.path.join(OUT, "disturbances.npz"), **out)
 
 
+def make_log_file(track="lvms", k=3):
+    """Utils/Logging_Plotting.py:321-395: the file Logger.save_logs wrote for one logged loop, every array as stored (the five raw
+    logs and the channels derived from them): what tum_control_amd.closed_loop.log_file_arrays must reproduce."""
+    with np.load(os.path.join(BASE, track, f"{k}.npz")) as r:
+        np.savez_compressed(os.path.join(OUT, f"log_file_{track}_{k}.npz"), **{key: r[key] for key in r.files})
+
+
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["kat0", "replay", "replay_hard", "planner", "pce", "snmpc_json", "snmpc_expr", "r2", "closed_loop", "disturbances"]
+    what = sys.argv[1:] or ["kat0", "replay", "replay_hard", "planner", "pce", "snmpc_json", "snmpc_expr", "r2", "closed_loop", "disturbances",
+                            "log_file"]
+    if "log_file" in what:
+        make_log_file()
     if "disturbances" in what:
         make_disturbances()
     if "replay_hard" in what:

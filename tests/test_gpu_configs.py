@@ -355,7 +355,7 @@ def test_bench_self_launched_world_size_1_rccl():
 
 
 def test_bench_line_carries_the_other_configurations():
-    """the default N = 1 line of bench.py carries a bounded leg for each of the other BASELINE configurations and for the coupled SNMPC OCP
+    """the --full N = 1 line of bench.py carries a bounded leg for each of the other BASELINE configurations and for the coupled SNMPC OCP
     (`other_configs`: what the driver times next to the headline): all five present, every instance solved, rates in the range the
     separate runs of the same configurations give (profiles/r06_configs.jsonl, r06_snmpc_bench.txt)"""
     import json
@@ -365,7 +365,8 @@ def test_bench_line_carries_the_other_configurations():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_SELF_LAUNCH", "BENCH_SELF_LAUNCHED"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-schedule-legs", "--no-host-legs"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-schedule-legs",
+           "--no-host-legs"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][0])

@@ -376,6 +376,9 @@ class _StandInSolver:
     def get_stats(self, f):
         return self.res[:, 3].astype(int) if f == "status" else self.res[:, 4].astype(int)
 
+    def get_cost(self):
+        return self.res[:, 2].copy()
+
     def get_iterate(self):
         return None, np.zeros((self.B, self.N, 2))
 
@@ -457,12 +460,13 @@ def test_bench_control_flow_world2_gloo(scaling):
         lo += sz
 
 
-def test_bench_launches_its_own_ranks_world2_gloo():
+def test_bench_launches_its_own_ranks_world2_gloo(tmp_path):
     """`python bench.py --gpus 2` with NO launcher around it (the shape of the driver's BENCH command with a larger N): bench.py
     starts its two ranks itself (bench.self_launch: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR = 127.0.0.1 / a free port, as
     torch.distributed.run sets them), the ranks form a process group (gloo here, with the stand-in solver the test supplies through
     TUM_BENCH_TEST_SOLVER; nccl = RCCL on GPUs), rank 0 prints the ONE JSON line, exit code 0. Round 5's bench.py exited with
-    "launch with torch.distributed.run" here."""
+    "launch with torch.distributed.run" here. --dump-outputs: rank 0 writes its capsule's results and the summary of all 96 instances as the
+    rooted gather delivered it."""
     import json
     import subprocess
     env = dict(os.environ, TUM_BENCH_TEST_SOLVER="test_host_logic:_StandInSolver",
@@ -470,7 +474,7 @@ def test_bench_launches_its_own_ranks_world2_gloo():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_SELF_LAUNCHED"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "4", "--horizon", "6",
-           "--batch", "48", "--streams", "2", "--no-cpu-baseline"]
+           "--batch", "48", "--streams", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -485,6 +489,13 @@ def test_bench_launches_its_own_ranks_world2_gloo():
     assert o["value"] <= sum(o["per_rank"]["value"]) * (1 + 1e-9)          # the job's rate is set by the slowest rank
     assert o["gather_ms_per_step"] >= 0 and o["status_ok_frac"] == 1.0
     assert "stand-in" in o["data"] and o["cpu_baseline"] is None
+    g = np.load(tmp_path / "gathered_summary.npy")
+    assert g.shape == (96, 5) and g.dtype == np.float64
+    from tum_control_amd.workloads import config_groups
+    x0, _, _ = config_groups(4, 0, 6, 6, N=6, variant=3)          # the last timed step's batch, both shards in rank order
+    np.testing.assert_allclose(g[:, 2], x0.sum(axis=1), rtol=1e-15)
+    np.testing.assert_array_equal(g[:, 4], 5 + (np.tile(np.arange(48), 2) % 3))
+    np.testing.assert_array_equal(g[:48, 2], np.load(tmp_path / "cost.npy"))
 
 
 def test_bench_self_launch_propagates_a_failing_rank():
@@ -500,6 +511,57 @@ def test_bench_self_launch_propagates_a_failing_rank():
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if '"metric"' in ln]
 
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full (stand-in solver on CPU): exactly --steps timed steps, none of the --full legs in the line;
+    --dump-outputs writes what the last timed step computed as float64 .npy files, the same ones for the same arguments. Beyond the size
+    limit every array keeps the same seeded sample of its rows."""
+    import json
+    import subprocess
+    import bench
+    from tum_control_amd.workloads import config_groups
+    env = dict(os.environ, TUM_BENCH_TEST_SOLVER="test_host_logic:_StandInSolver",
+               PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests"), ROOT, os.environ.get("PYTHONPATH", "")]))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_SELF_LAUNCH", "BENCH_SELF_LAUNCHED"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "4", "--horizon", "6",
+               "--batch", "48", "--streams", "2", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+        assert len(lines) == 1, r.stdout[-2000:]
+        o = json.loads(lines[0])
+        assert o["steps"] == 3 and o["full"] is False and o["launch"] == "single process"
+        assert o["value"] > 0 and abs(o["value"] * o["ms_per_step"] * 1e-3 - 48) < 1e-6 * 48
+        for k in ("other_configs", "n38", "cpu_baseline", "parity_vs_oracle_max_abs_u0"):
+            assert k not in o, k
+        assert o["value_single_stream"] is None and o["value_host_visible"] is None and o["value_repeated_batch"] is None
+        assert o["roofline"]["dominant"] is None
+        got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert sorted(got) == ["U", "cost", "qp_iter", "status"] and all(a.dtype == np.float64 for a in got.values())
+        dumps.append(got)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
+    # the last timed step solved fresh batch 3 (variant (steps - 1) mod nb + 1) on capsule 1 (four steps over two capsules)
+    x0, _, _ = config_groups(4, 0, 3, 3, N=6, variant=3)
+    np.testing.assert_allclose(dumps[0]["cost"], x0.sum(axis=1), rtol=1e-15)
+    np.testing.assert_array_equal(dumps[0]["qp_iter"], 5 + (np.arange(48) % 3))
+    # the size limit: 1000 x (8 + 1) doubles + 1000 x 2 doubles + index files > 40 kB
+    arrays = {"a": np.arange(8000.0).reshape(1000, 8), "b": np.arange(1000.0), "c": np.arange(2000.0).reshape(1000, 2)}
+    for run in range(2):
+        bench.write_outputs(str(tmp_path / f"cut{run}"), arrays, limit=40000)
+    files = sorted(os.listdir(tmp_path / "cut0"))
+    assert files == ["a.npy", "a_rows.npy", "b.npy", "b_rows.npy", "c.npy", "c_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "cut0" / f) for f in files) <= 40000
+    rows = np.load(tmp_path / "cut0" / "a_rows.npy")
+    assert 0 < len(rows) < 1000 and (np.diff(rows) > 0).all()
+    for name in ("a", "b", "c"):
+        np.testing.assert_array_equal(np.load(tmp_path / "cut0" / f"{name}_rows.npy"), rows)
+        np.testing.assert_array_equal(np.load(tmp_path / "cut0" / f"{name}.npy"), arrays[name][rows.astype(int)])
+        np.testing.assert_array_equal(np.load(tmp_path / "cut0" / f"{name}.npy"), np.load(tmp_path / "cut1" / f"{name}.npy"))
 
 def test_workload_variants_are_fresh_batches_of_the_same_workload():
     """variant 0 is the BASELINE configuration; variants k > 0 (what bench.py rotates through) differ from it and from each
@@ -598,12 +660,10 @@ def test_disturbance_generators_match_the_reference(golden_dir):
 def test_log_file_has_the_reference_schema(tmp_path, golden_dir):
     """closed_loop.log_file_arrays writes what Logger.save_logs writes (Utils/Logging_Plotting.py:357-372): every key a reader of the
     reference's full_logs.npz / _baseline/F/<track>/<k>.npz finds, with the reference's shapes and derived channels -- checked on a logged
-    acados loop: rebuilt from its five raw logs, the derived arrays must equal the ones the reference stored in the same file."""
+    acados loop (tests/golden/log_file_lvms_3.npz, the reference's file of loop 3 on LVMS): rebuilt from its five raw logs, the derived
+    arrays must equal the ones the reference stored in the same file."""
     from tum_control_amd import closed_loop as cl
-    ref_file = "/root/reference/Learning_To_Adapt/SafeRL_WMPC/_baseline/F/lvms/3.npz"
-    if not os.path.exists(ref_file):
-        pytest.skip("needs the reference's logged loops (build container only)")
-    r = np.load(ref_file)
+    r = np.load(os.path.join(golden_dir, "log_file_lvms_3.npz"))
     assert set(cl.LOG_KEYS) == set(r.files)
     # a batch of one vehicle; the file holds 5499 of the 5500 steps that were run (Logger.truncate): give the last one back as a copy
     raw = {k: r[k][:, None] for k in ("CiLX", "MPC_SimX", "simU", "simREF", "simSolverDebug")}
