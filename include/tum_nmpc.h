@@ -129,16 +129,31 @@ int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const double *v, 
  * the solve is timed by the device's wall clock (get_stats "time_tot") and the events around the interior point kernel are left out
  * (get_stats "time_ipm" needs tum_ocp_set_kernel(c, "time-ipm")). */
 int tum_ocp_solve(tum_ocp *c);
-/* Asynchronous flavour for benchmarking / pipelining: enqueue on the capsule's stream, no host sync. */
+/* Asynchronous flavour for benchmarking / pipelining: enqueue on the capsule's stream, no host sync.
+ * In SQP mode (tum_ocp_options_set) it returns behind the enqueue of the last iteration: the host reads the number of active
+ * instances between two iterations. */
 int tum_ocp_solve_async(tum_ocp *c);
+/* acados_solver.options_set(field, value) for the NLP solver (acados_ocp_SNMPC.json: nlp_solver_*; globalization FIXED_STEP):
+ * "nlp_solver_type"        0 SQP_RTI (default: one QP per solve, as before), 1 SQP (full solves)
+ * "nlp_solver_max_iter"    1..10000 QPs per SQP solve (default 100)
+ * "nlp_solver_tol_stat" | "nlp_solver_tol_eq" | "nlp_solver_tol_ineq" | "nlp_solver_tol_comp"   >= 0 (default 1e-6 each)
+ * "nlp_solver_step_length" in (0, 1] (default 1)
+ * An SQP solve evaluates the four NLP residuals of every instance at each iterate (after its linearisation, with the previous QP's
+ * multipliers), stops an instance whose residuals are all below their tolerances and ends when none is active or after max_iter QPs.
+ * Per-instance status: 0 converged, 2 max_iter reached (ACADOS_MAXITER), 4 a QP failed (the iterate stays at the last good one).
+ * SQP is refused for a capsule with the R2NMPC tightening attached, for the coupled SNMPC OCP, for the development kernels "fused" /
+ * "pipeline4", by tum_ocp_step_async and by the device closed loop (tum_sim_*): those stay SQP-RTI. */
+int tum_ocp_options_set(tum_ocp *c, const char *field, double value);
 int tum_ocp_synchronize(tum_ocp *c);
 
 /* acados_solver.get_cost()   NMPC_class.py:202 */
 int tum_ocp_get_cost(tum_ocp *c, double *out, int b0, int nb);
 /* acados_solver.get_stats(field)   NMPC_class.py:203-205
  * "time_tot" -> 1 double, device seconds of the last solve (HIP events on the capsule's stream)
- * "sqp_iter" -> nb ints (always 1), "qp_iter" -> nb ints, "status" -> nb ints, "qp_status" -> nb ints
- * "res" -> nb x 3 doubles (stat, ineq, comp residuals of the last QP). */
+ * "sqp_iter" -> nb ints (1 after an SQP-RTI solve; the QPs each instance solved after an SQP solve), "qp_iter" -> nb ints,
+ * "status" -> nb ints, "qp_status" -> nb ints
+ * "res" -> nb x 3 doubles (stat, ineq, comp residuals of the last QP)
+ * "residuals" -> nb x 4 doubles (stat, eq, ineq, comp residuals of the NLP at the returned iterate; after an SQP solve only). */
 int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b0, int nb);
 /* acados_solver.reset()   NMPC_class.py:251 -- zero the iterate of every instance */
 int tum_ocp_reset(tum_ocp *c);

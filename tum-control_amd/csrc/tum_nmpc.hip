@@ -19,6 +19,7 @@
 #endif
 #include "aux_kernels.hpp"
 #include "loop_kernels.hpp"
+#include "sqp_kernels.hpp"
 
 using namespace tum;
 
@@ -82,6 +83,11 @@ struct tum_ocp {
     double *hsum_s, *hX_s, *hU_s; unsigned long long *hts_s; bool cache_valid;                 // results of the last synchronous solve
     double *hXS_s; bool xs_cached;                                                             // ... and the sample copies of an SNMPC capsule, read back on first use
     bool time_ipm;                     // keep the events around the interior point kernel also where the library leaves them out (tum_ocp_set_kernel "time-ipm")
+    // full SQP solves (tum_ocp_options_set): the options, the device state of the loop (allocated by the first SQP solve), whether the
+    // LAST solve was one
+    int nlp_type, nlp_max_iter; double nlp_tol[4], nlp_alpha;
+    double *dnlpres, *dsnap; int *dsqpstate, *dsqpiter, *dsnapi; unsigned *dactive, *hactive; int active_cap; hipEvent_t evpoll[2];
+    bool solved_sqp;
 };
 
 static const int DBG_STRIDE = 20480;
@@ -146,6 +152,10 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
     c->dsum = nullptr; c->res_head = c->res_count = 0;
     c->hin_s = c->hsum_s = c->hX_s = c->hU_s = nullptr; c->hts_s = nullptr; c->in_mask = 0; c->in_x0 = c->in_inflight = false; c->ev_in = nullptr;
     c->cache_valid = false; c->time_ipm = false; c->hXS_s = nullptr; c->xs_cached = false;
+    // (defaults of the reference's generated solver, acados_ocp_SNMPC.json: SQP_RTI; for SQP 100 iterations, tolerances 1e-6, full steps)
+    c->nlp_type = 0; c->nlp_max_iter = 100; for (double &t : c->nlp_tol) t = 1e-6; c->nlp_alpha = 1.0;
+    c->dnlpres = c->dsnap = nullptr; c->dsqpstate = c->dsqpiter = c->dsnapi = nullptr; c->dactive = c->hactive = nullptr; c->active_cap = 0;
+    c->evpoll[0] = c->evpoll[1] = nullptr; c->solved_sqp = false;
     for (int i = 0; i < 2; i++) { c->hsum[i] = c->hX[i] = c->hU[i] = c->hin[i] = nullptr; c->hts[i] = nullptr; c->evres[i] = nullptr; c->res_iter[i] = false; }
     const int N = c->N; const size_t B = c->batch;
     bool ok = true;
@@ -263,6 +273,9 @@ extern "C" void tum_ocp_free(tum_ocp *c)
     (void)hipFree(c->dXS); (void)hipFree(c->dxs0); (void)hipFree(c->dApce); (void)hipFree(c->dws2); (void)hipFree(c->dpro); (void)hipFree(c->ddv); (void)hipFree(c->doffs); (void)hipFree(c->dxs_dirty);
     (void)hipFree(c->dr2S); (void)hipFree(c->dr2B); (void)hipFree(c->dpceA); (void)hipFree(c->dbnd_snap);
     (void)hipFree(c->dsum);
+    (void)hipFree(c->dnlpres); (void)hipFree(c->dsnap); (void)hipFree(c->dsqpstate); (void)hipFree(c->dsqpiter); (void)hipFree(c->dsnapi); (void)hipFree(c->dactive);
+    if (c->hactive) (void)hipHostFree(c->hactive);
+    for (hipEvent_t e : c->evpoll) if (e) (void)hipEventDestroy(e);
     if (c->hin_s) (void)hipHostFree(c->hin_s);
     if (c->hsum_s) (void)hipHostFree(c->hsum_s);
     if (c->hX_s) (void)hipHostFree(c->hX_s);
@@ -940,7 +953,9 @@ static void launch_lin_ahead(tum_ocp *c, hipStream_t st)
     c->lin_ahead = true;          // the next launch_pipeline skips its linearisation and tells the condensing kernel (consumed there)
 }
 
-static int launch_pipeline(tum_ocp *c, bool events)
+// part: 1 the linearisation and the condensing, 2 the interior point method and the expansion, 3 both (an SQP-RTI solve;
+// a full SQP solve puts its residual pass between the two, launch_sqp)
+static int launch_pipeline(tum_ocp *c, bool events, int part = 3)
 {
     PArgs pa;
     pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
@@ -950,6 +965,7 @@ static int launch_pipeline(tum_ocp *c, bool events)
     const bool cols = use_lin_cols(c);
     const dim3 g_cols((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), g_lane((unsigned)((items + 63) / 64));
     const bool lin_done = c->lin_ahead;
+    if (part & 1) {
     c->lin_ahead = false;
     if (lin_done) pa.ka.flags |= 8;          // (launch_lin_ahead ran it on another stream; the caller has joined that stream)
     else if (c->sn) {   // coupled SNMPC OCP: sample fan-out and prologue first, the QP solution goes to the epilogue through the workspace
@@ -962,6 +978,7 @@ static int launch_pipeline(tum_ocp *c, bool events)
         if (cols) hipLaunchKernelGGL(lin_cols_kernel<false>, g_cols, dim3(64), 0, c->stream, pa);
         else hipLaunchKernelGGL(lin_kernel<false>, g_lane, dim3(64), 0, c->stream, pa);
     }
+    }
     // (development aid: a larger LDS request lowers the number of OCPs that share a CU)
     // The expansion as the tail of the interior point kernel pays where a batch is at most one round of resident wavefronts (one
     // launch less: 0.424 against 0.432 ms per solve() call at 26 instances, 0.457 against 0.469 at 1024); beyond that its
@@ -973,7 +990,7 @@ static int launch_pipeline(tum_ocp *c, bool events)
     auto rest = [&](auto ntc) {
         constexpr int NTv = decltype(ntc)::value;
         const int ipm_lds = lds_req > PD<NTv>::I_LDS_BYTES ? lds_req : PD<NTv>::I_LDS_BYTES;
-        {
+        if (part & 1) {
             // six wavefronts per OCP while every OCP can have a CU's LDS to itself (cond_wide_kernel)
             const bool wide = use_cond_wide(c);
             if constexpr (NTv == 7) {      // N = 49..56: a diagonal W, one wavefront per OCP at every batch size
@@ -990,6 +1007,7 @@ static int launch_pipeline(tum_ocp *c, bool events)
             else hipLaunchKernelGGL((cond_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
             }
         }
+        if (!(part & 2)) return;
         if ((events && !c->skip_ipm_events) || c->time_ipm) (void)hipEventRecord(c->evi0, c->stream);
         bool expanded = false;
 #ifdef TUM_DEV_KERNELS
@@ -1073,8 +1091,132 @@ static int launch(tum_ocp *c, bool events = true)
     }
     c->solved = true;
     c->solved_pipe = c->pipe;
+    c->solved_sqp = false;
     c->ipm_timed = (events && !c->skip_ipm_events) || c->time_ipm;
     c->ts_slot = -1;          // (tum_ocp_step_async sets it behind this call)
+    return 0;
+}
+
+// ---- full SQP solves (nlp_solver_type SQP)
+// acados' option fields (acados_ocp_SNMPC.json: nlp_solver_type, nlp_solver_max_iter, nlp_solver_tol_*, nlp_solver_step_length); globalization
+// is FIXED_STEP
+extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
+{
+    if (!c || !field) return fail("null argument");
+    const std::string f(field);
+    if (!(value == value)) return fail("options_set " + f + ": NaN");
+    if (f == "nlp_solver_type") {
+        if (value != 0.0 && value != 1.0) return fail("options_set nlp_solver_type: 0 (SQP_RTI) or 1 (SQP)");
+        if (value == 1.0) {
+            if (c->r2) return fail("options_set nlp_solver_type: SQP is not available for a capsule with the R2NMPC tightening attached (SQP_RTI only, as Reduced_Robustified_NMPC_class.py requires)");
+            if (c->sn) return fail("options_set nlp_solver_type: SQP is not available for the coupled SNMPC OCP (SQP_RTI only)");
+        }
+        c->nlp_type = (int)value;
+        return 0;
+    }
+    if (f == "nlp_solver_max_iter") {
+        if (!(value >= 1.0 && value <= 10000.0) || value != std::floor(value)) return fail("options_set nlp_solver_max_iter: an integer in 1..10000");
+        c->nlp_max_iter = (int)value;
+        return 0;
+    }
+    const char *tols[4] = {"nlp_solver_tol_stat", "nlp_solver_tol_eq", "nlp_solver_tol_ineq", "nlp_solver_tol_comp"};
+    for (int i = 0; i < 4; i++)
+        if (f == tols[i]) {
+            if (!(value >= 0.0) || std::isinf(value)) return fail("options_set " + f + ": a finite value >= 0");
+            c->nlp_tol[i] = value;
+            return 0;
+        }
+    if (f == "nlp_solver_step_length") {
+        if (!(value > 0.0 && value <= 1.0)) return fail("options_set nlp_solver_step_length: in (0, 1]");
+        c->nlp_alpha = value;
+        return 0;
+    }
+    return fail("options_set: unknown field '" + f + "' (nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
+                "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length)");
+}
+
+// One full SQP solve: [lin, cond, residuals] then, while an instance is active and the cap is not reached, [snapshot, ipm, expand,
+// commit, lin, cond, residuals]. The host reads the number of active instances of every residual pass (a 4-byte copy into pinned
+// memory behind an event), one iteration behind the GPU; the kernels of the pipeline are the RTI's, launched as an SQP-RTI solve
+// launches them.
+static int launch_sqp(tum_ocp *c)
+{
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (c->r2) return fail("solve: SQP is not available for a capsule with the R2NMPC tightening attached (nlp_solver_type SQP_RTI only)");
+    if (c->sn) return fail("solve: SQP is not available for the coupled SNMPC OCP (nlp_solver_type SQP_RTI only)");
+    if (c->ka.flags & 6) return fail("solve: SQP does not run with the debug dump or the phase timers");
+    if (resolve_kernel(c)) return 1;
+    if (!c->pipe) return fail("solve: SQP runs on the pipeline only, not on the development kernel 'fused'");
+#ifdef TUM_DEV_KERNELS
+    if (c->kmode == 3) return fail("solve: SQP runs on the pipeline only, not on the development kernel 'pipeline4'");
+#endif
+    const size_t B = c->batch; const int N = c->N;
+    const int snap_len = (N + 1) * NX + N * NU + (6 * N + 2) + 6 * N + 4;
+    if (!c->dnlpres) {
+        if (dalloc(&c->dnlpres, B * 4) != hipSuccess || dalloc(&c->dsnap, B * snap_len) != hipSuccess || dalloc(&c->dsqpstate, B) != hipSuccess ||
+            dalloc(&c->dsqpiter, B) != hipSuccess || dalloc(&c->dsnapi, B * 3) != hipSuccess) return fail("solve: device allocation failed (SQP)");
+        HIPCHK(hipEventCreateWithFlags(&c->evpoll[0], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&c->evpoll[1], hipEventDisableTiming));
+    }
+    if (c->active_cap < c->nlp_max_iter + 1) {
+        (void)hipFree(c->dactive); c->dactive = nullptr;
+        if (c->hactive) { (void)hipHostFree(c->hactive); c->hactive = nullptr; }
+        if (dalloc(&c->dactive, (size_t)c->nlp_max_iter + 1) != hipSuccess) return fail("solve: device allocation failed (SQP)");
+        HIPCHK(hipHostMalloc((void **)&c->hactive, 2 * sizeof(unsigned), hipHostMallocDefault));
+        c->active_cap = c->nlp_max_iter + 1;
+    }
+    c->cache_valid = false; c->xs_cached = false;
+    if (flush_inputs(c)) return 1;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    c->ka.order = (c->lpt && c->order_valid && c->batch > 1024) ? c->dorder : nullptr;
+    HIPCHK(hipMemsetAsync(c->dsqpstate, 0, sizeof(int) * B, c->stream));
+    HIPCHK(hipMemsetAsync(c->dsqpiter, 0, sizeof(int) * B, c->stream));
+    HIPCHK(hipMemsetAsync(c->dactive, 0, sizeof(unsigned) * (size_t)(c->nlp_max_iter + 1), c->stream));
+    SqpArgs sq;
+    sq.res_nlp = c->dnlpres; sq.state = c->dsqpstate; sq.sqp_iter = c->dsqpiter; sq.active = c->dactive;
+    sq.snap = c->dsnap; sq.snapi = c->dsnapi; sq.snap_len = snap_len;
+    sq.tol_stat = c->nlp_tol[0]; sq.tol_eq = c->nlp_tol[1]; sq.tol_ineq = c->nlp_tol[2]; sq.tol_comp = c->nlp_tol[3];
+    sq.alpha = c->nlp_alpha; sq.cost = c->nlp_alpha != 1.0 ? 1 : 0;
+    PArgs pa;
+    pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
+    const int nt = tiles_of(c);
+    auto residuals = [&](int pass) {
+        sq.pass = pass; sq.last = (pass == c->nlp_max_iter) ? 1 : 0;
+        if (launch_pipeline(c, false, 1)) return 1;
+        if (nt == 7) hipLaunchKernelGGL(nlp_residual_kernel<7>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
+        else if (nt == 6) hipLaunchKernelGGL(nlp_residual_kernel<6>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
+        else hipLaunchKernelGGL(nlp_residual_kernel<5>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    // the count of residual pass p goes to the pinned word p & 1 behind event p & 1
+    auto count_copy = [&](int p) {
+        HIPCHK(hipMemcpyAsync(c->hactive + (p & 1), c->dactive + p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipEventRecord(c->evpoll[p & 1], c->stream));
+        return 0;
+    };
+    if (residuals(0) || count_copy(0)) return 1;
+    // The host reads the count of pass `it` while the GPU runs iteration `it`, which is enqueued in front of the read: the stream never
+    // waits for the host. When the count says that no instance was active any more, that iteration was a ride-along of finished
+    // instances only -- the commit kernel has put every one of them back -- and the solve ends behind it.
+    for (int it = 0; it < c->nlp_max_iter; it++) {
+        hipLaunchKernelGGL(sqp_snapshot_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq);
+        if (launch_pipeline(c, false, 2)) return 1;
+        hipLaunchKernelGGL(sqp_commit_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq);
+        HIPCHK(hipGetLastError());
+        if (residuals(it + 1) || count_copy(it + 1)) return 1;
+        HIPCHK(hipEventSynchronize(c->evpoll[it & 1]));
+        if (c->hactive[it & 1] == 0) break;
+    }
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    if (c->lpt && c->batch > 1024) {
+        hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->dqpiter, c->dorder, c->batch);
+        HIPCHK(hipGetLastError());
+        c->order_valid = true;
+    }
+    c->solved = true; c->solved_pipe = true; c->solved_sqp = true;
+    c->ipm_timed = c->time_ipm;
+    c->ts_slot = -1;
     return 0;
 }
 
@@ -1090,6 +1232,7 @@ extern "C" int tum_ocp_set_schedule(tum_ocp *c, int longest_first)
 extern "C" int tum_ocp_solve_async(tum_ocp *c)
 {
     if (!c) return fail("null capsule");
+    if (c->nlp_type) return launch_sqp(c);          // (the host reads the active count between iterations: returns behind the last QP)
     return launch(c);
 }
 extern "C" int tum_ocp_synchronize(tum_ocp *c)
@@ -1104,6 +1247,15 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
 {
     if (!c) { fail("null capsule"); return -1; }
     DevGuard guard(c->d.device); if (!guard.ok) { fail("hipSetDevice failed"); return -1; }
+    if (c->nlp_type) {
+        if (launch_sqp(c)) return -1;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
+        std::vector<int> st(c->batch);
+        if (hipMemcpy(st.data(), c->dstatus, sizeof(int) * c->batch, hipMemcpyDeviceToHost) != hipSuccess) { fail("status copy failed"); return -1; }
+        int mx = 0;
+        for (int s : st) if (s > mx) mx = s;
+        return mx;
+    }
     if (small_inputs(c) && results_pack_all(c, 1)) {
         // small capsule: [pending setters up + device clock] -> solve -> [summary, X, U into pinned slabs + device clock], ONE wait. No
         // event and no copy command on the stream; the getters that follow read the slabs (cache_valid).
@@ -1184,7 +1336,8 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
         *(double *)out = ms * 1e-3; return 0;
     }
     if (chk_range(c, b0, nb)) return 1;
-    if (f == "sqp_iter") { int *o = (int *)out; for (int i = 0; i < nb; i++) o[i] = 1; return 0; }
+    if (f == "sqp_iter" && !c->solved_sqp) { int *o = (int *)out; for (int i = 0; i < nb; i++) o[i] = 1; return 0; }      // (SQP-RTI: one QP per solve)
+    if (f == "residuals" && !c->solved_sqp) return fail("get_stats residuals: computed by a full SQP solve only (options_set nlp_solver_type 1)");
     if (c->cache_valid && (f == "qp_iter" || f == "status")) {
         int *o = (int *)out; const int col = (f == "status") ? 3 : 4;
         for (int i = 0; i < nb; i++) o[i] = (int)c->hsum_s[(size_t)(b0 + i) * 5 + col];
@@ -1196,6 +1349,8 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
     if (f == "status") { HIPCHK(hipMemcpy(out, c->dstatus + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "qp_status") { HIPCHK(hipMemcpy(out, c->dqpstatus + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "res") { HIPCHK(hipMemcpy(out, c->dres + (size_t)b0 * 3, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost)); return 0; }
+    if (f == "sqp_iter") { HIPCHK(hipMemcpy(out, c->dsqpiter + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
+    if (f == "residuals") { HIPCHK(hipMemcpy(out, c->dnlpres + (size_t)b0 * 4, sizeof(double) * 4 * nb, hipMemcpyDeviceToHost)); return 0; }
     return fail("get_stats: unknown field '" + f + "'");
 }
 
@@ -1377,6 +1532,7 @@ extern "C" int tum_ocp_step_async(tum_ocp *c, const double *x0, const double *yr
 {
     if (!c) return fail("null capsule");
     DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (c->nlp_type) return fail("step_async: one SQP-RTI iteration per step; a capsule in SQP mode (nlp_solver_type 1) takes tum_ocp_solve");
     if (c->res_count == 2) return fail("step_async: two requests outstanding on this capsule (call tum_ocp_results_wait first)");
     if (flush_inputs(c)) return 1;          // (setters older than this step's inputs)
     const size_t B = c->batch, nx0 = B * NX, nyr = B * (size_t)(c->N + 1) * 6;
@@ -1750,6 +1906,7 @@ extern "C" tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track,
     if (!c || !track || !windows) { fail("null argument"); return nullptr; }
     if (n_track < 2 || !(Tp > 0) || !(Ts > 0) || n_elem < 1 || log_capacity < 0) { fail("sim_create: bad arguments"); return nullptr; }
     for (int i = 0; i < 8; i++) if (windows[i] < 1 || windows[i] > 4) { fail("sim_create: estimator windows must be 1..4"); return nullptr; }
+    if (c->nlp_type) { fail("sim_create: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)"); return nullptr; }
     DevGuard guard(c->d.device); if (!guard.ok) { fail("hipSetDevice failed"); return nullptr; }
     if (c->sn) {   // the state estimator writes the nominal x0 only: the samples follow by fan-out
         if (!c->have_offs) { fail("sim_create: an SNMPC capsule needs its sample offsets (tum_ocp_snmpc_set_offsets)"); return nullptr; }
@@ -1877,6 +2034,7 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
 {
     if (!s || nsteps < 0) return fail("bad argument");
     tum_ocp *c = s->c;
+    if (c->nlp_type) return fail("sim_run: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     c->cache_valid = false;
     if (flush_inputs(c)) return 1;            // (pending host setters go up before anything is captured)

@@ -67,7 +67,7 @@ def dev_library():
 # every symbol include/tum_nmpc.h declares (tests/test_cabi.py checks the .so exports them all)
 C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_batch", "tum_ocp_horizon",
              "tum_ocp_set", "tum_ocp_get", "tum_ocp_constraints_set", "tum_ocp_cost_set",
-             "tum_ocp_solve", "tum_ocp_solve_async", "tum_ocp_synchronize",
+             "tum_ocp_solve", "tum_ocp_solve_async", "tum_ocp_synchronize", "tum_ocp_options_set",
              "tum_ocp_get_cost", "tum_ocp_get_stats", "tum_ocp_reset", "tum_ocp_get_from_qp_in",
              "tum_ocp_set_stream", "tum_ocp_get_device", "tum_ocp_put_device", "tum_ocp_bind_device", "tum_ocp_results_async", "tum_ocp_results_wait", "tum_ocp_results_outstanding", "tum_ocp_step_async", "tum_ocp_cold_start", "tum_ocp_last_kernel_ms",
              "tum_ocp_debug_dump", "tum_ocp_profile_phases", "tum_ocp_set_schedule", "tum_ocp_set_kernel",
@@ -107,6 +107,8 @@ def load_library(path=None):
     L.tum_ocp_get.argtypes = [vp, ci, cs, vp, ci, ci, ci, ci]
     L.tum_ocp_get_from_qp_in.argtypes = [vp, ci, cs, dp, ci, ci, ci, ci]
     L.tum_ocp_solve.argtypes = [vp]; L.tum_ocp_solve_async.argtypes = [vp]; L.tum_ocp_synchronize.argtypes = [vp]
+    if hasattr(L, "tum_ocp_options_set"):
+        L.tum_ocp_options_set.argtypes = [vp, cs, ctypes.c_double]
     L.tum_ocp_get_cost.argtypes = [vp, dp, ci, ci]
     L.tum_ocp_get_stats.argtypes = [vp, cs, vp, ci, ci]
     L.tum_ocp_reset.argtypes = [vp]; L.tum_ocp_cold_start.argtypes = [vp]
@@ -188,6 +190,10 @@ def _dp(a):
 
 
 _FIELD_BYTES = {}          # field name -> bytes, encoded once
+# acados' defaults of the NLP solver options as the reference's generated solver carries them (acados_ocp_SNMPC.json)
+_NLP_DEFAULTS = dict(nlp_solver_max_iter=100, nlp_solver_tol_stat=1e-6, nlp_solver_tol_eq=1e-6, nlp_solver_tol_ineq=1e-6,
+                     nlp_solver_tol_comp=1e-6, nlp_solver_step_length=1.0)
+_NLP_TYPES = {"SQP_RTI": 0, "SQP": 1}
 
 
 class BatchedOcpSolver:
@@ -195,7 +201,8 @@ class BatchedOcpSolver:
 
     def __init__(self, N=38, dt=0.08, nsub=3, batch=1, device=0, cfg=None, store_qp_in=False,
                  qp_iter_max=50, qp_tol=(1e-8, 1e-8, 1e-8), qp_mu0=0.05, qp_t0=0.05, qp_warm_start=None, qp_warm_mu=0.0,
-                 qp_warm_flips=0, qp_warm_viol=0.0):
+                 qp_warm_flips=0, qp_warm_viol=0.0, nlp_solver_type="SQP_RTI", nlp_solver_max_iter=100, nlp_solver_tol_stat=1e-6,
+                 nlp_solver_tol_eq=1e-6, nlp_solver_tol_ineq=1e-6, nlp_solver_tol_comp=1e-6, nlp_solver_step_length=1.0):
         self._L = load_library()
         self.N, self.dt, self.nsub, self.batch = int(N), float(dt), int(nsub), int(batch)
         self.cfg = cfg or _config.default_config()
@@ -211,6 +218,14 @@ class BatchedOcpSolver:
         if not self._h:
             raise RuntimeError("tum_ocp_create failed: " + self._err())
         self.status = 0
+        # NLP solver options (acados_ocp_SNMPC.json: nlp_solver_*); the defaults leave the capsule as created -- SQP_RTI
+        nlp = dict(nlp_solver_max_iter=nlp_solver_max_iter, nlp_solver_tol_stat=nlp_solver_tol_stat, nlp_solver_tol_eq=nlp_solver_tol_eq,
+                   nlp_solver_tol_ineq=nlp_solver_tol_ineq, nlp_solver_tol_comp=nlp_solver_tol_comp, nlp_solver_step_length=nlp_solver_step_length)
+        for k, v in nlp.items():
+            if v != _NLP_DEFAULTS[k]:
+                self.options_set(k, v)
+        if nlp_solver_type != "SQP_RTI":
+            self.options_set("nlp_solver_type", nlp_solver_type)
 
     # ------------------------------------------------------------------ plumbing
     def _err(self):
@@ -292,6 +307,19 @@ class BatchedOcpSolver:
         self.status = st
         return st
 
+    def options_set(self, field, value):
+        """acados_solver.options_set(field, value) for the NLP solver: 'nlp_solver_type' ('SQP_RTI' | 'SQP'), 'nlp_solver_max_iter',
+        'nlp_solver_tol_stat' | '_eq' | '_ineq' | '_comp', 'nlp_solver_step_length' (include/tum_nmpc.h, tum_ocp_options_set)"""
+        if field == "nlp_solver_type" and isinstance(value, str):
+            if value not in _NLP_TYPES:
+                raise Exception(f"BatchedOcpSolver.options_set: nlp_solver_type must be one of {sorted(_NLP_TYPES)}, got '{value}'")
+            value = _NLP_TYPES[value]
+        self._chk(self._L.tum_ocp_options_set(self._h, field.encode(), float(value)), "options_set")
+
+    def get_residuals(self):
+        """acados_solver.get_residuals(): [stat, eq, ineq, comp] of the NLP at the iterate of the last SQP solve; (batch, 4) for a batch"""
+        return self.get_stats("residuals")
+
     def get_cost(self):
         out = np.zeros(self.batch)
         self._chk(self._L.tum_ocp_get_cost(self._h, _dp(out), 0, self.batch), "get_cost")
@@ -311,6 +339,10 @@ class BatchedOcpSolver:
         if field == "res":
             out = np.zeros((self.batch, 3))
             self._chk(self._L.tum_ocp_get_stats(self._h, b"res", out.ctypes.data_as(ctypes.c_void_p), 0, self.batch), "get_stats")
+            return self._out(out)
+        if field == "residuals":
+            out = np.zeros((self.batch, 4))
+            self._chk(self._L.tum_ocp_get_stats(self._h, b"residuals", out.ctypes.data_as(ctypes.c_void_p), 0, self.batch), "get_stats")
             return self._out(out)
         raise Exception(f"BatchedOcpSolver.get_stats: unknown field '{field}'")
 
