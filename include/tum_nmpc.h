@@ -95,7 +95,10 @@ int tum_ocp_horizon(const tum_ocp *c);
  * with the terminal record padded to 6). */
 int tum_ocp_set(tum_ocp *c, int stage, const char *field, const double *v, int len, int b0, int nb, int stride);
 /* acados_solver.get(stage, field)          NMPC_class.py:193,198; Reduced_Robustified_NMPC_class.py:280,298
- * field: "x", "u" (and the soft-constraint slacks of the last QP: "sl", "su", 3 per stage in acados order). */
+ * field: "x", "u" (and the soft-constraint slacks of the last QP: "sl", "su", 3 per stage in acados order);
+ * "lam": the multipliers of the last QP's rows, per stage the lower sides in the order of "sl", then the upper sides in the order of
+ * "su" -- 2 / 6 / 4 values at stage 0 / 1..N-1 / N. (acados appends the multipliers of the slack bounds; this getter does not.)
+ * After a full SQP solve they are the multipliers the reported residuals were evaluated with. */
 int tum_ocp_get(tum_ocp *c, int stage, const char *field, double *v, int len, int b0, int nb, int stride);
 
 /* acados_solver.constraints_set(stage, field, value)   NMPC_class.py:111-112,245-246;

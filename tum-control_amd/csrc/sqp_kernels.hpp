@@ -23,7 +23,8 @@ struct SqpArgs {
     double alpha;           // step length (nlp_solver_step_length)
     int pass;               // which counter of `active` this residual pass adds to
     int last;               // 1: no QP follows this pass (iteration cap): the instances still active end with status 2
-    int cost;               // 1: the cost of the iterate is evaluated here (alpha != 1: the expansion's is that of the full step)
+    int cost;               // 1: the cost of the iterate is evaluated here (alpha != 1: the expansion's is that of the full step; pass 0
+                            //    of a cold-started solve: an instance that converges there has no expansion)
 };
 
 // Residuals of the NLP at the current iterate, with the multipliers of the previous QP, in the condensed form the pipeline

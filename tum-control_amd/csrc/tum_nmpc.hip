@@ -88,6 +88,10 @@ struct tum_ocp {
     int nlp_type, nlp_max_iter; double nlp_tol[4], nlp_alpha;
     double *dnlpres, *dsnap; int *dsqpstate, *dsqpiter, *dsnapi; unsigned *dactive, *hactive; int active_cap; hipEvent_t evpoll[2];
     bool solved_sqp;
+    // no solve since the last cold start / reset: the multipliers and slacks on the device are those of an EARLIER problem. An SQP-RTI
+    // solve never reads them (the warm-start word is 0); a full SQP solve evaluates pass 0 with them and damps towards them, so it clears
+    // them first (acados' reset() zeroes them)
+    bool cold;
 };
 
 static const int DBG_STRIDE = 20480;
@@ -155,7 +159,7 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
     // (defaults of the reference's generated solver, acados_ocp_SNMPC.json: SQP_RTI; for SQP 100 iterations, tolerances 1e-6, full steps)
     c->nlp_type = 0; c->nlp_max_iter = 100; for (double &t : c->nlp_tol) t = 1e-6; c->nlp_alpha = 1.0;
     c->dnlpres = c->dsnap = nullptr; c->dsqpstate = c->dsqpiter = c->dsnapi = nullptr; c->dactive = c->hactive = nullptr; c->active_cap = 0;
-    c->evpoll[0] = c->evpoll[1] = nullptr; c->solved_sqp = false;
+    c->evpoll[0] = c->evpoll[1] = nullptr; c->solved_sqp = false; c->cold = true;
     for (int i = 0; i < 2; i++) { c->hsum[i] = c->hX[i] = c->hU[i] = c->hin[i] = nullptr; c->hts[i] = nullptr; c->evres[i] = nullptr; c->res_iter[i] = false; }
     const int N = c->N; const size_t B = c->batch;
     bool ok = true;
@@ -691,6 +695,25 @@ extern "C" int tum_ocp_get(tum_ocp *c, int stage, const char *field, double *v, 
         }
         return 0;
     }
+    if (f == "lam") {
+        // multipliers of the last QP's rows (acados appends those of the slack bounds; not kept here): per stage the lower sides in the
+        // order of sl, then the upper sides in the order of su
+        const int want = (stage == 0) ? 2 : (stage == N ? 4 : 6);
+        if (stage < 0 || stage > N || len != want) return fail("get lam: bad stage/len");
+        if (stride < len) return fail("stride < len");
+        const int nl = 6 * N + 2;
+        std::vector<double> all((size_t)nb * nl);
+        if (fetch(c, c->dqplam, nl, 0, all.data(), nl, b0, nb, nl)) return 1;
+        for (int i = 0; i < nb; i++) {
+            double *o = v + (size_t)i * stride; int n = 0;
+            for (int side = 0; side < 2; side++) {
+                const double *s = &all[(size_t)i * nl + (size_t)side * 3 * N];
+                if (stage < N) o[n++] = s[stage];
+                if (stage >= 1) { o[n++] = s[N + 2 * (stage - 1)]; o[n++] = s[N + 2 * (stage - 1) + 1]; }
+            }
+        }
+        return 0;
+    }
     return fail("get: unknown field '" + f + "'");
 }
 
@@ -1091,7 +1114,7 @@ static int launch(tum_ocp *c, bool events = true)
     }
     c->solved = true;
     c->solved_pipe = c->pipe;
-    c->solved_sqp = false;
+    c->solved_sqp = false; c->cold = false;
     c->ipm_timed = (events && !c->skip_ipm_events) || c->time_ipm;
     c->ts_slot = -1;          // (tum_ocp_step_async sets it behind this call)
     return 0;
@@ -1172,16 +1195,27 @@ static int launch_sqp(tum_ocp *c)
     HIPCHK(hipMemsetAsync(c->dsqpstate, 0, sizeof(int) * B, c->stream));
     HIPCHK(hipMemsetAsync(c->dsqpiter, 0, sizeof(int) * B, c->stream));
     HIPCHK(hipMemsetAsync(c->dactive, 0, sizeof(unsigned) * (size_t)(c->nlp_max_iter + 1), c->stream));
+    const bool cold = c->cold;
+    if (cold) {
+        // pass 0 of a cold-started solve: zero multipliers and slacks, whatever this capsule solved before -- and no QP statistics of an
+        // earlier problem for an instance that converges before its first QP (its cost is evaluated by pass 0)
+        HIPCHK(hipMemsetAsync(c->dqplam, 0, sizeof(double) * B * (6 * (size_t)N + 2), c->stream));
+        HIPCHK(hipMemsetAsync(c->dslack, 0, sizeof(double) * B * 6 * (size_t)N, c->stream));
+        HIPCHK(hipMemsetAsync(c->dres, 0, sizeof(double) * B * 3, c->stream));
+        HIPCHK(hipMemsetAsync(c->dqpiter, 0, sizeof(int) * B, c->stream));
+        HIPCHK(hipMemsetAsync(c->dqpstatus, 0, sizeof(int) * B, c->stream));
+    }
     SqpArgs sq;
     sq.res_nlp = c->dnlpres; sq.state = c->dsqpstate; sq.sqp_iter = c->dsqpiter; sq.active = c->dactive;
     sq.snap = c->dsnap; sq.snapi = c->dsnapi; sq.snap_len = snap_len;
     sq.tol_stat = c->nlp_tol[0]; sq.tol_eq = c->nlp_tol[1]; sq.tol_ineq = c->nlp_tol[2]; sq.tol_comp = c->nlp_tol[3];
-    sq.alpha = c->nlp_alpha; sq.cost = c->nlp_alpha != 1.0 ? 1 : 0;
+    sq.alpha = c->nlp_alpha;
     PArgs pa;
     pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
     const int nt = tiles_of(c);
     auto residuals = [&](int pass) {
         sq.pass = pass; sq.last = (pass == c->nlp_max_iter) ? 1 : 0;
+        sq.cost = (c->nlp_alpha != 1.0 || (pass == 0 && cold)) ? 1 : 0;
         if (launch_pipeline(c, false, 1)) return 1;
         if (nt == 7) hipLaunchKernelGGL(nlp_residual_kernel<7>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
         else if (nt == 6) hipLaunchKernelGGL(nlp_residual_kernel<6>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
@@ -1214,7 +1248,7 @@ static int launch_sqp(tum_ocp *c)
         HIPCHK(hipGetLastError());
         c->order_valid = true;
     }
-    c->solved = true; c->solved_pipe = true; c->solved_sqp = true;
+    c->solved = true; c->solved_pipe = true; c->solved_sqp = true; c->cold = false;
     c->ipm_timed = c->time_ipm;
     c->ts_slot = -1;
     return 0;
@@ -1362,6 +1396,8 @@ extern "C" int tum_ocp_reset(tum_ocp *c)
     HIPCHK(hipMemsetAsync(c->dqplam, 0, sizeof(double) * (size_t)c->batch * (6 * (size_t)c->N + 2), c->stream));
     HIPCHK(hipMemsetAsync(c->dX, 0, sizeof(double) * (size_t)c->batch * (c->N + 1) * NX, c->stream));
     HIPCHK(hipMemsetAsync(c->dU, 0, sizeof(double) * (size_t)c->batch * c->N * NU, c->stream));
+    HIPCHK(hipMemsetAsync(c->dslack, 0, sizeof(double) * (size_t)c->batch * 6 * (size_t)c->N, c->stream));
+    c->cold = true;
     if (c->sn) HIPCHK(hipMemsetAsync(c->dXS, 0, sizeof(double) * (size_t)c->batch * (c->N + 1) * c->sa.ns * NX, c->stream));
     if (c->sn) { HIPCHK(hipMemsetAsync(c->dxs_dirty, 0, sizeof(int) * (size_t)c->batch, c->stream)); c->xs_lazy = false; }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1372,7 +1408,7 @@ extern "C" int tum_ocp_cold_start(tum_ocp *c)
 {
     if (!c) return fail("null capsule");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false;
+    c->cache_valid = false; c->cold = true;
     if (flush_inputs(c)) return 1;          // (the x0 it copies may still be in the pinned shadow)
     hipLaunchKernelGGL(cold_start_kernel, dim3(c->batch), dim3(64), 0, c->stream, c->dX, c->dU, c->dx0, c->N, c->batch, c->dqplam);
     if (c->sn && c->fanout && sn_fanout(c)) return 1;
@@ -2071,7 +2107,7 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
             done += s->graph_steps; s->step += s->graph_steps;
             // what launch() records on the host for every solve holds for the replayed solves as well
             if (c->sn) c->xs_lazy = true;
-            c->solved = true; c->solved_pipe = c->pipe; if (c->lpt && c->batch > 1024) c->order_valid = true;
+            c->solved = true; c->solved_pipe = c->pipe; c->cold = false; if (c->lpt && c->batch > 1024) c->order_valid = true;
         }
     }
     for (; done < nsteps; done++)

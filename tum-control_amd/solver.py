@@ -268,7 +268,8 @@ class BatchedOcpSolver:
         self._put(self._L.tum_ocp_set, stage, field, value, "set")
 
     def get(self, stage, field):
-        """acados_solver.get(stage, 'x'|'u'|'sl'|'su')"""
+        """acados_solver.get(stage, 'x'|'u'|'sl'|'su'|'lam'); 'lam': the multipliers of the last QP's rows, lower sides in the order of
+        'sl', then upper sides in the order of 'su' (without acados' trailing multipliers of the slack bounds)"""
         N = self.N
         if field == "x":
             ln = 8
@@ -276,6 +277,8 @@ class BatchedOcpSolver:
             ln = 2
         elif field in ("sl", "su"):
             ln = 1 if stage == 0 else (2 if stage == N else 3)
+        elif field == "lam":
+            ln = 2 if stage == 0 else (4 if stage == N else 6)
         else:
             raise Exception(f"BatchedOcpSolver.get: unknown field '{field}'")
         out = np.empty((self.batch, ln))
