@@ -145,7 +145,29 @@ int tum_ocp_solve_async(tum_ocp *c);
  * multipliers), stops an instance whose residuals are all below their tolerances and ends when none is active or after max_iter QPs.
  * Per-instance status: 0 converged, 2 max_iter reached (ACADOS_MAXITER), 4 a QP failed (the iterate stays at the last good one).
  * SQP is refused for a capsule with the R2NMPC tightening attached, for the coupled SNMPC OCP, for the development kernels "fused" /
- * "pipeline4", by tum_ocp_step_async and by the device closed loop (tum_sim_*): those stay SQP-RTI. */
+ * "pipeline4", by tum_ocp_step_async and by the device closed loop (tum_sim_*): those stay SQP-RTI.
+ *
+ * "rti_phase"              acados' split of the real-time iteration: 0 preparation and feedback in one solve (default, as before),
+ *                          1 PREPARATION, 2 FEEDBACK; any other value is an error.
+ * rti_phase 1: tum_ocp_solve / tum_ocp_solve_async upload the pending inputs and run what does not need the measured state -- the
+ *   linearisation and the condensing, the kernels a one-call solve of this capsule would run -- at the x0 the capsule holds, and keep
+ *   a device copy of that x0. Iterate, cost, status, qp_iter, qp_status, res, slacks and multipliers are untouched. Returns 0 (acados
+ *   >= 0.3 returns ACADOS_READY = 5 here; the reference's callers take every non-zero status for a failure). get_stats "time_tot" is
+ *   the preparation's device time.
+ * rti_phase 2: the pending x0 goes up, rti_feedback_kernel applies x0 - x0_prep to the gradient q and the row constants d of the
+ *   prepared QP (both affine in x0; nothing else of the QP depends on it), then the interior point method and the expansion run as in
+ *   a one-call solve (longest-first order, fused expansion, warm start, "time_tot" / "time_ipm", the single device round trip of a
+ *   small capsule's tum_ocp_solve). Returns the maximum status. At an unchanged x0 the result is the one-call solve's, bit for bit.
+ *   A feedback CONSUMES its preparation: without one -- or a second time -- it fails and leaves the iterate alone.
+ * Between the two the caller may change x0 by every route (constraints_set(0, "lbx" | "ubx"), put_device "x0", set_x0_fanout), read
+ *   anything, and change the bounds of the stages >= 1 and the penalties zl / zu / Zl / Zu (the interior point kernel reads them, in
+ *   the feedback). Whatever else the preparation has read makes it STALE and the feedback fail: set "x" | "u" | "yref", cost_set "W",
+ *   put_device "X" | "U" | "yref", bind_device, cold_start, reset, set_kernel. A solve in rti_phase 0 discards a pending preparation.
+ * tum_ocp_step_async: rti_phase 2 with yref = NULL is the one-call feedback step; with a yref (the reference enters in the
+ *   preparation) and in rti_phase 1 (a preparation has no results) it is an error.
+ * Refused, here where the condition is known and again by the solve: the coupled SNMPC OCP, a capsule with the R2NMPC tightening
+ *   attached or with a full W, SQP mode (in either order of setting), the development kernels "fused" / "pipeline4", the debug dump
+ *   and the phase timers, and tum_sim_create / tum_sim_run on a capsule whose rti_phase is not 0. */
 int tum_ocp_options_set(tum_ocp *c, const char *field, double value);
 int tum_ocp_synchronize(tum_ocp *c);
 
@@ -168,7 +190,9 @@ int tum_ocp_get_from_qp_in(tum_ocp *c, int stage, const char *field, double *out
  * stream) and copy results device-to-device into caller-owned HBM (for the RCCL gather). */
 int tum_ocp_set_stream(tum_ocp *c, void *hip_stream);
 /* field: "u0" (nb x 2), "x1" (nb x 8), "cost" (nb), "X" (nb x (N+1)*8), "U" (nb x N*2),
- * "status" / "qp_iter" (nb int32), "summary" (nb x 5 doubles: u0[2], cost, status, qp_iter -- the slab of the rooted gather) */
+ * "status" / "qp_iter" (nb int32), "summary" (nb x 5 doubles: u0[2], cost, status, qp_iter -- the slab of the rooted gather),
+ * "qp_vec" (nb x 2 NVP doubles, NVP = 80 / 96 / 112 for N <= 40 / 48 / 56: gradient q | row constants d of the condensed QP as the
+ * interior point kernel of the last solve -- or the next feedback -- reads them; d[2 (s - 1)], d[2 (s - 1) + 1]: steering angle and gg row of stage s) */
 int tum_ocp_get_device(tum_ocp *c, const char *field, void *dev_dst, int b0, int nb);
 /* Results on the HOST without stalling the stream (no reference counterpart; the caller it serves reads u0 / pred_X / cost /
  * status after every solve, NMPC_class.py:193-206). tum_ocp_results_async enqueues, on the capsule's stream and behind the

@@ -20,6 +20,7 @@
 #include "aux_kernels.hpp"
 #include "loop_kernels.hpp"
 #include "sqp_kernels.hpp"
+#include "rti_kernels.hpp"
 
 using namespace tum;
 
@@ -92,7 +93,16 @@ struct tum_ocp {
     // solve never reads them (the warm-start word is 0); a full SQP solve evaluates pass 0 with them and damps towards them, so it clears
     // them first (acados' reset() zeroes them)
     bool cold;
+    // split real-time iteration (tum_ocp_options_set "rti_phase"): 0 preparation and feedback in one solve, 1 the next solves are
+    // PREPARATIONS (linearisation and condensing), 2 FEEDBACKS (rti_feedback_kernel, interior point method, expansion).
+    // prep: 0 no preparation pending, 1 the workspace holds the condensed QP of a preparation at dx0prep, 2 that preparation is
+    // STALE: something it had read (iterate, reference, W, kernel variant, bound arrays) changed behind it
+    int rti_phase, prep; double *dx0prep; bool prep_timed;
 };
+
+// everything that changes what a preparation has read calls this (x0, the bounds of the stages >= 1 and the slack penalties are read
+// by the feedback: they do not)
+static void prep_stale(tum_ocp *c) { if (c->prep == 1) c->prep = 2; }
 
 static const int DBG_STRIDE = 20480;
 static const int DBG_INST = 4;
@@ -160,6 +170,7 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
     c->nlp_type = 0; c->nlp_max_iter = 100; for (double &t : c->nlp_tol) t = 1e-6; c->nlp_alpha = 1.0;
     c->dnlpres = c->dsnap = nullptr; c->dsqpstate = c->dsqpiter = c->dsnapi = nullptr; c->dactive = c->hactive = nullptr; c->active_cap = 0;
     c->evpoll[0] = c->evpoll[1] = nullptr; c->solved_sqp = false; c->cold = true;
+    c->rti_phase = 0; c->prep = 0; c->dx0prep = nullptr; c->prep_timed = false;
     for (int i = 0; i < 2; i++) { c->hsum[i] = c->hX[i] = c->hU[i] = c->hin[i] = nullptr; c->hts[i] = nullptr; c->evres[i] = nullptr; c->res_iter[i] = false; }
     const int N = c->N; const size_t B = c->batch;
     bool ok = true;
@@ -276,7 +287,7 @@ extern "C" void tum_ocp_free(tum_ocp *c)
     if (c->evi1) (void)hipEventDestroy(c->evi1);
     (void)hipFree(c->dXS); (void)hipFree(c->dxs0); (void)hipFree(c->dApce); (void)hipFree(c->dws2); (void)hipFree(c->dpro); (void)hipFree(c->ddv); (void)hipFree(c->doffs); (void)hipFree(c->dxs_dirty);
     (void)hipFree(c->dr2S); (void)hipFree(c->dr2B); (void)hipFree(c->dpceA); (void)hipFree(c->dbnd_snap);
-    (void)hipFree(c->dsum);
+    (void)hipFree(c->dsum); (void)hipFree(c->dx0prep);
     (void)hipFree(c->dnlpres); (void)hipFree(c->dsnap); (void)hipFree(c->dsqpstate); (void)hipFree(c->dsqpiter); (void)hipFree(c->dsnapi); (void)hipFree(c->dactive);
     if (c->hactive) (void)hipHostFree(c->hactive);
     for (hipEvent_t e : c->evpoll) if (e) (void)hipEventDestroy(e);
@@ -596,6 +607,7 @@ extern "C" int tum_ocp_set(tum_ocp *c, int stage, const char *field, const doubl
     if (!field || !v) return fail("null argument");
     const int N = c->N;
     const std::string f(field);
+    if (f == "x" || f == "u" || f == "yref") prep_stale(c);
     if (f == "x") {
         if (stage == TUM_ALL_STAGES) { if (len != (N + 1) * NX) return fail("set x: len != (N+1)*8"); return put(c, c->dX, (N + 1) * NX, 0, v, len, b0, nb, stride); }
         if (stage < 0 || stage > N) return fail("set x: stage out of range");
@@ -765,6 +777,7 @@ extern "C" int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const 
     const std::string f(field);
     if ((stage < 0 || stage > N) && !(stage == TUM_ALL_STAGES && f == "W")) return fail("cost_set: stage out of range");
     if (f == "W") {
+        prep_stale(c);
         // per stage, like acados (NMPC_class.py:294-296 sets every stage in a loop); stage == TUM_ALL_STAGES: one 6 x 6 W for all
         // the stages 0..N-1 in one call
         const bool all = stage == TUM_ALL_STAGES;
@@ -891,6 +904,7 @@ extern "C" int tum_ocp_set_kernel(tum_ocp *c, const char *name)
 #endif
     else return fail("set_kernel: unknown kernel '" + n + "' (auto | pipeline | lin-lane-per-stage | lin-eight-lanes | cond-one-wavefront | cond-six-wavefronts | loop-fork | loop-serial | prologue-mfma | prologue-passes; development build: fused | pipeline4)");
     c->epoch++;
+    prep_stale(c);
     return 0;
 }
 
@@ -978,7 +992,7 @@ static void launch_lin_ahead(tum_ocp *c, hipStream_t st)
 
 // part: 1 the linearisation and the condensing, 2 the interior point method and the expansion, 3 both (an SQP-RTI solve;
 // a full SQP solve puts its residual pass between the two, launch_sqp)
-static int launch_pipeline(tum_ocp *c, bool events, int part = 3)
+static int launch_pipeline(tum_ocp *c, bool events, int part)
 {
     PArgs pa;
     pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
@@ -1067,9 +1081,64 @@ static int launch_pipeline(tum_ocp *c, bool events, int part = 3)
     return 0;
 }
 
+// ---- split real-time iteration (tum_ocp_options_set "rti_phase")
+// what the split is not built for: the reason, or null
+static const char *rti_unsupported(const tum_ocp *c)
+{
+    if (c->sn) return "the split real-time iteration is not available for the coupled SNMPC OCP (its prologue and epilogue kernels read x0 themselves): rti_phase 0 only";
+    if (c->r2) return "the split real-time iteration is not available for a capsule with the R2NMPC tightening attached (the back-off follows every whole solve): rti_phase 0 only";
+    if (c->dWf) return "the split real-time iteration is not available for a capsule with a full W (cost_set 'W' with off-diagonal entries: x0 then enters the input rows of the gradient as well): rti_phase 0 only";
+    if (c->nlp_type) return "the split real-time iteration is one SQP-RTI step; this capsule is in SQP mode (nlp_solver_type 1)";
+    if (c->kmode == 1 || c->kmode == 3) return "the split real-time iteration runs on the pipeline only, not on the development kernels 'fused' / 'pipeline4'";
+    if (c->ka.flags & 6) return "the split real-time iteration does not run with the debug dump or the phase timers";
+    return nullptr;
+}
+// may a solve in the capsule's phase start: nothing is touched when it may not
+static int rti_gate(tum_ocp *c)
+{
+    if (!c->rti_phase) return 0;
+    if (const char *why = rti_unsupported(c)) return fail(std::string("solve: ") + why);
+    if (c->rti_phase == 2 && c->prep == 0)
+        return fail("solve: rti_phase 2 (feedback) without a preparation: solve with rti_phase 1 first (every feedback consumes its preparation)");
+    if (c->rti_phase == 2 && c->prep == 2)
+        return fail("solve: rti_phase 2 (feedback): the preparation is stale -- the iterate, the reference, W, the kernel choice or a bound array changed "
+                    "behind it (between the phases: x0, the bounds of the stages >= 1 and the slack penalties only); prepare again");
+    return 0;
+}
+static void launch_rti_feedback(tum_ocp *c)
+{
+    PArgs pa;
+    pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
+    const int nt = tiles_of(c);
+    if (nt == 7) hipLaunchKernelGGL(rti_feedback_kernel<7>, dim3(c->batch), dim3(64), 0, c->stream, pa, c->dx0prep);
+    else if (nt == 6) hipLaunchKernelGGL(rti_feedback_kernel<6>, dim3(c->batch), dim3(64), 0, c->stream, pa, c->dx0prep);
+    else hipLaunchKernelGGL(rti_feedback_kernel<5>, dim3(c->batch), dim3(64), 0, c->stream, pa, c->dx0prep);
+}
+// PREPARATION (rti_phase 1): pending inputs up, part 1 of the pipeline as a one-call solve of this capsule would run it, and the x0 it
+// condensed at. Iterate, results, multipliers, slacks and the getters' cache stay as they are.
+static int launch_prepare(tum_ocp *c)
+{
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (rti_gate(c)) return 1;
+    if (resolve_kernel(c)) return 1;
+    if (!c->dx0prep && dalloc(&c->dx0prep, (size_t)c->batch * NX) != hipSuccess) return fail("solve: device allocation failed (rti_phase 1)");
+    c->prep = 0;
+    if (flush_inputs(c)) return 1;
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    if (launch_pipeline(c, false, 1)) return 1;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->dx0prep, c->dx0, sizeof(double) * (size_t)c->batch * NX, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    c->prep = 1; c->prep_timed = true;
+    c->ts_slot = -1;          // (get_stats "time_tot": the events of the preparation)
+    return 0;
+}
+
 static int launch(tum_ocp *c, bool events = true)
 {
     DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (rti_gate(c)) return 1;
+    const bool feedback = c->rti_phase == 2;
     if (resolve_kernel(c)) return 1;
     c->cache_valid = false; c->xs_cached = false;
     if (flush_inputs(c)) return 1;          // setters still in the pinned shadow (small capsules)
@@ -1086,7 +1155,10 @@ static int launch(tum_ocp *c, bool events = true)
         return fail("solve: kernel 'fused' takes at most 16 samples / PCE terms (use 'auto' or 'pipeline')");
     if (c->sn && !c->pipe && c->sa.uph > SN_UPHMAX_FUSED)
         return fail("solve: kernel 'fused' reads the sample columns of one wavefront: uncertainty propagation horizon <= 31 (use 'auto' or 'pipeline')");
-    if (c->pipe) { if (launch_pipeline(c, events)) return 1; }
+    if (c->pipe) {
+        if (feedback) launch_rti_feedback(c);
+        if (launch_pipeline(c, events, feedback ? 2 : 3)) return 1;
+    }
     else if (c->sn) {
         if (c->fanout && sn_fanout(c)) return 1;
         sn_launch_lin(c);
@@ -1097,7 +1169,8 @@ static int launch(tum_ocp *c, bool events = true)
     else { if (prof) fused(nmpc_rti_kernel<true>); else fused(nmpc_rti_kernel<false>); }
     if (!c->pipe) HIPCHK(hipMemsetAsync(c->dqplam, 0, sizeof(double) * (size_t)c->batch * (6 * (size_t)c->N + 2), c->stream));      // (the fused kernel leaves no multipliers behind)
 #else
-    if (launch_pipeline(c, events)) return 1;
+    if (feedback) launch_rti_feedback(c);
+    if (launch_pipeline(c, events, feedback ? 2 : 3)) return 1;
 #endif
     HIPCHK(hipGetLastError());
     if (c->r2) {   // constraint tightening for the NEXT solve from this one's linearisation (skipped per instance on failure)
@@ -1117,6 +1190,7 @@ static int launch(tum_ocp *c, bool events = true)
     c->solved_sqp = false; c->cold = false;
     c->ipm_timed = (events && !c->skip_ipm_events) || c->time_ipm;
     c->ts_slot = -1;          // (tum_ocp_step_async sets it behind this call)
+    c->prep = 0; c->prep_timed = false;          // (a feedback consumes its preparation; a one-call solve discards a pending one)
     return 0;
 }
 
@@ -1131,6 +1205,7 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
     if (f == "nlp_solver_type") {
         if (value != 0.0 && value != 1.0) return fail("options_set nlp_solver_type: 0 (SQP_RTI) or 1 (SQP)");
         if (value == 1.0) {
+            if (c->rti_phase) return fail("options_set nlp_solver_type: SQP is not available while the capsule splits the real-time iteration (rti_phase 1 / 2 is one SQP-RTI step): set rti_phase 0 first");
             if (c->r2) return fail("options_set nlp_solver_type: SQP is not available for a capsule with the R2NMPC tightening attached (SQP_RTI only, as Reduced_Robustified_NMPC_class.py requires)");
             if (c->sn) return fail("options_set nlp_solver_type: SQP is not available for the coupled SNMPC OCP (SQP_RTI only)");
         }
@@ -1154,8 +1229,14 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
         c->nlp_alpha = value;
         return 0;
     }
+    if (f == "rti_phase") {      // acados: 0 PREPARATION_AND_FEEDBACK, 1 PREPARATION, 2 FEEDBACK
+        if (value != 0.0 && value != 1.0 && value != 2.0) return fail("options_set rti_phase: 0 (preparation and feedback), 1 (preparation) or 2 (feedback)");
+        if (value != 0.0) { if (const char *why = rti_unsupported(c)) return fail(std::string("options_set rti_phase: ") + why); }
+        c->rti_phase = (int)value;
+        return 0;
+    }
     return fail("options_set: unknown field '" + f + "' (nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
-                "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length)");
+                "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length | rti_phase)");
 }
 
 // One full SQP solve: [lin, cond, residuals] then, while an instance is active and the cap is not reached, [snapshot, ipm, expand,
@@ -1249,6 +1330,7 @@ static int launch_sqp(tum_ocp *c)
         c->order_valid = true;
     }
     c->solved = true; c->solved_pipe = true; c->solved_sqp = true; c->cold = false;
+    c->prep = 0; c->prep_timed = false;
     c->ipm_timed = c->time_ipm;
     c->ts_slot = -1;
     return 0;
@@ -1267,6 +1349,7 @@ extern "C" int tum_ocp_solve_async(tum_ocp *c)
 {
     if (!c) return fail("null capsule");
     if (c->nlp_type) return launch_sqp(c);          // (the host reads the active count between iterations: returns behind the last QP)
+    if (c->rti_phase == 1) return launch_prepare(c);
     return launch(c);
 }
 extern "C" int tum_ocp_synchronize(tum_ocp *c)
@@ -1289,6 +1372,15 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
         int mx = 0;
         for (int s : st) if (s > mx) mx = s;
         return mx;
+    }
+    if (c->rti_phase) {
+        if (rti_gate(c)) return -1;          // (before anything is uploaded or invalidated)
+        if (c->rti_phase == 1) {
+            // a preparation has no results: 0 (acados >= 0.3 returns ACADOS_READY here; the reference's callers take any non-zero status for a failure)
+            if (launch_prepare(c)) return -1;
+            if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
+            return 0;
+        }
     }
     if (small_inputs(c) && results_pack_all(c, 1)) {
         // small capsule: [pending setters up + device clock] -> solve -> [summary, X, U into pinned slabs + device clock], ONE wait. No
@@ -1324,7 +1416,7 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
 
 extern "C" double tum_ocp_last_kernel_ms(tum_ocp *c)
 {
-    if (!c || !c->solved) return 0.0;
+    if (!c || !(c->solved || c->prep_timed)) return 0.0;
     DevGuard guard(c->d.device); if (!guard.ok) return 0.0;
     if (c->ts_slot == 2) {      // the synchronous solve of a small capsule: clocked by its first and last kernel, already waited for
         c->last_ms = (float)((double)(c->hts_s[1] - c->hts_s[0]) / c->ts_khz);
@@ -1392,7 +1484,7 @@ extern "C" int tum_ocp_reset(tum_ocp *c)
 {
     if (!c) return fail("null capsule");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false;
+    c->cache_valid = false; prep_stale(c);
     HIPCHK(hipMemsetAsync(c->dqplam, 0, sizeof(double) * (size_t)c->batch * (6 * (size_t)c->N + 2), c->stream));
     HIPCHK(hipMemsetAsync(c->dX, 0, sizeof(double) * (size_t)c->batch * (c->N + 1) * NX, c->stream));
     HIPCHK(hipMemsetAsync(c->dU, 0, sizeof(double) * (size_t)c->batch * c->N * NU, c->stream));
@@ -1408,7 +1500,7 @@ extern "C" int tum_ocp_cold_start(tum_ocp *c)
 {
     if (!c) return fail("null capsule");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false; c->cold = true;
+    c->cache_valid = false; c->cold = true; prep_stale(c);
     if (flush_inputs(c)) return 1;          // (the x0 it copies may still be in the pinned shadow)
     hipLaunchKernelGGL(cold_start_kernel, dim3(c->batch), dim3(64), 0, c->stream, c->dX, c->dU, c->dx0, c->N, c->batch, c->dqplam);
     if (c->sn && c->fanout && sn_fanout(c)) return 1;
@@ -1490,6 +1582,13 @@ extern "C" int tum_ocp_get_device(tum_ocp *c, const char *field, void *dst, int 
     if (f == "U") { HIPCHK(hipMemcpyAsync(dst, c->dU + (size_t)b0 * N * NU, 8 * (size_t)nb * N * NU, hipMemcpyDeviceToDevice, s)); return 0; }
     if (f == "status") { HIPCHK(hipMemcpyAsync(dst, c->dstatus + b0, 4 * (size_t)nb, hipMemcpyDeviceToDevice, s)); return 0; }
     if (f == "qp_iter") { HIPCHK(hipMemcpyAsync(dst, c->dqpiter + b0, 4 * (size_t)nb, hipMemcpyDeviceToDevice, s)); return 0; }
+    if (f == "qp_vec") {      // gradient q and row constants d of the condensed QP in the pipeline's workspace, read-only
+        if (!c->dvec) return fail("get_device qp_vec: no pipeline solve or preparation yet");
+        const int nt = tiles_of(c);
+        const size_t nvp = nt == 7 ? PD<7>::NVP : nt == 6 ? PD<6>::NVP : PD<5>::NVP, pvec = nt == 7 ? PD<7>::PVEC : nt == 6 ? PD<6>::PVEC : PD<5>::PVEC;
+        HIPCHK(hipMemcpy2DAsync(dst, 2 * nvp * 8, c->dvec + (size_t)b0 * pvec, pvec * 8, 2 * nvp * 8, nb, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
     return fail("get_device: unknown field '" + f + "'");
 }
 
@@ -1570,6 +1669,9 @@ extern "C" int tum_ocp_step_async(tum_ocp *c, const double *x0, const double *yr
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if (c->nlp_type) return fail("step_async: one SQP-RTI iteration per step; a capsule in SQP mode (nlp_solver_type 1) takes tum_ocp_solve");
     if (c->res_count == 2) return fail("step_async: two requests outstanding on this capsule (call tum_ocp_results_wait first)");
+    if (c->rti_phase == 1) return fail("step_async: a preparation (rti_phase 1) has no results: prepare with tum_ocp_solve / tum_ocp_solve_async");
+    if (c->rti_phase == 2 && yref) return fail("step_async: the reference enters in the preparation; a feedback step (rti_phase 2) takes x0 only (yref = NULL)");
+    if (rti_gate(c)) return 1;
     if (flush_inputs(c)) return 1;          // (setters older than this step's inputs)
     const size_t B = c->batch, nx0 = B * NX, nyr = B * (size_t)(c->N + 1) * 6;
     // the staging area of the result slot this step will use: its previous step has been waited for, so its uploads are done
@@ -1620,6 +1722,7 @@ extern "C" int tum_ocp_put_device(tum_ocp *c, const char *field, const void *src
     DevGuard guard(c->d.device); GUARD_OK(guard);
     hipStream_t s = c->stream;
     c->cache_valid = false;
+    if (f != "x0") prep_stale(c);
     if (flush_inputs(c)) return 1;          // (setters older than this upload)
     if (f == "x0") {
         if (c->sn) { if (!c->have_offs) return fail("put_device x0: an SNMPC capsule needs its sample offsets (tum_ocp_snmpc_set_offsets)"); c->fanout = true; }
@@ -1641,6 +1744,7 @@ extern "C" int tum_ocp_bind_device(tum_ocp *c, const char *field, void *dev_ptr)
     if (!c || !field) return fail("null argument");
     const std::string f(field);
     if (f != "x0" && f != "yref") return fail("bind_device: field must be 'x0' or 'yref'");
+    prep_stale(c);
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if (flush_inputs(c)) return 1;          // (setters parked in the pinned shadow belong to the array in use until now)
     if (f == "x0") {
@@ -1661,6 +1765,7 @@ extern "C" int tum_ocp_debug_dump(tum_ocp *c, int b, double *out, int len)
 {
     if (!c) return fail("null capsule");
     if (b < 0 || b >= DBG_INST || b >= c->batch) return fail("debug_dump: instance out of range");
+    if (c->rti_phase) return fail("debug_dump: the split real-time iteration does not run with the debug dump or the phase timers (set rti_phase 0)");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if (len > DBG_STRIDE) len = DBG_STRIDE;
 #ifdef TUM_DEV_KERNELS
@@ -1710,6 +1815,7 @@ extern "C" int tum_ocp_profile_phases(tum_ocp *c, long long *out)
 {
     if (!c || !out) return fail("null argument");
     if (c->N > NMAX) return fail("profile_phases: the instrumented kernels are built for N <= 40");
+    if (c->rti_phase) return fail("profile_phases: the split real-time iteration does not run with the debug dump or the phase timers (set rti_phase 0)");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     c->ka.flags |= 4;
     int rc = launch(c);
@@ -1943,6 +2049,7 @@ extern "C" tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track,
     if (n_track < 2 || !(Tp > 0) || !(Ts > 0) || n_elem < 1 || log_capacity < 0) { fail("sim_create: bad arguments"); return nullptr; }
     for (int i = 0; i < 8; i++) if (windows[i] < 1 || windows[i] > 4) { fail("sim_create: estimator windows must be 1..4"); return nullptr; }
     if (c->nlp_type) { fail("sim_create: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)"); return nullptr; }
+    if (c->rti_phase) { fail("sim_create: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0"); return nullptr; }
     DevGuard guard(c->d.device); if (!guard.ok) { fail("hipSetDevice failed"); return nullptr; }
     if (c->sn) {   // the state estimator writes the nominal x0 only: the samples follow by fan-out
         if (!c->have_offs) { fail("sim_create: an SNMPC capsule needs its sample offsets (tum_ocp_snmpc_set_offsets)"); return nullptr; }
@@ -1972,7 +2079,7 @@ extern "C" int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *
     if (!s || !x_sim || !x_mpc) return fail("null argument");
     tum_ocp *c = s->c; const size_t B = c->batch;
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false;
+    c->cache_valid = false; prep_stale(c);
     if (flush_inputs(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(s->dxsim, x_sim, sizeof(double) * B * 7, hipMemcpyHostToDevice));
@@ -2071,6 +2178,7 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
     if (!s || nsteps < 0) return fail("bad argument");
     tum_ocp *c = s->c;
     if (c->nlp_type) return fail("sim_run: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
+    if (c->rti_phase) return fail("sim_run: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     c->cache_valid = false;
     if (flush_inputs(c)) return 1;            // (pending host setters go up before anything is captured)

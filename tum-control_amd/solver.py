@@ -194,6 +194,15 @@ _FIELD_BYTES = {}          # field name -> bytes, encoded once
 _NLP_DEFAULTS = dict(nlp_solver_max_iter=100, nlp_solver_tol_stat=1e-6, nlp_solver_tol_eq=1e-6, nlp_solver_tol_ineq=1e-6,
                      nlp_solver_tol_comp=1e-6, nlp_solver_step_length=1.0)
 _NLP_TYPES = {"SQP_RTI": 0, "SQP": 1}
+# acados' rti_phase values: 0 preparation and feedback in one solve(), 1 preparation, 2 feedback
+_RTI_PHASES = {0: "PREPARATION_AND_FEEDBACK", 1: "PREPARATION", 2: "FEEDBACK"}
+
+
+def _rti_phase_value(value):
+    """rti_phase as acados takes it: the integer 0, 1 or 2 (anything else is refused before the library sees it)"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer, float, np.floating)) or value not in _RTI_PHASES:
+        raise Exception(f"BatchedOcpSolver.options_set: rti_phase must be 0 (preparation and feedback), 1 (preparation) or 2 (feedback), got {value!r}")
+    return int(value)
 
 
 class BatchedOcpSolver:
@@ -312,12 +321,30 @@ class BatchedOcpSolver:
 
     def options_set(self, field, value):
         """acados_solver.options_set(field, value) for the NLP solver: 'nlp_solver_type' ('SQP_RTI' | 'SQP'), 'nlp_solver_max_iter',
-        'nlp_solver_tol_stat' | '_eq' | '_ineq' | '_comp', 'nlp_solver_step_length' (include/tum_nmpc.h, tum_ocp_options_set)"""
+        'nlp_solver_tol_stat' | '_eq' | '_ineq' | '_comp', 'nlp_solver_step_length' (include/tum_nmpc.h, tum_ocp_options_set);
+        'rti_phase' 0 | 1 | 2: the following solve() calls are whole SQP-RTI steps (default), preparations or feedbacks"""
+        if field == "rti_phase":
+            value = _rti_phase_value(value)
         if field == "nlp_solver_type" and isinstance(value, str):
             if value not in _NLP_TYPES:
                 raise Exception(f"BatchedOcpSolver.options_set: nlp_solver_type must be one of {sorted(_NLP_TYPES)}, got '{value}'")
             value = _NLP_TYPES[value]
         self._chk(self._L.tum_ocp_options_set(self._h, field.encode(), float(value)), "options_set")
+
+    def prepare(self):
+        """PREPARATION of a split real-time iteration (options_set('rti_phase', 1) + solve()): linearisation and condensing at the
+        current iterate, reference and x0 -- everything that can run before the measured state is known. Leaves iterate and results
+        untouched, returns 0; get_stats('time_tot') is its device time. The capsule stays in rti_phase 1."""
+        self.options_set("rti_phase", 1)
+        return self.solve()
+
+    def feedback(self, x0=None):
+        """FEEDBACK of a split real-time iteration (options_set('rti_phase', 2) + solve()): x0 (None: keep) enters the prepared QP, then
+        the interior point method and the expansion. Raises without a (fresh) preparation. The capsule stays in rti_phase 2."""
+        self.options_set("rti_phase", 2)
+        if x0 is not None:
+            self.set_x0(x0)
+        return self.solve()
 
     def get_residuals(self):
         """acados_solver.get_residuals(): [stat, eq, ineq, comp] of the NLP at the iterate of the last SQP solve; (batch, 4) for a batch"""
@@ -439,7 +466,8 @@ class BatchedOcpSolver:
     def step_async(self, x0=None, yref=None, with_iterate=True):
         """One control step of a host-driven loop in one call (tum_ocp_step_async): x0 (batch, 8) and yref (batch, N+1, 6) -- None:
         keep -- uploaded through pinned staging on the capsule's stream, one SQP-RTI behind them, the results request behind the
-        solve. Returns at once; results_wait() delivers."""
+        solve. Returns at once; results_wait() delivers. In rti_phase 2 it is the one-call FEEDBACK step (x0 in, feedback, results;
+        yref must be None: the reference enters in the preparation); in rti_phase 1 it is an error."""
         def arr(a, n):
             if a is None:
                 return None, None
@@ -619,6 +647,12 @@ class CoupledSnmpcSolver(BatchedOcpSolver):
             self._chk(self._L.tum_ocp_set(self._h, int(stage), b"p", v.ctypes.data, v.size, 0, self.batch, 0), "set")
             return
         super().set(stage, field, value)
+
+    def options_set(self, field, value):
+        if field == "rti_phase" and _rti_phase_value(value) != 0:
+            raise Exception("CoupledSnmpcSolver.options_set: the split real-time iteration (rti_phase 1 / 2) is not available for the coupled "
+                            "SNMPC OCP: its prologue and epilogue kernels read x0 themselves")
+        super().options_set(field, value)
 
     def get(self, stage, field):
         if field == "x":
