@@ -167,7 +167,18 @@ int tum_ocp_solve_async(tum_ocp *c);
  *   preparation) and in rti_phase 1 (a preparation has no results) it is an error.
  * Refused, here where the condition is known and again by the solve: the coupled SNMPC OCP, a capsule with the R2NMPC tightening
  *   attached or with a full W, SQP mode (in either order of setting), the development kernels "fused" / "pipeline4", the debug dump
- *   and the phase timers, and tum_sim_create / tum_sim_run on a capsule whose rti_phase is not 0. */
+ *   and the phase timers, and tum_sim_create / tum_sim_run on a capsule whose rti_phase is not 0.
+ *
+ * "lin_dedup"              1 (default): while the iterate is the same at every stage -- after cold_start() or reset(), until anything
+ *                          writes it: set "x" | "u", put_device "X" | "U", a solve that expands, the device closed loop -- the
+ *                          linearisation runs the Runge-Kutta pass once per instance instead of once per stage and fills the stage
+ *                          records from it (lin_uniform_kernel + lin_fill_kernel). The records, and every result, are bit-identical to
+ *                          the general linearisation's. 0: always the general linearisation (A/B runs, tests). Applies where the
+ *                          lane-per-stage kernel of the nominal OCP would run: not on the eight-lane latency path, not to the
+ *                          coupled SNMPC OCP, not in the device closed loop (tum_sim_run captures and replays its steps). A caller who
+ *                          captures solves into a graph of their own captures the cold_start() with them, or sets 0. The fill kernel compares every stage with stage 0: should the
+ *                          library ever take the path on a non-uniform iterate, every synchronous call fails and says so until the next
+ *                          cold_start() / reset(), which re-initialise the iterate and re-arm the check. */
 int tum_ocp_options_set(tum_ocp *c, const char *field, double value);
 int tum_ocp_synchronize(tum_ocp *c);
 
@@ -178,7 +189,8 @@ int tum_ocp_get_cost(tum_ocp *c, double *out, int b0, int nb);
  * "sqp_iter" -> nb ints (1 after an SQP-RTI solve; the QPs each instance solved after an SQP solve), "qp_iter" -> nb ints,
  * "status" -> nb ints, "qp_status" -> nb ints
  * "res" -> nb x 3 doubles (stat, ineq, comp residuals of the last QP)
- * "residuals" -> nb x 4 doubles (stat, eq, ineq, comp residuals of the NLP at the returned iterate; after an SQP solve only). */
+ * "residuals" -> nb x 4 doubles (stat, eq, ineq, comp residuals of the NLP at the returned iterate; after an SQP solve only).
+ * "lin_uniform" -> 1 int: linearisations of this capsule that took the uniform path (options_set "lin_dedup") since it was created. */
 int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b0, int nb);
 /* acados_solver.reset()   NMPC_class.py:251 -- zero the iterate of every instance */
 int tum_ocp_reset(tum_ocp *c);

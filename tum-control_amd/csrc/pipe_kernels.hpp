@@ -259,6 +259,97 @@ __global__ void __launch_bounds__(64, 1) lin_cols_kernel(const PArgs pa)
         if ((int)threadIdx.x < NF) dst[(size_t)it * PREC + threadIdx.x] = sT[it * L_PITCH + threadIdx.x];
 }
 
+// ---- K1 for a STAGE-UNIFORM iterate: X_k = X_0 and U_k = U_0 for every k (what cold_start() and reset() leave behind).
+// rk4_sens and h_con depend on (X_k, U_k) only, so lin_kernel evaluates them N times per instance on the same operands and gets
+// the same Sp, S, xn and gg row N times; only the four cost residuals (yref_k) differ from stage to stage. Two kernels then:
+//   lin_uniform_kernel   lane = instance (batch / 64 wavefronts instead of batch x (N + 1) / 64): the same rk4_sens and h_con on
+//                        X_0, U_0 LOADED from the iterate (a literal zero for U would fold and change the FMA contraction), results
+//                        to lin1[b][LIN1];
+//   lin_fill_kernel      a wavefront per instance, lane = field of a record: composes the N + 1 records exactly as lin_kernel lays
+//                        them out -- Sp, S and the defect xn - X_{k+1} for k < N, the residuals from X_k and yref_k, the gg row for
+//                        k >= 1, delta_f -- one coalesced store per record, no LDS, no branch in the stage loop.
+// Every field is produced by the operations lin_kernel applies to the same operands: the records, and with them everything
+// downstream, are bit-identical (tests/test_gpu_lin_uniform.py). The host decides (tum_nmpc.hip: iter_uniform); lin_fill_kernel
+// reads X_k and U_k anyway and compares them bitwise with stage 0: a mismatch -- an invalidation the host missed -- sets *bad,
+// which the host reads at its next synchronous point.
+// lin1 fields: [0,1] Sp | [2..43] S[6][7] (as in a record) | [44..51] xn | [52..55] g3 g5 g7 h
+constexpr int L1_XN = 44, L1_GH = 52, L1_NF = 56, LIN1 = 64;
+__global__ void __launch_bounds__(64, 1) lin_uniform_kernel(const PArgs pa, double *lin1)
+{
+    __shared__ double sT[64 * L_PITCH];          // transposed store, as in lin_kernel
+    const KArgs &ka = pa.ka;
+    const int N = ka.N, NB = N + 1;
+    const int b0 = blockIdx.x * 64, bl = b0 + (int)threadIdx.x;
+    const int b = (bl < ka.batch) ? bl : ka.batch - 1;       // (lanes beyond the last instance shadow it and store nothing)
+    const double *gX = ka.X + (size_t)b * NB * NX;
+    double xk[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) xk[i] = gX[i];
+    const double *gU = ka.U + (size_t)b * N * NU;
+    double uk[2] = {gU[0], gU[1]};
+    double h, g3, g5, g7;
+    h_con(ka.mp, xk[3], xk[5], xk[7], h, g3, g5, g7);
+    double xn[8], Sp[2], S[6][7];
+    rk4_sens(ka.mp, xk, uk, ka.dt, ka.nsub, xn, Sp, S);
+    double *rw = sT + threadIdx.x * L_PITCH;
+    rw[0] = Sp[0]; rw[1] = Sp[1];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int c = 0; c < 7; c++) rw[2 + i * 7 + c] = S[i][c];
+#pragma unroll
+    for (int i = 0; i < 8; i++) rw[L1_XN + i] = xn[i];
+    rw[L1_GH + 0] = g3; rw[L1_GH + 1] = g5; rw[L1_GH + 2] = g7; rw[L1_GH + 3] = h;
+    wsync();
+    double *dst = lin1 + (size_t)b0 * LIN1;
+    const int nitem = (ka.batch - b0 < 64) ? (ka.batch - b0) : 64;
+    for (int it = 0; it < nitem; it++)
+        if ((int)threadIdx.x < L1_NF) dst[(size_t)it * LIN1 + threadIdx.x] = sT[it * L_PITCH + threadIdx.x];
+}
+
+constexpr int LF_WAVES = 4;          // instances (wavefronts) per workgroup
+__global__ void __launch_bounds__(64 * LF_WAVES) lin_fill_kernel(const PArgs pa, const double *lin1, int *bad)
+{
+    const KArgs &ka = pa.ka;
+    const int N = ka.N, NB = N + 1;
+    const int f = threadIdx.x & 63;
+    const int b = blockIdx.x * LF_WAVES + (int)(threadIdx.x >> 6);
+    if (b >= ka.batch) return;
+    // One wavefront walks the N + 1 records of ONE instance, lane = field. What a lane needs of lin1 it loads once; of every stage it
+    // reads one number of the iterate (through a per-lane pointer and stride: no branches in the loop) and one of the reference.
+    const double *Xb = ka.X + (size_t)b * NB * NX, *Ub = ka.U + (size_t)b * N * NU;
+    const bool is_def = f >= L1_XN && f < PR_RES, is_res = f >= PR_RES && f < PR_GH, is_gh = f >= PR_GH && f < PR_XD, is_xd = f == PR_XD;
+    const bool is_u = f >= NX && f < NX + NU;
+    //   lanes 0..7: X_k[f] (safety net) | 8, 9: U_k (safety net) | 44..51: X_{k+1}[f - 44] (defect) | 52..55: X_k[f - 52] (residuals) | 60: X_k[6]
+    const int comp = (f < NX) ? f : is_u ? f - NX : is_def ? f - L1_XN : is_res ? f - PR_RES : is_xd ? 6 : 0;
+    const int koff = is_def ? 1 : 0, kmax = is_u ? N - 1 : N, stride = is_u ? NU : NX;       // (stage index clamped: the number read at the clamp is not used)
+    const double *px = (is_u ? Ub : Xb) + comp;
+    const double *py = ka.yref + (size_t)b * NB * 6 + (is_res ? f - PR_RES : 0);
+    const double base = lin1[(size_t)b * LIN1 + (is_gh ? L1_GH + f - PR_GH : (f < PR_RES ? f : 0))];
+    // the wrapped yaw of stage j on lane j (N + 1 <= 57 lanes): fmod once per record, as in lin_kernel, handed to lane 54 by a shuffle
+    const double wy = wrap_yaw(Xb[(size_t)((f < NB) ? f : 0) * NX + 2]);
+    const long long bits0 = __double_as_longlong(px[0]);          // (lanes 0..9: stage 0)
+    bool differs = false;
+    double *dst = pa.rec + (size_t)b * NB * PREC + f;
+#pragma unroll 4
+    for (int k = 0; k < NB; k++) {
+        int ks = k + koff; ks = (ks < kmax) ? ks : kmax;
+        const double x = px[(size_t)ks * stride];
+        const double y = py[(size_t)k * 6];
+        const double wyk = __shfl(wy, k);
+        const double xr = (f == PR_RES + 2) ? wyk : x;
+        double v = base;                                          // Sp, S (k < N), gg row (k >= 1)
+        v = is_def ? base - x : v;                                // xn - X_{k+1}
+        v = is_res ? xr - y : v;                                  // X_k - yref_k, the yaw wrapped
+        v = is_xd ? x : v;
+        if ((f < PR_RES && k == N) || (is_gh && k == 0)) v = 0.0;
+        // the safety net: the state (lanes 0..7) and the input (lanes 8, 9) of this stage against stage 0, bit for bit
+        if (f < NX + NU) differs |= __double_as_longlong(x) != bits0;
+        if (f <= PR_XD) dst[(size_t)k * PREC] = v;
+    }
+    if (differs) *bad = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- K2
 // (Round 5 also built the stage record through the SCALAR data path -- address space 4, s_load, the fields as scalar operands of the FMAs:
 //  +38 us, every stage waits for its loads -- and three wavefronts per SIMD: slower in every form; profiles/r05_ab_cond_variants.txt,

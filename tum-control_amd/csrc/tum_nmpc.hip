@@ -98,11 +98,37 @@ struct tum_ocp {
     // prep: 0 no preparation pending, 1 the workspace holds the condensed QP of a preparation at dx0prep, 2 that preparation is
     // STALE: something it had read (iterate, reference, W, kernel variant, bound arrays) changed behind it
     int rti_phase, prep; double *dx0prep; bool prep_timed;
+    // linearisation of a STAGE-UNIFORM iterate once per instance (lin_uniform_kernel + lin_fill_kernel, pipe_kernels.hpp).
+    // iter_uniform: X_k = X_0 and U_k = U_0 for every k -- set by cold_start() and reset(), cleared by everything that writes dX / dU
+    // (iterate_changed below). lin_dedup: options_set "lin_dedup", 1 by default. n_lin_uniform: linearisations that took the
+    // uniform path (get_stats "lin_uniform"). hlin_bad: pinned word lin_fill_kernel sets when it finds a stage that differs from
+    // stage 0 -- an invalidation missed here; checked at the synchronous entry points (lin_uniform_check).
+    // capturing: tum_sim_run is recording a chunk of the closed loop into a graph (a captured launch is replayed on other iterates)
+    bool iter_uniform, capturing; int lin_dedup; int n_lin_uniform; double *dlin1; int *hlin_bad;
 };
 
 // everything that changes what a preparation has read calls this (x0, the bounds of the stages >= 1 and the slack penalties are read
 // by the feedback: they do not)
 static void prep_stale(tum_ocp *c) { if (c->prep == 1) c->prep = 2; }
+// cold_start() / reset() re-initialise the iterate: a capsule the safety net has failed works again from there. The word may only be
+// written once the kernels that could still set it have finished (they never do in a correct library: the wait is paid after an error only)
+static void lin_uniform_rearm(tum_ocp *c)
+{
+    if (!c->hlin_bad || !*(volatile int *)c->hlin_bad) return;
+    (void)hipStreamSynchronize(c->stream);
+    *(volatile int *)c->hlin_bad = 0;
+}
+// every entry point that writes the iterate (dX, dU) calls this: the next linearisation is the general one
+static void iterate_changed(tum_ocp *c) { c->iter_uniform = false; }
+// the safety net of the uniform linearisation, at the points where the host has waited for the stream anyway
+static int lin_uniform_check(const tum_ocp *c)
+{
+    if (c->hlin_bad && *(volatile int *)c->hlin_bad)
+        return fail("the uniform linearisation (lin_dedup) ran on an iterate that was NOT the same at every stage: the results since the last "
+                    "cold_start() / reset() are wrong. This is a bug of the library (a writer of the iterate that does not call iterate_changed). "
+                    "Every synchronous call fails until the next cold_start() / reset(); options_set('lin_dedup', 0) before it avoids the path");
+    return 0;
+}
 
 static const int DBG_STRIDE = 20480;
 static const int DBG_INST = 4;
@@ -171,6 +197,7 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
     c->dnlpres = c->dsnap = nullptr; c->dsqpstate = c->dsqpiter = c->dsnapi = nullptr; c->dactive = c->hactive = nullptr; c->active_cap = 0;
     c->evpoll[0] = c->evpoll[1] = nullptr; c->solved_sqp = false; c->cold = true;
     c->rti_phase = 0; c->prep = 0; c->dx0prep = nullptr; c->prep_timed = false;
+    c->iter_uniform = false; c->capturing = false; c->lin_dedup = 1; c->n_lin_uniform = 0; c->dlin1 = nullptr; c->hlin_bad = nullptr;
     for (int i = 0; i < 2; i++) { c->hsum[i] = c->hX[i] = c->hU[i] = c->hin[i] = nullptr; c->hts[i] = nullptr; c->evres[i] = nullptr; c->res_iter[i] = false; }
     const int N = c->N; const size_t B = c->batch;
     bool ok = true;
@@ -178,6 +205,9 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
     ok &= hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess;
     ok &= dalloc(&c->dX, B * (N + 1) * NX) == hipSuccess;
     ok &= dalloc(&c->dU, B * N * NU) == hipSuccess;
+    ok &= dalloc(&c->dlin1, B * LIN1) == hipSuccess;
+    ok &= hipHostMalloc((void **)&c->hlin_bad, sizeof(int), hipHostMallocDefault) == hipSuccess;
+    if (c->hlin_bad) *c->hlin_bad = 0;
     ok &= dalloc(&c->dx0, B * NX) == hipSuccess;
     ok &= dalloc(&c->dyref, B * (N + 1) * 6) == hipSuccess;
     c->dx0_own = c->dx0; c->dyref_own = c->dyref;
@@ -287,7 +317,8 @@ extern "C" void tum_ocp_free(tum_ocp *c)
     if (c->evi1) (void)hipEventDestroy(c->evi1);
     (void)hipFree(c->dXS); (void)hipFree(c->dxs0); (void)hipFree(c->dApce); (void)hipFree(c->dws2); (void)hipFree(c->dpro); (void)hipFree(c->ddv); (void)hipFree(c->doffs); (void)hipFree(c->dxs_dirty);
     (void)hipFree(c->dr2S); (void)hipFree(c->dr2B); (void)hipFree(c->dpceA); (void)hipFree(c->dbnd_snap);
-    (void)hipFree(c->dsum); (void)hipFree(c->dx0prep);
+    (void)hipFree(c->dsum); (void)hipFree(c->dx0prep); (void)hipFree(c->dlin1);
+    if (c->hlin_bad) (void)hipHostFree(c->hlin_bad);
     (void)hipFree(c->dnlpres); (void)hipFree(c->dsnap); (void)hipFree(c->dsqpstate); (void)hipFree(c->dsqpiter); (void)hipFree(c->dsnapi); (void)hipFree(c->dactive);
     if (c->hactive) (void)hipHostFree(c->hactive);
     for (hipEvent_t e : c->evpoll) if (e) (void)hipEventDestroy(e);
@@ -578,7 +609,7 @@ static int put(tum_ocp *c, double *dbase, size_t rec, size_t off, const double *
     if (stride != 0 && stride < len) return fail("stride < len");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if ((dbase == c->dx0 || dbase == c->dyref) && flush_inputs(c)) return 1;          // (older setters still in the shadow go first)
-    if (dbase == c->dX || dbase == c->dU) c->cache_valid = false;
+    if (dbase == c->dX || dbase == c->dU) { c->cache_valid = false; iterate_changed(c); }
     const double *src = v;
     size_t spitch = (size_t)stride * sizeof(double);
     if (stride == 0) {
@@ -598,7 +629,7 @@ static int fetch(tum_ocp *c, const double *dbase, size_t rec, size_t off, double
     HIPCHK(hipMemcpy2DAsync(v, (size_t)stride * sizeof(double), dbase + (size_t)b0 * rec + off, rec * sizeof(double),
                             (size_t)len * sizeof(double), nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return lin_uniform_check(c);
 }
 
 extern "C" int tum_ocp_set(tum_ocp *c, int stage, const char *field, const double *v, int len, int b0, int nb, int stride)
@@ -990,6 +1021,10 @@ static void launch_lin_ahead(tum_ocp *c, hipStream_t st)
     c->lin_ahead = true;          // the next launch_pipeline skips its linearisation and tells the condensing kernel (consumed there)
 }
 
+// The uniform linearisation replaces lin_kernel<false> only: the nominal OCP beyond the latency path, and never inside the capture of
+// a closed-loop chunk (a captured launch is replayed on iterates that are uniform no more; tum_sim_run clears the mark as well).
+static bool use_lin_uniform(const tum_ocp *c) { return c->iter_uniform && c->lin_dedup && !c->capturing; }
+
 // part: 1 the linearisation and the condensing, 2 the interior point method and the expansion, 3 both (an SQP-RTI solve;
 // a full SQP solve puts its residual pass between the two, launch_sqp)
 static int launch_pipeline(tum_ocp *c, bool events, int part)
@@ -1013,9 +1048,16 @@ static int launch_pipeline(tum_ocp *c, bool events, int part)
         else hipLaunchKernelGGL(lin_kernel<true>, g_lane, dim3(64), 0, c->stream, pa);
     } else {
         if (cols) hipLaunchKernelGGL(lin_cols_kernel<false>, g_cols, dim3(64), 0, c->stream, pa);
+        else if (use_lin_uniform(c)) {
+            // a stage-uniform iterate (cold_start(), reset()): the Runge-Kutta pass once per instance, then the records of every stage
+            hipLaunchKernelGGL(lin_uniform_kernel, dim3((unsigned)((c->batch + 63) / 64)), dim3(64), 0, c->stream, pa, c->dlin1);
+            hipLaunchKernelGGL(lin_fill_kernel, dim3((unsigned)((c->batch + LF_WAVES - 1) / LF_WAVES)), dim3(64 * LF_WAVES), 0, c->stream, pa, c->dlin1, c->hlin_bad);
+            c->n_lin_uniform++;
+        }
         else hipLaunchKernelGGL(lin_kernel<false>, g_lane, dim3(64), 0, c->stream, pa);
     }
     }
+    if (part & 2) iterate_changed(c);          // (the expansion writes the new iterate)
     // (development aid: a larger LDS request lowers the number of OCPs that share a CU)
     // The expansion as the tail of the interior point kernel pays where a batch is at most one round of resident wavefronts (one
     // launch less: 0.424 against 0.432 ms per solve() call at 26 instances, 0.457 against 0.469 at 1024); beyond that its
@@ -1188,6 +1230,7 @@ static int launch(tum_ocp *c, bool events = true)
     c->solved = true;
     c->solved_pipe = c->pipe;
     c->solved_sqp = false; c->cold = false;
+    iterate_changed(c);          // (whichever kernel variant ran: the solve wrote the new iterate)
     c->ipm_timed = (events && !c->skip_ipm_events) || c->time_ipm;
     c->ts_slot = -1;          // (tum_ocp_step_async sets it behind this call)
     c->prep = 0; c->prep_timed = false;          // (a feedback consumes its preparation; a one-call solve discards a pending one)
@@ -1235,7 +1278,12 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
         c->rti_phase = (int)value;
         return 0;
     }
-    return fail("options_set: unknown field '" + f + "' (nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
+    if (f == "lin_dedup") {      // 1: a stage-uniform iterate is linearised once per instance (default); 0: lin_kernel always (A/B runs, tests)
+        if (value != 0.0 && value != 1.0) return fail("options_set lin_dedup: 0 or 1");
+        c->lin_dedup = (int)value;
+        return 0;
+    }
+    return fail("options_set: unknown field '" + f + "' (lin_dedup | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
                 "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length | rti_phase)");
 }
 
@@ -1330,6 +1378,7 @@ static int launch_sqp(tum_ocp *c)
         c->order_valid = true;
     }
     c->solved = true; c->solved_pipe = true; c->solved_sqp = true; c->cold = false;
+    iterate_changed(c);
     c->prep = 0; c->prep_timed = false;
     c->ipm_timed = c->time_ipm;
     c->ts_slot = -1;
@@ -1357,7 +1406,7 @@ extern "C" int tum_ocp_synchronize(tum_ocp *c)
     if (!c) return fail("null capsule");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return lin_uniform_check(c);
 }
 
 extern "C" int tum_ocp_solve(tum_ocp *c)
@@ -1367,6 +1416,7 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
     if (c->nlp_type) {
         if (launch_sqp(c)) return -1;
         if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
+        if (lin_uniform_check(c)) return -1;
         std::vector<int> st(c->batch);
         if (hipMemcpy(st.data(), c->dstatus, sizeof(int) * c->batch, hipMemcpyDeviceToHost) != hipSuccess) { fail("status copy failed"); return -1; }
         int mx = 0;
@@ -1379,6 +1429,7 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
             // a preparation has no results: 0 (acados >= 0.3 returns ACADOS_READY here; the reference's callers take any non-zero status for a failure)
             if (launch_prepare(c)) return -1;
             if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
+            if (lin_uniform_check(c)) return -1;
             return 0;
         }
     }
@@ -1399,6 +1450,7 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
         hipLaunchKernelGGL(pack_results_kernel, dim3(8), dim3(256), 0, c->stream, c->dX, c->dU, c->dcost, c->dstatus, c->dqpiter, N, (int)B,
                            c->hsum_s, c->hX_s, c->hU_s, c->hts_s);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
+        if (lin_uniform_check(c)) return -1;
         c->in_inflight = false;
         c->ts_slot = 2; c->cache_valid = true; c->xs_cached = false;
         int mx = 0;
@@ -1407,6 +1459,7 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
     }
     if (launch(c)) return -1;
     if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
+    if (lin_uniform_check(c)) return -1;
     std::vector<int> st(c->batch);
     if (hipMemcpy(st.data(), c->dstatus, sizeof(int) * c->batch, hipMemcpyDeviceToHost) != hipSuccess) { fail("status copy failed"); return -1; }
     int mx = 0;
@@ -1443,6 +1496,7 @@ extern "C" int tum_ocp_get_cost(tum_ocp *c, double *out, int b0, int nb)
     if (c->cache_valid) { for (int i = 0; i < nb; i++) out[i] = c->hsum_s[(size_t)(b0 + i) * 5 + 2]; return 0; }
     DevGuard guard(c->d.device); GUARD_OK(guard);
     HIPCHK(hipStreamSynchronize(c->stream));        // (the copy below runs on the NULL stream, which the capsule's non-blocking stream is not ordered with)
+    if (lin_uniform_check(c)) return 1;
     HIPCHK(hipMemcpy(out, c->dcost + b0, sizeof(double) * nb, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1461,6 +1515,7 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
         if (hipEventSynchronize(c->evi1) != hipSuccess || hipEventElapsedTime(&ms, c->evi0, c->evi1) != hipSuccess) return fail("get_stats time_ipm: no timing");
         *(double *)out = ms * 1e-3; return 0;
     }
+    if (f == "lin_uniform") { *(int *)out = c->n_lin_uniform; return 0; }      // linearisations that took the uniform path (one int)
     if (chk_range(c, b0, nb)) return 1;
     if (f == "sqp_iter" && !c->solved_sqp) { int *o = (int *)out; for (int i = 0; i < nb; i++) o[i] = 1; return 0; }      // (SQP-RTI: one QP per solve)
     if (f == "residuals" && !c->solved_sqp) return fail("get_stats residuals: computed by a full SQP solve only (options_set nlp_solver_type 1)");
@@ -1471,6 +1526,7 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
     }
     DevGuard guard(c->d.device); GUARD_OK(guard);
     HIPCHK(hipStreamSynchronize(c->stream));        // (after tum_ocp_solve_async: the copies below are on the NULL stream)
+    if (lin_uniform_check(c)) return 1;
     if (f == "qp_iter") { HIPCHK(hipMemcpy(out, c->dqpiter + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "status") { HIPCHK(hipMemcpy(out, c->dstatus + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "qp_status") { HIPCHK(hipMemcpy(out, c->dqpstatus + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
@@ -1489,7 +1545,8 @@ extern "C" int tum_ocp_reset(tum_ocp *c)
     HIPCHK(hipMemsetAsync(c->dX, 0, sizeof(double) * (size_t)c->batch * (c->N + 1) * NX, c->stream));
     HIPCHK(hipMemsetAsync(c->dU, 0, sizeof(double) * (size_t)c->batch * c->N * NU, c->stream));
     HIPCHK(hipMemsetAsync(c->dslack, 0, sizeof(double) * (size_t)c->batch * 6 * (size_t)c->N, c->stream));
-    c->cold = true;
+    c->cold = true; c->iter_uniform = true;          // (X = 0, U = 0 at every stage)
+    lin_uniform_rearm(c);
     if (c->sn) HIPCHK(hipMemsetAsync(c->dXS, 0, sizeof(double) * (size_t)c->batch * (c->N + 1) * c->sa.ns * NX, c->stream));
     if (c->sn) { HIPCHK(hipMemsetAsync(c->dxs_dirty, 0, sizeof(int) * (size_t)c->batch, c->stream)); c->xs_lazy = false; }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1507,6 +1564,8 @@ extern "C" int tum_ocp_cold_start(tum_ocp *c)
     if (c->sn) hipLaunchKernelGGL(snmpc_cold_start_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->dXS, c->dxs0, c->N, c->sa.ns, c->batch);
     if (c->sn) { HIPCHK(hipMemsetAsync(c->dxs_dirty, 0, sizeof(int) * (size_t)c->batch, c->stream)); c->xs_lazy = false; }
     HIPCHK(hipGetLastError());
+    c->iter_uniform = true;          // (X_k = x0, U_k = 0 at every stage)
+    lin_uniform_rearm(c);
     return 0;
 }
 
@@ -1660,7 +1719,7 @@ extern "C" int tum_ocp_results_wait(tum_ocp *c, const double **summary, const do
     if (X) *X = c->res_iter[r] ? c->hX[r] : nullptr;
     if (U) *U = c->res_iter[r] ? c->hU[r] : nullptr;
     c->res_head ^= 1; c->res_count--;
-    return 0;
+    return lin_uniform_check(c);
 }
 
 extern "C" int tum_ocp_step_async(tum_ocp *c, const double *x0, const double *yref, int with_iterate)
@@ -1729,6 +1788,7 @@ extern "C" int tum_ocp_put_device(tum_ocp *c, const char *field, const void *src
         HIPCHK(hipMemcpyAsync(c->dx0 + (size_t)b0 * NX, src, 8 * (size_t)nb * NX, hipMemcpyDeviceToDevice, s)); return 0;
     }
     if (f == "yref") { HIPCHK(hipMemcpyAsync(c->dyref + (size_t)b0 * (N + 1) * 6, src, 8 * (size_t)nb * (N + 1) * 6, hipMemcpyDeviceToDevice, s)); return 0; }
+    if (f == "X" || f == "U") iterate_changed(c);
     if (f == "X") { HIPCHK(hipMemcpyAsync(c->dX + (size_t)b0 * (N + 1) * NX, src, 8 * (size_t)nb * (N + 1) * NX, hipMemcpyDeviceToDevice, s)); return 0; }
     if (f == "U") { HIPCHK(hipMemcpyAsync(c->dU + (size_t)b0 * N * NU, src, 8 * (size_t)nb * N * NU, hipMemcpyDeviceToDevice, s)); return 0; }
     return fail("put_device: unknown field '" + f + "'");
@@ -2116,6 +2176,7 @@ extern "C" int tum_sim_advance(tum_sim *s)
     if (!c->solved) return fail("sim_advance: no solve yet");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     c->cache_valid = false;          // (the plant re-initialises the iterate of an instance whose solve failed, and writes the next x0)
+    iterate_changed(c);
     if (flush_inputs(c)) return 1;
     SimArgs sa;
     memset(&sa, 0, sizeof(sa));
@@ -2181,6 +2242,7 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
     if (c->rti_phase) return fail("sim_run: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
     DevGuard guard(c->d.device); GUARD_OK(guard);
     c->cache_valid = false;
+    iterate_changed(c);          // (the closed loop keeps the general linearisation: its chunks are captured and replayed)
     if (flush_inputs(c)) return 1;            // (pending host setters go up before anything is captured)
     if (resolve_kernel(c)) return 1;          // (workspace allocation must not happen inside the capture below)
     // ... nor the reallocation / synchronisation a changed SNMPC parameter vector can trigger, nor the deferred freeze
@@ -2199,10 +2261,12 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
             hipGraph_t g = nullptr;
             const int step0 = s->step;
             bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+            c->capturing = ok;
             if (ok) {
                 c->solved = true;                                      // the captured solve precedes every captured advance
                 for (int i = 0; i < GRAPH_STEPS && ok; i++) ok = sim_enqueue_step(s, false) == 0;
                 ok = (hipStreamEndCapture(c->stream, &g) == hipSuccess) && ok;
+                c->capturing = false;
                 s->step = step0;                                       // nothing ran yet
             }
             if (ok && g) ok = hipGraphInstantiate(&s->graph, g, nullptr, nullptr, 0) == hipSuccess;

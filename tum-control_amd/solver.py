@@ -322,7 +322,8 @@ class BatchedOcpSolver:
     def options_set(self, field, value):
         """acados_solver.options_set(field, value) for the NLP solver: 'nlp_solver_type' ('SQP_RTI' | 'SQP'), 'nlp_solver_max_iter',
         'nlp_solver_tol_stat' | '_eq' | '_ineq' | '_comp', 'nlp_solver_step_length' (include/tum_nmpc.h, tum_ocp_options_set);
-        'rti_phase' 0 | 1 | 2: the following solve() calls are whole SQP-RTI steps (default), preparations or feedbacks"""
+        'rti_phase' 0 | 1 | 2: the following solve() calls are whole SQP-RTI steps (default), preparations or feedbacks;
+        'lin_dedup' 1 | 0: linearise a stage-uniform iterate (after cold_start() / reset()) once per instance (default) or per stage"""
         if field == "rti_phase":
             value = _rti_phase_value(value)
         if field == "nlp_solver_type" and isinstance(value, str):
@@ -366,6 +367,10 @@ class BatchedOcpSolver:
             if field == "sqp_iter" and self.batch == 1:
                 return int(out[0])
             return out            # acados returns an array for qp_iter; callers take np.max
+        if field == "lin_uniform":      # linearisations that took the uniform path (options_set('lin_dedup', 0 | 1))
+            o = ctypes.c_int(0)
+            self._chk(self._L.tum_ocp_get_stats(self._h, field.encode(), ctypes.byref(o), 0, 1), "get_stats")
+            return o.value
         if field == "res":
             out = np.zeros((self.batch, 3))
             self._chk(self._L.tum_ocp_get_stats(self._h, b"res", out.ctypes.data_as(ctypes.c_void_p), 0, self.batch), "get_stats")
