@@ -264,16 +264,21 @@ def _stale_ops():
         s.put_device("X", t.data_ptr()); s.synchronize()
 
     return dict(set_x=set_x, set_u=set_u, set_yref=set_yref, cost_set_W=cost_w, cold_start=lambda s, X, U: s.cold_start(),
-                reset=lambda s, X, U: s.reset(), put_device_X=put_x)
+                reset=lambda s, X, U: s.reset(), put_device_X=put_x, sim_advance=lambda s, X, U: s.loop.advance())
 
 
-@pytest.mark.parametrize("op", ["set_x", "set_u", "set_yref", "cost_set_W", "cold_start", "reset", "put_device_X"])
+@pytest.mark.parametrize("op", ["set_x", "set_u", "set_yref", "cost_set_W", "cold_start", "reset", "put_device_X", "sim_advance"])
 def test_stale_preparation_is_refused(op):
     N, B = 40, 3
     x0, yref = _inputs(N, B)
     split, twin = _mk(N, B), _mk(N, B)
     for s in (split, twin):
         s.set_x0(x0); s.set_yref_all(yref); s.cold_start()
+        if op == "sim_advance":          # the plant of the device closed loop (it writes the iterate and x0): created in rti_phase 0, state as the capsule's
+            from tum_control_amd.planner import load_track
+            from tum_control_amd.solver import DeviceClosedLoop
+            s.loop = DeviceClosedLoop(s, load_track("monteblanco"), N * DT)
+            s.loop.set_state(x0[:, :7], x0, cold_start=True)
         assert s.solve() == 0
     X, U = twin.get_iterate()
     assert split.prepare() == 0

@@ -24,92 +24,95 @@
 
 using namespace tum;
 
+// an integer switch of the environment (include/tum_nmpc.h lists them)
+static int env_int(const char *name, int fallback) { const char *e = getenv(name); return e ? atoi(e) : fallback; }
+
 static thread_local std::string g_err;
 static int fail(const std::string &m) { g_err = m; return 1; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 struct tum_ocp {
-    tum_ocp_desc d;
-    int N, batch;
-    hipStream_t stream; bool own_stream;
-    hipEvent_t ev0, ev1;
-    KArgs ka;
-    double *dx0_own, *dyref_own;        // the capsule's own x0 / yref arrays; dx0 / dyref below are what is IN USE (tum_ocp_bind_device: the caller's)
-    double *dX, *dU, *dx0, *dyref, *dW, *dpen, *dbnd, *dcost, *dres, *dslack, *dqpin, *ddbg, *dqplam;
-    double *dWf;                       // full W per stage, [b][N+1][36] (allocated by the first cost_set 'W' with an off-diagonal entry; null: diagonal W)
-    int *dstatus, *dqpiter, *dqpstatus, *dorder;
-    bool lpt, order_valid;
-    long long *dprof;
-    double *dws, *dhws;
-    int kmode;                     // 0 auto (= the pipeline), 1 fused, 2 pipeline, 3 pipeline with the four-wavefront interior point kernel
-    unsigned epoch;                // bumped by everything a captured launch bakes into its kernel arguments (kernel variant, schedule,
+    tum_ocp_desc d{};
+    int N = 0, batch = 0;
+    hipStream_t stream = nullptr; bool own_stream = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    KArgs ka{};
+    double *dx0_own = nullptr, *dyref_own = nullptr;        // the capsule's own x0 / yref arrays; dx0 / dyref below are what is IN USE (tum_ocp_bind_device: the caller's)
+    double *dX = nullptr, *dU = nullptr, *dx0 = nullptr, *dyref = nullptr, *dW = nullptr, *dpen = nullptr, *dbnd = nullptr, *dcost = nullptr, *dres = nullptr,
+           *dslack = nullptr, *dqpin = nullptr, *ddbg = nullptr, *dqplam = nullptr;
+    double *dWf = nullptr;             // full W per stage, [b][N+1][36] (allocated by the first cost_set 'W' with an off-diagonal entry; null: diagonal W)
+    int *dstatus = nullptr, *dqpiter = nullptr, *dqpstatus = nullptr, *dorder = nullptr;
+    bool lpt = true, order_valid = false;
+    long long *dprof = nullptr;
+    double *dws = nullptr, *dhws = nullptr;
+    int kmode = 0;                 // 0 auto (= the pipeline), 1 fused, 2 pipeline, 3 pipeline with the four-wavefront interior point kernel
+    unsigned epoch = 0;            // bumped by everything a captured launch bakes into its kernel arguments (kernel variant, schedule,
                                    // SNMPC horizon / risk parameter / work buffers, R2 attachment): tum_sim_run re-captures its graph
-    bool pipe;                     // this solve runs the four-kernel pipeline (resolved from kmode at launch)
-    bool solved_pipe;              // the LAST solve ran the pipeline: its linearisation is in the stage records, not in qpin
-    double *drec, *dcws, *dvec;    // pipeline workspace: stage records, gg rows in operand layout, q | d | dv
-    hipEvent_t evi0, evi1;         // around the interior point kernel of the pipeline
-    bool skip_ipm_events, ipm_timed;   // a step leaves them out (tum_ocp_step_async); was the LAST solve timed with them
-    float last_ms;
-    bool solved;
+    bool pipe = false;             // this solve runs the four-kernel pipeline (resolved from kmode at launch)
+    bool solved_pipe = false;      // the LAST solve ran the pipeline: its linearisation is in the stage records, not in qpin
+    double *drec = nullptr, *dcws = nullptr, *dvec = nullptr;    // pipeline workspace: stage records, gg rows in operand layout, q | d | dv
+    hipEvent_t evi0 = nullptr, evi1 = nullptr;         // around the interior point kernel of the pipeline
+    bool skip_ipm_events = false, ipm_timed = false;   // a step leaves them out (tum_ocp_step_async); was the LAST solve timed with them
+    float last_ms = 0;
+    bool solved = false;
     std::vector<double> stage;     // host staging
     // coupled SNMPC OCP (tum_ocp_snmpc_attach)
-    bool sn;
-    SnArgs sa;
-    double *dXS, *dxs0, *dApce, *dws2, *dpro, *ddv, *doffs;
-    int *dxs_dirty; bool xs_lazy;          // sample copies of the stages > uph not yet frozen (snmpc_freeze_kernel)
-    bool have_offs, fanout;        // sample initial conditions derived from the nominal x0 at every solve
-    int sim_fork; bool lin_ahead;      // device closed loop: linearisation beside the planner (-1 the library's choice, 0 never, 1 where possible); state of one step
-    int cond_wide;                     // condensing with six wavefronts per OCP: -1 the library's choice (at most one workgroup per CU), 0 never, 1 always
-    int lin_cols;                      // linearisation with eight lanes per (instance, stage): -1 the library's choice (small batches), 0 never, 1 always (tum_ocp_set_kernel)
-    int sn_prologue;                   // prologue of the SNMPC OCP: -1 the library's choice, 2 the matrix-core kernel, 0 column slots and passes (tum_ocp_set_kernel)
+    bool sn = false;
+    SnArgs sa{};
+    double *dXS = nullptr, *dxs0 = nullptr, *dApce = nullptr, *dws2 = nullptr, *dpro = nullptr, *ddv = nullptr, *doffs = nullptr;
+    int *dxs_dirty = nullptr; bool xs_lazy = false;          // sample copies of the stages > uph not yet frozen (snmpc_freeze_kernel)
+    bool have_offs = false, fanout = false;        // sample initial conditions derived from the nominal x0 at every solve
+    int sim_fork = -1; bool lin_ahead = false;      // device closed loop: linearisation beside the planner (-1 the library's choice, 0 never, 1 where possible); state of one step
+    int cond_wide = -1;                // condensing with six wavefronts per OCP: -1 the library's choice (at most one workgroup per CU), 0 never, 1 always
+    int lin_cols = -1;                 // linearisation with eight lanes per (instance, stage): -1 the library's choice (small batches), 0 never, 1 always (tum_ocp_set_kernel)
+    int sn_prologue = -1;              // prologue of the SNMPC OCP: -1 the library's choice, 2 the matrix-core kernel, 0 column slots and passes (tum_ocp_set_kernel)
     // R2NMPC tightening after every solve (tum_ocp_r2_attach)
-    bool r2; int r2_uph; double r2_dmin, r2_dmax, r2_uh; double *dr2S, *dr2B;
+    bool r2 = false; int r2_uph = 0; double r2_dmin = 0, r2_dmax = 0, r2_uh = 0; double *dr2S = nullptr, *dr2B = nullptr;
     // per-stage parameter vector of the SNMPC OCP as the caller last set it (tum_ocp_set "p")
-    std::vector<double> hApce, p_gamma, p_stop; bool p_dirty; int uph_cap; size_t pro_cap; double gamma;
+    std::vector<double> hApce, p_gamma, p_stop; bool p_dirty = false; int uph_cap = 0; size_t pro_cap = 0; double gamma = 0.0;
     // PCE matrix of the scenario fan-out (tum_pce_attach), snapshot of the bounds (tum_ocp_bounds_snapshot)
-    double *dpceA; int pce_L, pce_S; double *dbnd_snap;
+    double *dpceA = nullptr; int pce_L = 0, pce_S = 0; double *dbnd_snap = nullptr;
     // results on the host without a stream stall (tum_ocp_results_async / _wait): device slab of the packed summary, pinned
     // host slabs, the event behind the copies
     // two sets, used in turn: the request for the NEXT batch can be enqueued before the previous batch's results have been read
-    double *dsum, *hsum[2], *hX[2], *hU[2]; hipEvent_t evres[2]; bool res_iter[2]; int res_head, res_count;
-    double *hin[2];                    // pinned staging of x0 | yref of a step (tum_ocp_step_async), one per result slot
-    unsigned long long *hts[2];        // device wall clock at the start / end of a step timed without events (pinned, one pair per result slot)
-    int ts_slot; double ts_khz;        // slot whose clock pair times the LAST solve (-1: the events ev0 / ev1 do; 2: the synchronous slot below)
+    double *dsum = nullptr, *hsum[2] = {}, *hX[2] = {}, *hU[2] = {}; hipEvent_t evres[2] = {}; bool res_iter[2] = {}; int res_head = 0, res_count = 0;
+    double *hin[2] = {};               // pinned staging of x0 | yref of a step (tum_ocp_step_async), one per result slot
+    unsigned long long *hts[2] = {};   // device wall clock at the start / end of a step timed without events (pinned, one pair per result slot)
+    int ts_slot = -1; double ts_khz = 0.0;   // slot whose clock pair times the LAST solve (-1: the events ev0 / ev1 do; 2: the synchronous slot below)
     // The reference's LITERAL call pattern on a small capsule (NMPC_class.py:169-206: N+1 x set yref, solve, 1 + N x get, get_cost,
     // 3 x get_stats -- every one a synchronous call): the per-step setters land in a pinned shadow of x0 | yref with a dirty map and go
     // up in ONE kernel in front of the next solve; a synchronous solve ends with ONE kernel that writes summary, X and U into pinned
     // slabs, and the getters that follow are served from those slabs until something changes the iterate. 83 calls of ~21 us each
     // (a stream synchronisation per call) become one solve and 82 host copies.
-    double *hin_s; unsigned long long in_mask; bool in_x0, in_inflight; hipEvent_t ev_in;      // shadow of x0 | yref, dirty stages, upload in flight
-    double *hsum_s, *hX_s, *hU_s; unsigned long long *hts_s; bool cache_valid;                 // results of the last synchronous solve
-    double *hXS_s; bool xs_cached;                                                             // ... and the sample copies of an SNMPC capsule, read back on first use
-    bool time_ipm;                     // keep the events around the interior point kernel also where the library leaves them out (tum_ocp_set_kernel "time-ipm")
+    double *hin_s = nullptr; unsigned long long in_mask = 0; bool in_x0 = false, in_inflight = false; hipEvent_t ev_in = nullptr;      // shadow of x0 | yref, dirty stages, upload in flight
+    double *hsum_s = nullptr, *hX_s = nullptr, *hU_s = nullptr; unsigned long long *hts_s = nullptr; bool cache_valid = false;     // results of the last synchronous solve
+    double *hXS_s = nullptr; bool xs_cached = false;                                           // ... and the sample copies of an SNMPC capsule, read back on first use
+    bool time_ipm = false;             // keep the events around the interior point kernel also where the library leaves them out (tum_ocp_set_kernel "time-ipm")
     // full SQP solves (tum_ocp_options_set): the options, the device state of the loop (allocated by the first SQP solve), whether the
     // LAST solve was one
-    int nlp_type, nlp_max_iter; double nlp_tol[4], nlp_alpha;
-    double *dnlpres, *dsnap; int *dsqpstate, *dsqpiter, *dsnapi; unsigned *dactive, *hactive; int active_cap; hipEvent_t evpoll[2];
-    bool solved_sqp;
+    // (defaults of the reference's generated solver, acados_ocp_SNMPC.json: SQP_RTI; for SQP 100 iterations, tolerances 1e-6, full steps)
+    int nlp_type = 0, nlp_max_iter = 100; double nlp_tol[4] = {1e-6, 1e-6, 1e-6, 1e-6}, nlp_alpha = 1.0;
+    double *dnlpres = nullptr, *dsnap = nullptr; int *dsqpstate = nullptr, *dsqpiter = nullptr, *dsnapi = nullptr;
+    unsigned *dactive = nullptr, *hactive = nullptr; int active_cap = 0; hipEvent_t evpoll[2] = {};
+    bool solved_sqp = false;
     // no solve since the last cold start / reset: the multipliers and slacks on the device are those of an EARLIER problem. An SQP-RTI
     // solve never reads them (the warm-start word is 0); a full SQP solve evaluates pass 0 with them and damps towards them, so it clears
     // them first (acados' reset() zeroes them)
-    bool cold;
+    bool cold = true;
     // split real-time iteration (tum_ocp_options_set "rti_phase"): 0 preparation and feedback in one solve, 1 the next solves are
     // PREPARATIONS (linearisation and condensing), 2 FEEDBACKS (rti_feedback_kernel, interior point method, expansion).
     // prep: 0 no preparation pending, 1 the workspace holds the condensed QP of a preparation at dx0prep, 2 that preparation is
     // STALE: something it had read (iterate, reference, W, kernel variant, bound arrays) changed behind it
-    int rti_phase, prep; double *dx0prep; bool prep_timed;
+    int rti_phase = 0, prep = 0; double *dx0prep = nullptr; bool prep_timed = false;
     // linearisation of a STAGE-UNIFORM iterate once per instance (lin_uniform_kernel + lin_fill_kernel, pipe_kernels.hpp).
     // iter_uniform: X_k = X_0 and U_k = U_0 for every k -- set by cold_start() and reset(), cleared by everything that writes dX / dU
-    // (iterate_changed below). lin_dedup: options_set "lin_dedup", 1 by default. n_lin_uniform: linearisations that took the
+    // (invalidate below). lin_dedup: options_set "lin_dedup", 1 by default. n_lin_uniform: linearisations that took the
     // uniform path (get_stats "lin_uniform"). hlin_bad: pinned word lin_fill_kernel sets when it finds a stage that differs from
     // stage 0 -- an invalidation missed here; checked at the synchronous entry points (lin_uniform_check).
     // capturing: tum_sim_run is recording a chunk of the closed loop into a graph (a captured launch is replayed on other iterates)
-    bool iter_uniform, capturing; int lin_dedup; int n_lin_uniform; double *dlin1; int *hlin_bad;
+    bool iter_uniform = false, capturing = false; int lin_dedup = 1; int n_lin_uniform = 0; double *dlin1 = nullptr; int *hlin_bad = nullptr;
 };
 
-// everything that changes what a preparation has read calls this (x0, the bounds of the stages >= 1 and the slack penalties are read
-// by the feedback: they do not)
-static void prep_stale(tum_ocp *c) { if (c->prep == 1) c->prep = 2; }
 // cold_start() / reset() re-initialise the iterate: a capsule the safety net has failed works again from there. The word may only be
 // written once the kernels that could still set it have finished (they never do in a correct library: the wait is paid after an error only)
 static void lin_uniform_rearm(tum_ocp *c)
@@ -118,16 +121,61 @@ static void lin_uniform_rearm(tum_ocp *c)
     (void)hipStreamSynchronize(c->stream);
     *(volatile int *)c->hlin_bad = 0;
 }
-// every entry point that writes the iterate (dX, dU) calls this: the next linearisation is the general one
-static void iterate_changed(tum_ocp *c) { c->iter_uniform = false; }
 // the safety net of the uniform linearisation, at the points where the host has waited for the stream anyway
 static int lin_uniform_check(const tum_ocp *c)
 {
+    // (the text is part of the interface and keeps its wording: the call it names is invalidate(c, CH_ITERATE) below)
     if (c->hlin_bad && *(volatile int *)c->hlin_bad)
         return fail("the uniform linearisation (lin_dedup) ran on an iterate that was NOT the same at every stage: the results since the last "
                     "cold_start() / reset() are wrong. This is a bug of the library (a writer of the iterate that does not call iterate_changed). "
                     "Every synchronous call fails until the next cold_start() / reset(); options_set('lin_dedup', 0) before it avoids the path");
     return 0;
+}
+
+// What an entry point WROTE. It says so to invalidate() and sets none of the flags below itself.
+enum : unsigned {
+    CH_ITERATE = 1,       // dX / dU (the sample copies with them)
+    CH_RESTART = 2,       // cold_start() / reset() have enqueued their re-initialisation: the iterate is the same at every stage now, and
+                          // there has been no solve since. Passed on its own, behind the CH_ITERATE of the same entry point
+    CH_REF = 4,           // the reference (tum_sim_set_state: the pose the planner derives the next one from)
+    CH_W = 8,             // W, diagonal or full
+    CH_X0 = 16,           // x0, of the nominal copy or the samples
+    CH_BOUNDS = 32,       // bounds of the stages >= 1, slack penalties
+    CH_VARIANT = 64,      // the kernel variant, the array x0 / yref is bound to
+    CH_CAPTURED = 128,    // something a captured launch holds by value (tum_ocp::epoch)
+    CH_RESULTS = 256,     // cost, status and iteration counts: a solve is being enqueued
+    CH_UPLOAD = 512       // tum_ocp_put_device / tum_sim_set_state uploaded an input. Nothing the getters serve changed, but both have
+                          // always dropped the cache, and that is kept
+};
+// The one place that knows what a write invalidates. Per row:
+//   prep     a pending preparation has read it: 1 -> 2, the feedback is refused (x0, the bounds of the stages >= 1 and the slack
+//            penalties are read by the feedback itself: they do not -- their rows say so and do nothing else)
+//   cache    the pinned slabs the getters are served from (tum_ocp_solve) and the SNMPC sample copies beside them are dropped. The host
+//            setters of yref / W / x0 / bounds leave them: the 83-call control step sets the next step's inputs behind its getters
+//   uniform  -1 the next linearisation is the general one, +1 it may be the uniform one (and the multipliers are an earlier problem's)
+//   epoch    tum_sim_run captures its chunk again
+static void invalidate(tum_ocp *c, unsigned what)
+{
+    static const struct { unsigned bit; bool prep, cache; int uniform; bool epoch; } table[] = {
+        {CH_ITERATE,  true,  true,  -1, false},
+        {CH_RESTART,  false, false, +1, false},
+        {CH_REF,      true,  false,  0, false},
+        {CH_W,        true,  false,  0, false},
+        {CH_X0,       false, false,  0, false},
+        {CH_BOUNDS,   false, false,  0, false},
+        {CH_VARIANT,  true,  false,  0, false},
+        {CH_CAPTURED, false, false,  0, true},
+        {CH_RESULTS,  false, true,   0, false},
+        {CH_UPLOAD,   false, true,   0, false},
+    };
+    for (const auto &r : table) {
+        if (!(what & r.bit)) continue;
+        if (r.prep && c->prep == 1) c->prep = 2;
+        if (r.cache) c->cache_valid = c->xs_cached = false;
+        if (r.uniform) c->iter_uniform = r.uniform > 0;
+        if (r.uniform > 0) { c->cold = true; lin_uniform_rearm(c); }
+        if (r.epoch) c->epoch++;
+    }
 }
 
 static const int DBG_STRIDE = 20480;
@@ -172,6 +220,21 @@ static hipError_t dalloc(T **p, size_t n)
     return e;
 }
 
+// the vehicle constants the OCP's model (Model) and the plant of the closed loop (PlantModel) share
+template <typename M>
+static void vehicle_constants(M &m, const tum_ocp_desc &d)
+{
+    m.lf = d.lf; m.lr = d.lr; m.m = d.m; m.inv_m = 1.0 / d.m; m.inv_Iz = 1.0 / d.Iz;
+    m.ka = 0.5 * d.ro * d.S * d.Cd;
+    m.Bf = d.Bf; m.Cf = d.Cf; m.Df = d.Df; m.Ef = d.Ef;
+    m.Br = d.Br; m.Cr = d.Cr; m.Dr = d.Dr; m.Er = d.Er;
+    m.Fz_f = d.m * d.lr * d.g / (d.lf + d.lr);
+    m.Fz_r = d.m * d.lf * d.g / (d.lf + d.lr);
+    m.invFmax_f = 1.0 / std::sqrt(m.Fz_f * m.Fz_f + (d.Cf * m.Fz_f) * (d.Cf * m.Fz_f));
+    m.invFmax_r = 1.0 / std::sqrt(m.Fz_r * m.Fz_r + (d.Cr * m.Fz_r) * (d.Cr * m.Fz_r));
+    m.fr0 = d.fr0; m.fr1 = d.fr1; m.fr4 = d.fr4;
+}
+
 extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
 {
     if (!desc) { fail("null desc"); return nullptr; }
@@ -184,21 +247,7 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
     if (desc->device < 0 || desc->device >= ndev) { fail("device ordinal out of range"); return nullptr; }
     DevGuard guard(desc->device); if (!guard.ok) { fail("hipSetDevice failed"); return nullptr; }
     tum_ocp *c = new tum_ocp();
-    c->d = *desc; c->N = desc->N; c->batch = desc->batch; c->last_ms = 0; c->solved = false; c->epoch = 0;
-    c->sn = false; c->dXS = c->dxs0 = c->dApce = c->dws2 = c->dpro = c->ddv = c->doffs = nullptr; c->dxs_dirty = nullptr; c->xs_lazy = false;
-    c->have_offs = c->fanout = false; c->sn_prologue = -1; c->lin_cols = -1; c->cond_wide = -1; c->sim_fork = -1; c->lin_ahead = false;
-    c->r2 = false; c->dr2S = c->dr2B = nullptr;
-    c->p_dirty = false; c->uph_cap = 0; c->gamma = 0.0; c->dpceA = nullptr; c->pce_L = c->pce_S = 0; c->dbnd_snap = nullptr;
-    c->dsum = nullptr; c->res_head = c->res_count = 0;
-    c->hin_s = c->hsum_s = c->hX_s = c->hU_s = nullptr; c->hts_s = nullptr; c->in_mask = 0; c->in_x0 = c->in_inflight = false; c->ev_in = nullptr;
-    c->cache_valid = false; c->time_ipm = false; c->hXS_s = nullptr; c->xs_cached = false;
-    // (defaults of the reference's generated solver, acados_ocp_SNMPC.json: SQP_RTI; for SQP 100 iterations, tolerances 1e-6, full steps)
-    c->nlp_type = 0; c->nlp_max_iter = 100; for (double &t : c->nlp_tol) t = 1e-6; c->nlp_alpha = 1.0;
-    c->dnlpres = c->dsnap = nullptr; c->dsqpstate = c->dsqpiter = c->dsnapi = nullptr; c->dactive = c->hactive = nullptr; c->active_cap = 0;
-    c->evpoll[0] = c->evpoll[1] = nullptr; c->solved_sqp = false; c->cold = true;
-    c->rti_phase = 0; c->prep = 0; c->dx0prep = nullptr; c->prep_timed = false;
-    c->iter_uniform = false; c->capturing = false; c->lin_dedup = 1; c->n_lin_uniform = 0; c->dlin1 = nullptr; c->hlin_bad = nullptr;
-    for (int i = 0; i < 2; i++) { c->hsum[i] = c->hX[i] = c->hU[i] = c->hin[i] = nullptr; c->hts[i] = nullptr; c->evres[i] = nullptr; c->res_iter[i] = false; }
+    c->d = *desc; c->N = desc->N; c->batch = desc->batch;
     const int N = c->N; const size_t B = c->batch;
     bool ok = true;
     ok &= hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess; c->own_stream = true;
@@ -229,23 +278,19 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
         ok &= hipMemcpy(c->dorder, id.data(), sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
         c->order_valid = true;
     }
-    c->dqpin = nullptr;
 #ifdef TUM_DEV_KERNELS      // (only the fused kernel writes A | B | b per stage; the pipeline's stage records hold them)
     if (desc->store_qp_in) ok &= dalloc(&c->dqpin, B * N * 88) == hipSuccess;
 #endif
     ok &= dalloc(&c->ddbg, (size_t)DBG_STRIDE * DBG_INST) == hipSuccess;
     ok &= dalloc(&c->dprof, B * 12) == hipSuccess;
-    c->dws = nullptr;
 #ifdef TUM_DEV_KERNELS      // (linearisation records parked by the fused kernel during its interior point loop)
     ok &= dalloc(&c->dws, B * WS_DOUBLES) == hipSuccess;
 #endif
-    c->dhws = nullptr;
     { const char *e = getenv("TUM_NMPC_KERNEL"); const std::string k(e ? e : "auto"); c->kmode = (k == "pipeline") ? 2 : 0;
 #ifdef TUM_DEV_KERNELS
       if (k == "fused") c->kmode = 1; else if (k == "pipeline4") c->kmode = 3;
 #endif
-      c->pipe = false; c->solved_pipe = false; }
-    c->drec = c->dcws = c->dvec = nullptr; c->evi0 = c->evi1 = nullptr; c->skip_ipm_events = c->ipm_timed = false; c->ts_slot = -1; c->ts_khz = 0.0;
+    }
     ok &= hipEventCreate(&c->evi0) == hipSuccess && hipEventCreate(&c->evi1) == hipSuccess;
     if (!ok) { fail("device allocation failed"); tum_ocp_free(c); return nullptr; }
 
@@ -268,15 +313,7 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
       ka.warm_flips = (e && e[0] == '0') ? -1 : (desc->qp_warm_flips != 0 ? desc->qp_warm_flips : 16);
       ka.warm_viol = desc->qp_warm_viol > 0 ? desc->qp_warm_viol : 0.1; }
     Model &m = ka.mp;
-    m.lf = desc->lf; m.lr = desc->lr; m.m = desc->m; m.inv_m = 1.0 / desc->m; m.inv_Iz = 1.0 / desc->Iz;
-    m.ka = 0.5 * desc->ro * desc->S * desc->Cd;
-    m.Bf = desc->Bf; m.Cf = desc->Cf; m.Df = desc->Df; m.Ef = desc->Ef;
-    m.Br = desc->Br; m.Cr = desc->Cr; m.Dr = desc->Dr; m.Er = desc->Er;
-    m.Fz_f = desc->m * desc->lr * desc->g / (desc->lf + desc->lr);
-    m.Fz_r = desc->m * desc->lf * desc->g / (desc->lf + desc->lr);
-    m.invFmax_f = 1.0 / std::sqrt(m.Fz_f * m.Fz_f + (desc->Cf * m.Fz_f) * (desc->Cf * m.Fz_f));
-    m.invFmax_r = 1.0 / std::sqrt(m.Fz_r * m.Fz_r + (desc->Cr * m.Fz_r) * (desc->Cr * m.Fz_r));
-    m.fr0 = desc->fr0; m.fr1 = desc->fr1; m.fr4 = desc->fr4;
+    vehicle_constants(m, *desc);
     m.ax_brake = -desc->acc_min;
     m.n_ggv = desc->n_ggv;
     for (int i = 0; i < 16; i++) { m.ggv_v[i] = desc->ggv_v[i]; m.ggv_ax[i] = desc->ggv_ax[i]; m.ggv_ay[i] = desc->ggv_ay[i]; }
@@ -408,7 +445,7 @@ extern "C" int tum_ocp_snmpc_attach(tum_ocp *c, int ns, int L, const double *Apc
     c->p_gamma.assign(N + 1, gamma); c->p_stop.assign(N + 1, 0.0);
     for (int k = uph; k <= N; k++) c->p_stop[k] = 1.0;
     c->p_dirty = false;
-    c->epoch++;
+    invalidate(c, CH_CAPTURED);
     return 0;
 }
 
@@ -445,7 +482,7 @@ static void sn_launch_lin(tum_ocp *c)
     const long long items = (long long)c->batch * c->sa.uph * c->sa.ns;
     if (items <= 0) return;
     // eight lanes per item while that still is one round of wavefronts on the chip (the same rule as launch_pipeline's for lin_cols_kernel)
-    static const int cols_env = [] { const char *e = getenv("TUM_LIN_COLS"); return e ? atoi(e) : -1; }();
+    static const int cols_env = env_int("TUM_LIN_COLS", -1);
     const int want = (c->lin_cols >= 0) ? c->lin_cols : cols_env;
     if (want > 0 || (want < 0 && items * SLC_LANES <= 64LL * 1024))
         hipLaunchKernelGGL(snmpc_lin_cols_kernel, dim3((unsigned)((items + SLC_ITEMS - 1) / SLC_ITEMS)), dim3(64), 0, c->stream, c->sa);
@@ -516,7 +553,7 @@ static int sn_apply_p(tum_ocp *c)
     c->sa.kappa = std::sqrt((1.0 - c->gamma) / c->gamma);
     c->sa.uph = uph; c->ka.uph = uph;
     c->p_dirty = false;
-    c->epoch++;                                   // (uph, kappa and the work buffers are kernel arguments of a captured launch)
+    invalidate(c, CH_CAPTURED);                   // (uph, kappa and the work buffers are kernel arguments of a captured launch)
     return 0;
 }
 extern "C" int tum_ocp_snmpc_samples(const tum_ocp *c) { return (c && c->sn) ? c->sa.ns : 0; }
@@ -588,6 +625,7 @@ static int shadow_write(tum_ocp *c, int stage, const double *v, int len, int str
         memcpy(dst, src, sizeof(double) * len);
     }
     if (stage < 0) c->in_x0 = true; else c->in_mask |= 1ull << stage;
+    invalidate(c, stage < 0 ? CH_X0 : CH_REF);
     return 0;
 }
 // pending setters -> device, one kernel on the capsule's stream (ts: the device clock at its start goes to ts[0])
@@ -603,13 +641,13 @@ static int flush_inputs(tum_ocp *c, unsigned long long *ts = nullptr, bool force
     return 0;
 }
 
-// strided scatter: host records (nb x len, `stride` apart; stride 0 = broadcast) -> device rows
-static int put(tum_ocp *c, double *dbase, size_t rec, size_t off, const double *v, int len, int b0, int nb, int stride)
+// strided scatter: host records (nb x len, `stride` apart; stride 0 = broadcast) -> device rows; what: CH_* of the array written
+static int put(tum_ocp *c, unsigned what, double *dbase, size_t rec, size_t off, const double *v, int len, int b0, int nb, int stride)
 {
     if (stride != 0 && stride < len) return fail("stride < len");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    if ((dbase == c->dx0 || dbase == c->dyref) && flush_inputs(c)) return 1;          // (older setters still in the shadow go first)
-    if (dbase == c->dX || dbase == c->dU) { c->cache_valid = false; iterate_changed(c); }
+    if ((what & (CH_X0 | CH_REF)) && flush_inputs(c)) return 1;          // (older setters still in the shadow go first)
+    invalidate(c, what);
     const double *src = v;
     size_t spitch = (size_t)stride * sizeof(double);
     if (stride == 0) {
@@ -638,35 +676,34 @@ extern "C" int tum_ocp_set(tum_ocp *c, int stage, const char *field, const doubl
     if (!field || !v) return fail("null argument");
     const int N = c->N;
     const std::string f(field);
-    if (f == "x" || f == "u" || f == "yref") prep_stale(c);
     if (f == "x") {
-        if (stage == TUM_ALL_STAGES) { if (len != (N + 1) * NX) return fail("set x: len != (N+1)*8"); return put(c, c->dX, (N + 1) * NX, 0, v, len, b0, nb, stride); }
+        if (stage == TUM_ALL_STAGES) { if (len != (N + 1) * NX) return fail("set x: len != (N+1)*8"); return put(c, CH_ITERATE, c->dX, (N + 1) * NX, 0, v, len, b0, nb, stride); }
         if (stage < 0 || stage > N) return fail("set x: stage out of range");
         if (c->sn && len == NX * (c->sa.ns + 1)) {   // stacked state: nominal copy, then the sample copies (SNMPC_class.py:126-127)
             if (stride != 0 && stride < len) return fail("stride < len");
             const int ns = c->sa.ns;
             // (a write to stage uph would change what the deferred freeze copies into the stages behind it: freeze first)
             if (stage >= c->sa.uph && sn_materialise(c)) return 1;
-            if (put(c, c->dX, (N + 1) * NX, (size_t)stage * NX, v, NX, b0, nb, stride)) return 1;
-            return put(c, c->dXS, (size_t)(N + 1) * ns * NX, (size_t)stage * ns * NX, v + NX, ns * NX, b0, nb, stride);
+            if (put(c, CH_ITERATE, c->dX, (N + 1) * NX, (size_t)stage * NX, v, NX, b0, nb, stride)) return 1;
+            return put(c, CH_ITERATE, c->dXS, (size_t)(N + 1) * ns * NX, (size_t)stage * ns * NX, v + NX, ns * NX, b0, nb, stride);
         }
         if (len != NX) return fail("set x: mismatching dimension, expected 8");
-        return put(c, c->dX, (N + 1) * NX, (size_t)stage * NX, v, len, b0, nb, stride);
+        return put(c, CH_ITERATE, c->dX, (N + 1) * NX, (size_t)stage * NX, v, len, b0, nb, stride);
     }
     if (f == "u") {
-        if (stage == TUM_ALL_STAGES) { if (len != N * NU) return fail("set u: len != N*2"); return put(c, c->dU, N * NU, 0, v, len, b0, nb, stride); }
+        if (stage == TUM_ALL_STAGES) { if (len != N * NU) return fail("set u: len != N*2"); return put(c, CH_ITERATE, c->dU, N * NU, 0, v, len, b0, nb, stride); }
         if (stage < 0 || stage >= N) return fail("set u: stage out of range");
         if (len != NU) return fail("set u: mismatching dimension, expected 2");
-        return put(c, c->dU, N * NU, (size_t)stage * NU, v, len, b0, nb, stride);
+        return put(c, CH_ITERATE, c->dU, N * NU, (size_t)stage * NU, v, len, b0, nb, stride);
     }
     if (f == "yref") {
-        if (stage == TUM_ALL_STAGES) { if (len != (N + 1) * 6) return fail("set yref: len != (N+1)*6"); return put(c, c->dyref, (N + 1) * 6, 0, v, len, b0, nb, stride); }
+        if (stage == TUM_ALL_STAGES) { if (len != (N + 1) * 6) return fail("set yref: len != (N+1)*6"); return put(c, CH_REF, c->dyref, (N + 1) * 6, 0, v, len, b0, nb, stride); }
         if (stage < 0 || stage > N) return fail("set yref: stage out of range");
         const int want = (stage < N) ? TUM_NY : TUM_NYE;
         if (len != want) return fail("set yref: mismatching dimension for this stage");
         // the reference sets one stage per call, N + 1 calls per control step (NMPC_class.py:169-180): into the shadow, up with the solve
         if (b0 == 0 && nb == c->batch && small_inputs(c) && (stride == 0 || stride >= len)) return shadow_write(c, stage, v, len, stride);
-        return put(c, c->dyref, (N + 1) * 6, (size_t)stage * 6, v, len, b0, nb, stride);
+        return put(c, CH_REF, c->dyref, (N + 1) * 6, (size_t)stage * 6, v, len, b0, nb, stride);
     }
     if (f == "p") {
         if (b0 != 0 || nb != c->batch) return fail("set p: the parameter vector is shared by all instances (b0 = 0, nb = batch)");
@@ -772,8 +809,8 @@ extern "C" int tum_ocp_constraints_set(tum_ocp *c, int stage, const char *field,
             if (c->sn && len == NX * (c->sa.ns + 1)) {   // x0 of all copies (SNMPC_class.py:262-264)
                 if (stride != 0 && stride < len) return fail("stride < len");
                 c->fanout = false;
-                if (put(c, c->dx0, NX, 0, v, NX, b0, nb, stride)) return 1;
-                return put(c, c->dxs0, (size_t)c->sa.ns * NX, 0, v + NX, c->sa.ns * NX, b0, nb, stride);
+                if (put(c, CH_X0, c->dx0, NX, 0, v, NX, b0, nb, stride)) return 1;
+                return put(c, CH_X0, c->dxs0, (size_t)c->sa.ns * NX, 0, v + NX, c->sa.ns * NX, b0, nb, stride);
             }
             if (len != NX) return fail("constraints_set lbx/ubx at stage 0: expected 8 values (x0)");
             if (c->sn) {
@@ -782,20 +819,20 @@ extern "C" int tum_ocp_constraints_set(tum_ocp *c, int stage, const char *field,
             }
             // (set twice per control step, lbx and ubx: NMPC_class.py:243-246)
             if (b0 == 0 && nb == c->batch && small_inputs(c) && (stride == 0 || stride >= len)) return shadow_write(c, -1, v, len, stride);
-            return put(c, c->dx0, NX, 0, v, len, b0, nb, stride);
+            return put(c, CH_X0, c->dx0, NX, 0, v, len, b0, nb, stride);
         }
         if (len != 1) return fail("constraints_set lbx/ubx: expected 1 value (steering angle)");
-        return put(c, c->dbnd, 6 * NB, (size_t)(f == "lbx" ? 2 : 3) * NB + stage, v, 1, b0, nb, stride);
+        return put(c, CH_BOUNDS, c->dbnd, 6 * NB, (size_t)(f == "lbx" ? 2 : 3) * NB + stage, v, 1, b0, nb, stride);
     }
     if (f == "lbu" || f == "ubu") {
         if (stage >= N) return fail("constraints_set lbu/ubu: stage out of range");
         if (len != 1) return fail("constraints_set lbu/ubu: expected 1 value (steering rate)");
-        return put(c, c->dbnd, 6 * NB, (size_t)(f == "lbu" ? 0 : 1) * NB + stage, v, 1, b0, nb, stride);
+        return put(c, CH_BOUNDS, c->dbnd, 6 * NB, (size_t)(f == "lbu" ? 0 : 1) * NB + stage, v, 1, b0, nb, stride);
     }
     if (f == "lh" || f == "uh") {
         if (stage == 0) return fail("constraints_set lh/uh: no nonlinear constraint at stage 0 (nh_0 = 0)");
         if (len != 1) return fail("constraints_set lh/uh: expected 1 value");
-        return put(c, c->dbnd, 6 * NB, (size_t)(f == "lh" ? 4 : 5) * NB + stage, v, 1, b0, nb, stride);
+        return put(c, CH_BOUNDS, c->dbnd, 6 * NB, (size_t)(f == "lh" ? 4 : 5) * NB + stage, v, 1, b0, nb, stride);
     }
     return fail("constraints_set: unknown field '" + f + "'");
 }
@@ -808,7 +845,6 @@ extern "C" int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const 
     const std::string f(field);
     if ((stage < 0 || stage > N) && !(stage == TUM_ALL_STAGES && f == "W")) return fail("cost_set: stage out of range");
     if (f == "W") {
-        prep_stale(c);
         // per stage, like acados (NMPC_class.py:294-296 sets every stage in a loop); stage == TUM_ALL_STAGES: one 6 x 6 W for all
         // the stages 0..N-1 in one call
         const bool all = stage == TUM_ALL_STAGES;
@@ -838,7 +874,7 @@ extern "C" int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const 
             const size_t n = (size_t)c->batch * (N + 1);
             hipLaunchKernelGGL(wf_from_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->dW, c->dWf, (long long)n);
             HIPCHK(hipGetLastError());
-            c->ka.Wf = c->dWf; c->epoch++;
+            c->ka.Wf = c->dWf; invalidate(c, CH_CAPTURED);
         }
         if (c->dWf) {
             std::vector<double> full((size_t)cnt * rep * 36, 0.0);
@@ -848,9 +884,9 @@ extern "C" int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const 
                     for (int r = 0; r < ny; r++)
                         for (int q = 0; q < ny; q++) full[((size_t)i * rep + k) * 36 + r * 6 + q] = 0.5 * (Wm[q * ny + r] + Wm[r * ny + q]);
             }
-            if (put(c, c->dWf, (size_t)(N + 1) * 36, all ? 0 : (size_t)stage * 36, full.data(), rep * 36, b0, nb, stride == 0 ? 0 : rep * 36)) return 1;
+            if (put(c, CH_W, c->dWf, (size_t)(N + 1) * 36, all ? 0 : (size_t)stage * 36, full.data(), rep * 36, b0, nb, stride == 0 ? 0 : rep * 36)) return 1;
         }
-        return put(c, c->dW, (size_t)(N + 1) * 6, all ? 0 : (size_t)stage * 6, diag.data(), rep * ny, b0, nb, stride == 0 ? 0 : rep * ny);
+        return put(c, CH_W, c->dW, (size_t)(N + 1) * 6, all ? 0 : (size_t)stage * 6, diag.data(), rep * ny, b0, nb, stride == 0 ? 0 : rep * ny);
     }
     int which = -1;
     if (f == "zl") which = 0; else if (f == "zu") which = 1; else if (f == "Zl") which = 2; else if (f == "Zu") which = 3;
@@ -866,7 +902,7 @@ extern "C" int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const 
         const int cnt = stride == 0 ? 1 : nb;
         std::vector<double> col(cnt);
         for (int i = 0; i < cnt; i++) col[i] = v[(size_t)i * stride + j];
-        if (put(c, c->dpen, 36, (size_t)(cls * 3 + slot) * 4 + which, col.data(), 1, b0, nb, stride == 0 ? 0 : 1)) return 1;
+        if (put(c, CH_BOUNDS, c->dpen, 36, (size_t)(cls * 3 + slot) * 4 + which, col.data(), 1, b0, nb, stride == 0 ? 0 : 1)) return 1;
     }
     return 0;
 }
@@ -875,25 +911,38 @@ extern "C" int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const 
 // (TUM_FORCE_TILES: development aid -- a larger instantiation at a horizon a smaller one covers: the padding variables must not change the answer.)
 static int tiles_of(const tum_ocp *c)
 {
-    static const int force = [] { const char *e = getenv("TUM_FORCE_TILES"); return e ? atoi(e) : 0; }();
+    static const int force = env_int("TUM_FORCE_TILES", 0);
     const int need = c->N > 48 ? 7 : (c->N > NMAX ? 6 : 5);
     return (force > need && force <= 7 && !c->sn) ? force : need;
+}
+// the one dispatch on it: f(std::integral_constant<int, NT>) with the capsule's tile count; sizes and offsets are PD<NT>'s
+template <typename F>
+static auto with_tiles(const tum_ocp *c, F &&f)
+{
+    const int nt = tiles_of(c);
+    if (nt == 7) return f(std::integral_constant<int, 7>());
+    if (nt == 6) return f(std::integral_constant<int, 6>());
+    return f(std::integral_constant<int, 5>());
+}
+// what the kernels of the pipeline are given
+static PArgs pargs(const tum_ocp *c)
+{
+    PArgs pa;
+    pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
+    return pa;
 }
 // workspaces of the kernel variants, allocated when a variant is first used
 static int ensure_workspace(tum_ocp *c)
 {
-    const size_t B = c->batch;
-    const int nt = tiles_of(c);          // horizons beyond 40: six MFMA tiles (PD<6>), beyond 48: seven (PD<7>)
-    const size_t ntt = nt == 7 ? PD<7>::NTT : nt == 6 ? PD<6>::NTT : PD<5>::NTT, nch = nt == 7 ? PD<7>::NCH : nt == 6 ? PD<6>::NCH : PD<5>::NCH,
-                 pvec = nt == 7 ? PD<7>::PVEC : nt == 6 ? PD<6>::PVEC : PD<5>::PVEC;
-    if (c->pipe && !c->dhws) {
-        if (dalloc(&c->dhws, B * ntt * 256) != hipSuccess) return fail("workspace allocation failed (H tiles)");
-    }
-    if (c->pipe && !c->drec) {
-        if (dalloc(&c->drec, B * (size_t)(c->N + 1) * PREC) != hipSuccess || dalloc(&c->dcws, B * nch * 64) != hipSuccess ||
-            dalloc(&c->dvec, B * pvec) != hipSuccess) return fail("workspace allocation failed (pipeline)");
-    }
-    return 0;
+    if (!c->pipe) return 0;
+    return with_tiles(c, [&](auto ntc) {          // horizons beyond 40: six MFMA tiles (PD<6>), beyond 48: seven (PD<7>)
+        using D = PD<decltype(ntc)::value>;
+        const size_t B = c->batch;
+        if (!c->dhws && dalloc(&c->dhws, B * D::NTT * 256) != hipSuccess) return fail("workspace allocation failed (H tiles)");
+        if (!c->drec && (dalloc(&c->drec, B * (size_t)(c->N + 1) * PREC) != hipSuccess || dalloc(&c->dcws, B * D::NCH * 64) != hipSuccess ||
+                         dalloc(&c->dvec, B * D::PVEC) != hipSuccess)) return fail("workspace allocation failed (pipeline)");
+        return 0;
+    });
 }
 
 // "fused": one kernel per solve; "pipeline": linearise / condense / interior point / expand as four kernels, each at its own
@@ -934,8 +983,7 @@ extern "C" int tum_ocp_set_kernel(tum_ocp *c, const char *name)
         return fail("set_kernel: kernel '" + n + "' exists in the development build only (libtumnmpc_dev.so); this library is the pipeline");
 #endif
     else return fail("set_kernel: unknown kernel '" + n + "' (auto | pipeline | lin-lane-per-stage | lin-eight-lanes | cond-one-wavefront | cond-six-wavefronts | loop-fork | loop-serial | prologue-mfma | prologue-passes; development build: fused | pipeline4)");
-    c->epoch++;
-    prep_stale(c);
+    invalidate(c, CH_VARIANT | CH_CAPTURED);
     return 0;
 }
 
@@ -989,13 +1037,13 @@ static void sn_launch_prologue(tum_ocp *c)
 // do the wide kernels of the latency path run for this capsule (host's choice by batch size, tum_ocp_set_kernel, environment)
 static bool use_lin_cols(const tum_ocp *c)
 {
-    static const int cols_env = [] { const char *e = getenv("TUM_LIN_COLS"); return e ? atoi(e) : -1; }();
+    static const int cols_env = env_int("TUM_LIN_COLS", -1);
     const int want = (c->lin_cols >= 0) ? c->lin_cols : cols_env;
     return want > 0 || (want < 0 && (long long)c->batch * (c->N + 1) * LC_LANES <= 64LL * 1024);
 }
 static bool use_cond_wide(const tum_ocp *c)
 {
-    static const int wide_env = [] { const char *e = getenv("TUM_COND_WIDE"); return e ? atoi(e) : -1; }();
+    static const int wide_env = env_int("TUM_COND_WIDE", -1);
     const int want = (c->cond_wide >= 0) ? c->cond_wide : wide_env;
     if (tiles_of(c) == 7) return false;          // (seven tiles: the six-wavefront kernel's row store does not fit a CU's LDS beside a full W; one wavefront per OCP at every batch size)
     return want > 0 || (want < 0 && c->batch <= 256) || c->dWf != nullptr;          // (a full W exists as an instantiation of this kernel only)
@@ -1005,7 +1053,7 @@ static bool use_cond_wide(const tum_ocp *c)
 // while it loads the records (flags & 8). Nominal OCP on the latency path only (lin_cols_kernel + cond_wide_kernel).
 static bool lin_ahead_ok(const tum_ocp *c)
 {
-    static const int fork_env = [] { const char *e = getenv("TUM_SIM_FORK"); return e ? atoi(e) : -1; }();
+    static const int fork_env = env_int("TUM_SIM_FORK", -1);
     const int want = (c->sim_fork >= 0) ? c->sim_fork : fork_env;
     // (off unless asked for: measured SLOWER -- 0.169 against 0.160 ms per control step at 26 vehicles, 0.158-0.162 against 0.156 at one:
     //  the two cross-stream dependencies of a step cost more than the 15 us of planner the linearisation hides behind; HISTORY.md (round-4 document, section 7))
@@ -1013,8 +1061,7 @@ static bool lin_ahead_ok(const tum_ocp *c)
 }
 static void launch_lin_ahead(tum_ocp *c, hipStream_t st)
 {
-    PArgs pa;
-    pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
+    PArgs pa = pargs(c);
     pa.ka.flags |= 8;
     const long long items = (long long)c->batch * (c->N + 1);
     hipLaunchKernelGGL(lin_cols_kernel<false>, dim3((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), dim3(64), 0, st, pa);
@@ -1027,10 +1074,10 @@ static bool use_lin_uniform(const tum_ocp *c) { return c->iter_uniform && c->lin
 
 // part: 1 the linearisation and the condensing, 2 the interior point method and the expansion, 3 both (an SQP-RTI solve;
 // a full SQP solve puts its residual pass between the two, launch_sqp)
-static int launch_pipeline(tum_ocp *c, bool events, int part)
+// ipm_events: the events around the interior point kernel (get_stats "time_ipm") are recorded
+static int launch_pipeline(tum_ocp *c, bool ipm_events, int part)
 {
-    PArgs pa;
-    pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
+    PArgs pa = pargs(c);
     const bool prof = (c->ka.flags & 4) != 0;
     const long long items = (long long)c->batch * (c->N + 1);
     // linearisation: eight lanes per item while that still is one round of wavefronts on the chip (256 CUs x 4 SIMDs), see lin_cols_kernel
@@ -1057,37 +1104,36 @@ static int launch_pipeline(tum_ocp *c, bool events, int part)
         else hipLaunchKernelGGL(lin_kernel<false>, g_lane, dim3(64), 0, c->stream, pa);
     }
     }
-    if (part & 2) iterate_changed(c);          // (the expansion writes the new iterate)
     // (development aid: a larger LDS request lowers the number of OCPs that share a CU)
     // The expansion as the tail of the interior point kernel pays where a batch is at most one round of resident wavefronts (one
     // launch less: 0.424 against 0.432 ms per solve() call at 26 instances, 0.457 against 0.469 at 1024); beyond that its
     // loads run at the interior point kernel's occupancy -- one wavefront per SIMD, four OCPs per CU -- and hold that slot:
     // 3.72 against 3.96 M solves/s on config 2 (three streams). TUM_FUSED_EXPAND=0 / 1 forces it off / on (development aid).
-    static const int fuse_env = [] { const char *e = getenv("TUM_FUSED_EXPAND"); return e ? atoi(e) : -1; }();
+    static const int fuse_env = env_int("TUM_FUSED_EXPAND", -1);
     const bool no_fuse = fuse_env == 0 || (fuse_env < 0 && c->batch > 1024);
-    static const int lds_req = [] { const char *e = getenv("TUM_IPM_LDS"); const int v = e ? atoi(e) : 0; return (v > 0 && v <= 64 * 1024) ? v : 0; }();
-    auto rest = [&](auto ntc) {
+    static const int lds_req = [] { const int v = env_int("TUM_IPM_LDS", 0); return (v > 0 && v <= 64 * 1024) ? v : 0; }();
+    with_tiles(c, [&](auto ntc) {
         constexpr int NTv = decltype(ntc)::value;
         const int ipm_lds = lds_req > PD<NTv>::I_LDS_BYTES ? lds_req : PD<NTv>::I_LDS_BYTES;
         if (part & 1) {
-            // six wavefronts per OCP while every OCP can have a CU's LDS to itself (cond_wide_kernel)
-            const bool wide = use_cond_wide(c);
-            if constexpr (NTv == 7) {      // N = 49..56: a diagonal W, one wavefront per OCP at every batch size
+            bool wide = false;
+            if constexpr (NTv != 7) {      // (N = 49..56: a diagonal W, one wavefront per OCP at every batch size)
+                // six wavefronts per OCP while every OCP can have a CU's LDS to itself (cond_wide_kernel)
+                wide = use_cond_wide(c);
+                const dim3 blk(64 * cw_waves<NTv>());
+                if (wide && c->sn) hipLaunchKernelGGL((cond_wide_kernel<NTv, true>), dim3(c->batch), blk, 0, c->stream, pa);
+                else if (wide && c->dWf) hipLaunchKernelGGL((cond_wide_kernel<NTv, false, true>), dim3(c->batch), blk, 0, c->stream, pa);
+                else if (wide) hipLaunchKernelGGL((cond_wide_kernel<NTv, false>), dim3(c->batch), blk, 0, c->stream, pa);
+            }
+            if (!wide) {
+                // (coupled SNMPC: the register form of the stage record pays behind stage uph and costs in front of it, pipe_kernels.hpp)
                 if (c->sn && 2 * c->sa.uph <= c->N) hipLaunchKernelGGL((cond_kernel<NTv, true, true>), dim3(c->batch), dim3(64), 0, c->stream, pa);
                 else if (c->sn) hipLaunchKernelGGL((cond_kernel<NTv, true, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
                 else hipLaunchKernelGGL((cond_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-            } else {
-            if (wide && c->sn) hipLaunchKernelGGL((cond_wide_kernel<NTv, true>), dim3(c->batch), dim3(64 * cw_waves<NTv>()), 0, c->stream, pa);
-            else if (wide && c->dWf) hipLaunchKernelGGL((cond_wide_kernel<NTv, false, true>), dim3(c->batch), dim3(64 * cw_waves<NTv>()), 0, c->stream, pa);
-            else if (wide) hipLaunchKernelGGL((cond_wide_kernel<NTv, false>), dim3(c->batch), dim3(64 * cw_waves<NTv>()), 0, c->stream, pa);
-            // (coupled SNMPC: the register form of the stage record pays behind stage uph and costs in front of it, pipe_kernels.hpp)
-            else if (c->sn && 2 * c->sa.uph <= c->N) hipLaunchKernelGGL((cond_kernel<NTv, true, true>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-            else if (c->sn) hipLaunchKernelGGL((cond_kernel<NTv, true, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-            else hipLaunchKernelGGL((cond_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
             }
         }
         if (!(part & 2)) return;
-        if ((events && !c->skip_ipm_events) || c->time_ipm) (void)hipEventRecord(c->evi0, c->stream);
+        if (ipm_events) (void)hipEventRecord(c->evi0, c->stream);
         bool expanded = false;
 #ifdef TUM_DEV_KERNELS
         if (prof && c->kmode == 3 && NTv == 5) hipLaunchKernelGGL((ipm4_kernel<true>), dim3(c->batch), dim3(256), I4::BYTES, c->stream, pa);
@@ -1106,7 +1152,7 @@ static int launch_pipeline(tum_ocp *c, bool events, int part)
             if (c->sn || no_fuse) hipLaunchKernelGGL((ipm_kernel<false, NTv>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa);
             else { hipLaunchKernelGGL((ipm_kernel<false, NTv, true>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa); expanded = true; }
         }
-        if ((events && !c->skip_ipm_events) || c->time_ipm) (void)hipEventRecord(c->evi1, c->stream);
+        if (ipm_events) (void)hipEventRecord(c->evi1, c->stream);
         if (c->sn) {
             // the epilogue steps the sample copies AND the nominal copy of the stages 1..uph (their PCE mean); the expansion
             // kernel behind it takes the nominal recursion from stage uph to the end of the horizon and evaluates the cost
@@ -1118,8 +1164,7 @@ static int launch_pipeline(tum_ocp *c, bool events, int part)
             c->xs_lazy = true;
             hipLaunchKernelGGL((expand_kernel<NTv, true>), dim3(c->batch), dim3(64), 0, c->stream, pa);
         } else if (!expanded) hipLaunchKernelGGL((expand_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-    };
-    { const int nt = tiles_of(c); if (nt == 7) rest(std::integral_constant<int, 7>()); else if (nt == 6) rest(std::integral_constant<int, 6>()); else rest(std::integral_constant<int, 5>()); }
+    });
     return 0;
 }
 
@@ -1149,13 +1194,41 @@ static int rti_gate(tum_ocp *c)
 }
 static void launch_rti_feedback(tum_ocp *c)
 {
-    PArgs pa;
-    pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
-    const int nt = tiles_of(c);
-    if (nt == 7) hipLaunchKernelGGL(rti_feedback_kernel<7>, dim3(c->batch), dim3(64), 0, c->stream, pa, c->dx0prep);
-    else if (nt == 6) hipLaunchKernelGGL(rti_feedback_kernel<6>, dim3(c->batch), dim3(64), 0, c->stream, pa, c->dx0prep);
-    else hipLaunchKernelGGL(rti_feedback_kernel<5>, dim3(c->batch), dim3(64), 0, c->stream, pa, c->dx0prep);
+    with_tiles(c, [&](auto ntc) { hipLaunchKernelGGL(rti_feedback_kernel<decltype(ntc)::value>, dim3(c->batch), dim3(64), 0, c->stream, pargs(c), c->dx0prep); });
 }
+// ---- what every solve has in common, whichever way its kernels get onto the stream
+enum SolveKind { SOLVE_RTI, SOLVE_SQP, SOLVE_REPLAY };          // launch(), launch_sqp(), a solve inside a replayed chunk of tum_sim_run
+// the opening: the results of the last solve are on their way out, pending setters go up, the clock starts
+static int solve_begin(tum_ocp *c, bool events)
+{
+    invalidate(c, CH_RESULTS);
+    if (flush_inputs(c)) return 1;          // setters still in the pinned shadow (small capsules)
+    if (events) HIPCHK(hipEventRecord(c->ev0, c->stream));
+    // longest-first schedule from the previous solve's iteration counts (only matters when the batch is more than one
+    // round of resident wavefronts)
+    c->ka.order = (c->lpt && c->order_valid && c->batch > 1024) ? c->dorder : nullptr;
+    return 0;
+}
+// a solve of this kind has been enqueued. A replayed one was enqueued by the graph: its kernels (the schedule's among them) are in
+// the chunk, nothing is launched here, and nothing was timed -- what the last timed solve left behind stays
+static int solve_done(tum_ocp *c, SolveKind kind, bool ipm_timed)
+{
+    if (c->lpt && c->batch > 1024) {
+        if (kind != SOLVE_REPLAY) {
+            hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->dqpiter, c->dorder, c->batch);
+            HIPCHK(hipGetLastError());
+        }
+        c->order_valid = true;
+    }
+    c->solved = true; c->solved_pipe = c->pipe; c->solved_sqp = kind == SOLVE_SQP; c->cold = false;
+    invalidate(c, CH_ITERATE);          // (whichever kernel variant ran: the solve wrote the new iterate)
+    c->prep = 0; c->prep_timed = false;          // (a feedback consumes its preparation; a one-call solve discards a pending one)
+    if (kind == SOLVE_REPLAY) { if (c->sn) c->xs_lazy = true; return 0; }          // (the epilogue kernel of the chunk, as launch_pipeline records it)
+    c->ipm_timed = ipm_timed;
+    c->ts_slot = -1;          // (tum_ocp_step_async sets it behind this call)
+    return 0;
+}
+
 // PREPARATION (rti_phase 1): pending inputs up, part 1 of the pipeline as a one-call solve of this capsule would run it, and the x0 it
 // condensed at. Iterate, results, multipliers, slacks and the getters' cache stay as they are.
 static int launch_prepare(tum_ocp *c)
@@ -1182,12 +1255,8 @@ static int launch(tum_ocp *c, bool events = true)
     if (rti_gate(c)) return 1;
     const bool feedback = c->rti_phase == 2;
     if (resolve_kernel(c)) return 1;
-    c->cache_valid = false; c->xs_cached = false;
-    if (flush_inputs(c)) return 1;          // setters still in the pinned shadow (small capsules)
-    if (events) HIPCHK(hipEventRecord(c->ev0, c->stream));
-    // longest-first schedule from the previous solve's iteration counts (only matters when the batch is more than one
-    // round of resident wavefronts)
-    c->ka.order = (c->lpt && c->order_valid && c->batch > 1024) ? c->dorder : nullptr;
+    if (solve_begin(c, events)) return 1;
+    const bool ipm_events = (events && !c->skip_ipm_events) || c->time_ipm;
     // the instrumented instantiation carries the phase timers (flag 4) and the debug dump (flag 2)
     if (c->sn && sn_apply_p(c)) return 1;
 #ifdef TUM_DEV_KERNELS
@@ -1197,23 +1266,22 @@ static int launch(tum_ocp *c, bool events = true)
         return fail("solve: kernel 'fused' takes at most 16 samples / PCE terms (use 'auto' or 'pipeline')");
     if (c->sn && !c->pipe && c->sa.uph > SN_UPHMAX_FUSED)
         return fail("solve: kernel 'fused' reads the sample columns of one wavefront: uncertainty propagation horizon <= 31 (use 'auto' or 'pipeline')");
-    if (c->pipe) {
-        if (feedback) launch_rti_feedback(c);
-        if (launch_pipeline(c, events, feedback ? 2 : 3)) return 1;
-    }
-    else if (c->sn) {
-        if (c->fanout && sn_fanout(c)) return 1;
-        sn_launch_lin(c);
-        sn_launch_prologue(c);
-        if (prof) fused(nmpc_rti_kernel<true, true>); else fused(nmpc_rti_kernel<false, true>);
-        hipLaunchKernelGGL((snmpc_epilogue_kernel<>), dim3(c->batch), dim3(64), 0, c->stream, c->sa); c->xs_lazy = true;
-    }
-    else { if (prof) fused(nmpc_rti_kernel<true>); else fused(nmpc_rti_kernel<false>); }
-    if (!c->pipe) HIPCHK(hipMemsetAsync(c->dqplam, 0, sizeof(double) * (size_t)c->batch * (6 * (size_t)c->N + 2), c->stream));      // (the fused kernel leaves no multipliers behind)
-#else
-    if (feedback) launch_rti_feedback(c);
-    if (launch_pipeline(c, events, feedback ? 2 : 3)) return 1;
+    if (!c->pipe) {
+        if (c->sn) {
+            if (c->fanout && sn_fanout(c)) return 1;
+            sn_launch_lin(c);
+            sn_launch_prologue(c);
+            if (prof) fused(nmpc_rti_kernel<true, true>); else fused(nmpc_rti_kernel<false, true>);
+            hipLaunchKernelGGL((snmpc_epilogue_kernel<>), dim3(c->batch), dim3(64), 0, c->stream, c->sa); c->xs_lazy = true;
+        }
+        else { if (prof) fused(nmpc_rti_kernel<true>); else fused(nmpc_rti_kernel<false>); }
+        HIPCHK(hipMemsetAsync(c->dqplam, 0, sizeof(double) * (size_t)c->batch * (6 * (size_t)c->N + 2), c->stream));      // (the fused kernel leaves no multipliers behind)
+    } else
 #endif
+    {
+        if (feedback) launch_rti_feedback(c);
+        if (launch_pipeline(c, ipm_events, feedback ? 2 : 3)) return 1;
+    }
     HIPCHK(hipGetLastError());
     if (c->r2) {   // constraint tightening for the NEXT solve from this one's linearisation (skipped per instance on failure)
         hipLaunchKernelGGL(r2_backoff_kernel, dim3((c->batch + 3) / 4), dim3(256), 0, c->stream, c->dqpin, c->dX, c->dbnd, c->ka.mp,
@@ -1222,19 +1290,7 @@ static int launch(tum_ocp *c, bool events = true)
         HIPCHK(hipGetLastError());
     }
     if (events) HIPCHK(hipEventRecord(c->ev1, c->stream));
-    if (c->lpt && c->batch > 1024) {
-        hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->dqpiter, c->dorder, c->batch);
-        HIPCHK(hipGetLastError());
-        c->order_valid = true;
-    }
-    c->solved = true;
-    c->solved_pipe = c->pipe;
-    c->solved_sqp = false; c->cold = false;
-    iterate_changed(c);          // (whichever kernel variant ran: the solve wrote the new iterate)
-    c->ipm_timed = (events && !c->skip_ipm_events) || c->time_ipm;
-    c->ts_slot = -1;          // (tum_ocp_step_async sets it behind this call)
-    c->prep = 0; c->prep_timed = false;          // (a feedback consumes its preparation; a one-call solve discards a pending one)
-    return 0;
+    return solve_done(c, SOLVE_RTI, ipm_events);
 }
 
 // ---- full SQP solves (nlp_solver_type SQP)
@@ -1317,10 +1373,7 @@ static int launch_sqp(tum_ocp *c)
         HIPCHK(hipHostMalloc((void **)&c->hactive, 2 * sizeof(unsigned), hipHostMallocDefault));
         c->active_cap = c->nlp_max_iter + 1;
     }
-    c->cache_valid = false; c->xs_cached = false;
-    if (flush_inputs(c)) return 1;
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    c->ka.order = (c->lpt && c->order_valid && c->batch > 1024) ? c->dorder : nullptr;
+    if (solve_begin(c, true)) return 1;
     HIPCHK(hipMemsetAsync(c->dsqpstate, 0, sizeof(int) * B, c->stream));
     HIPCHK(hipMemsetAsync(c->dsqpiter, 0, sizeof(int) * B, c->stream));
     HIPCHK(hipMemsetAsync(c->dactive, 0, sizeof(unsigned) * (size_t)(c->nlp_max_iter + 1), c->stream));
@@ -1339,16 +1392,12 @@ static int launch_sqp(tum_ocp *c)
     sq.snap = c->dsnap; sq.snapi = c->dsnapi; sq.snap_len = snap_len;
     sq.tol_stat = c->nlp_tol[0]; sq.tol_eq = c->nlp_tol[1]; sq.tol_ineq = c->nlp_tol[2]; sq.tol_comp = c->nlp_tol[3];
     sq.alpha = c->nlp_alpha;
-    PArgs pa;
-    pa.ka = c->ka; pa.rec = c->drec; pa.hws = c->dhws; pa.cws = c->dcws; pa.vec = c->dvec;
-    const int nt = tiles_of(c);
+    const PArgs pa = pargs(c);
     auto residuals = [&](int pass) {
         sq.pass = pass; sq.last = (pass == c->nlp_max_iter) ? 1 : 0;
         sq.cost = (c->nlp_alpha != 1.0 || (pass == 0 && cold)) ? 1 : 0;
         if (launch_pipeline(c, false, 1)) return 1;
-        if (nt == 7) hipLaunchKernelGGL(nlp_residual_kernel<7>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
-        else if (nt == 6) hipLaunchKernelGGL(nlp_residual_kernel<6>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
-        else hipLaunchKernelGGL(nlp_residual_kernel<5>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq);
+        with_tiles(c, [&](auto ntc) { hipLaunchKernelGGL(nlp_residual_kernel<decltype(ntc)::value>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq); });
         HIPCHK(hipGetLastError());
         return 0;
     };
@@ -1364,7 +1413,8 @@ static int launch_sqp(tum_ocp *c)
     // instances only -- the commit kernel has put every one of them back -- and the solve ends behind it.
     for (int it = 0; it < c->nlp_max_iter; it++) {
         hipLaunchKernelGGL(sqp_snapshot_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq);
-        if (launch_pipeline(c, false, 2)) return 1;
+        if (launch_pipeline(c, c->time_ipm, 2)) return 1;
+        invalidate(c, CH_ITERATE);          // (the expansion wrote a new iterate: the residual pass below linearises the general way)
         hipLaunchKernelGGL(sqp_commit_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq);
         HIPCHK(hipGetLastError());
         if (residuals(it + 1) || count_copy(it + 1)) return 1;
@@ -1372,24 +1422,14 @@ static int launch_sqp(tum_ocp *c)
         if (c->hactive[it & 1] == 0) break;
     }
     HIPCHK(hipEventRecord(c->ev1, c->stream));
-    if (c->lpt && c->batch > 1024) {
-        hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->dqpiter, c->dorder, c->batch);
-        HIPCHK(hipGetLastError());
-        c->order_valid = true;
-    }
-    c->solved = true; c->solved_pipe = true; c->solved_sqp = true; c->cold = false;
-    iterate_changed(c);
-    c->prep = 0; c->prep_timed = false;
-    c->ipm_timed = c->time_ipm;
-    c->ts_slot = -1;
-    return 0;
+    return solve_done(c, SOLVE_SQP, c->time_ipm);
 }
 
 // 1: dispatch instances longest-first using the previous solve's iteration counts (default), 0: natural order
 extern "C" int tum_ocp_set_schedule(tum_ocp *c, int longest_first)
 {
     if (!c) return fail("null capsule");
-    if (c->lpt != (longest_first != 0)) c->epoch++;
+    if (c->lpt != (longest_first != 0)) invalidate(c, CH_CAPTURED);
     c->lpt = longest_first != 0;
     return 0;
 }
@@ -1409,30 +1449,27 @@ extern "C" int tum_ocp_synchronize(tum_ocp *c)
     return lin_uniform_check(c);
 }
 
+// the end of a synchronous solve: wait, the safety net, the largest status of the batch (-1: the call failed). A preparation has no
+// results: 0 (acados >= 0.3 returns ACADOS_READY here; the reference's callers take any non-zero status for a failure)
+static int wait_status(tum_ocp *c, bool results = true)
+{
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
+    if (lin_uniform_check(c)) return -1;
+    if (!results) return 0;
+    std::vector<int> st(c->batch);
+    if (hipMemcpy(st.data(), c->dstatus, sizeof(int) * c->batch, hipMemcpyDeviceToHost) != hipSuccess) { fail("status copy failed"); return -1; }
+    int mx = 0;
+    for (int s : st) if (s > mx) mx = s;
+    return mx;
+}
+
 extern "C" int tum_ocp_solve(tum_ocp *c)
 {
     if (!c) { fail("null capsule"); return -1; }
     DevGuard guard(c->d.device); if (!guard.ok) { fail("hipSetDevice failed"); return -1; }
-    if (c->nlp_type) {
-        if (launch_sqp(c)) return -1;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
-        if (lin_uniform_check(c)) return -1;
-        std::vector<int> st(c->batch);
-        if (hipMemcpy(st.data(), c->dstatus, sizeof(int) * c->batch, hipMemcpyDeviceToHost) != hipSuccess) { fail("status copy failed"); return -1; }
-        int mx = 0;
-        for (int s : st) if (s > mx) mx = s;
-        return mx;
-    }
-    if (c->rti_phase) {
-        if (rti_gate(c)) return -1;          // (before anything is uploaded or invalidated)
-        if (c->rti_phase == 1) {
-            // a preparation has no results: 0 (acados >= 0.3 returns ACADOS_READY here; the reference's callers take any non-zero status for a failure)
-            if (launch_prepare(c)) return -1;
-            if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
-            if (lin_uniform_check(c)) return -1;
-            return 0;
-        }
-    }
+    if (c->nlp_type) return launch_sqp(c) ? -1 : wait_status(c);
+    if (rti_gate(c)) return -1;          // (before anything is uploaded or invalidated)
+    if (c->rti_phase == 1) return launch_prepare(c) ? -1 : wait_status(c, false);
     if (small_inputs(c) && results_pack_all(c, 1)) {
         // small capsule: [pending setters up + device clock] -> solve -> [summary, X, U into pinned slabs + device clock], ONE wait. No
         // event and no copy command on the stream; the getters that follow read the slabs (cache_valid).
@@ -1452,19 +1489,12 @@ extern "C" int tum_ocp_solve(tum_ocp *c)
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
         if (lin_uniform_check(c)) return -1;
         c->in_inflight = false;
-        c->ts_slot = 2; c->cache_valid = true; c->xs_cached = false;
+        c->ts_slot = 2; c->cache_valid = true;          // (xs_cached went with the cache at the start of the solve)
         int mx = 0;
         for (size_t b = 0; b < B; b++) { const int st = (int)c->hsum_s[b * 5 + 3]; if (st > mx) mx = st; }
         return mx;
     }
-    if (launch(c)) return -1;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { fail("kernel execution failed"); return -1; }
-    if (lin_uniform_check(c)) return -1;
-    std::vector<int> st(c->batch);
-    if (hipMemcpy(st.data(), c->dstatus, sizeof(int) * c->batch, hipMemcpyDeviceToHost) != hipSuccess) { fail("status copy failed"); return -1; }
-    int mx = 0;
-    for (int s : st) if (s > mx) mx = s;
-    return mx;
+    return launch(c) ? -1 : wait_status(c);
 }
 
 extern "C" double tum_ocp_last_kernel_ms(tum_ocp *c)
@@ -1540,13 +1570,12 @@ extern "C" int tum_ocp_reset(tum_ocp *c)
 {
     if (!c) return fail("null capsule");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false; prep_stale(c);
+    invalidate(c, CH_ITERATE);
     HIPCHK(hipMemsetAsync(c->dqplam, 0, sizeof(double) * (size_t)c->batch * (6 * (size_t)c->N + 2), c->stream));
     HIPCHK(hipMemsetAsync(c->dX, 0, sizeof(double) * (size_t)c->batch * (c->N + 1) * NX, c->stream));
     HIPCHK(hipMemsetAsync(c->dU, 0, sizeof(double) * (size_t)c->batch * c->N * NU, c->stream));
     HIPCHK(hipMemsetAsync(c->dslack, 0, sizeof(double) * (size_t)c->batch * 6 * (size_t)c->N, c->stream));
-    c->cold = true; c->iter_uniform = true;          // (X = 0, U = 0 at every stage)
-    lin_uniform_rearm(c);
+    invalidate(c, CH_RESTART);          // (X = 0, U = 0 at every stage)
     if (c->sn) HIPCHK(hipMemsetAsync(c->dXS, 0, sizeof(double) * (size_t)c->batch * (c->N + 1) * c->sa.ns * NX, c->stream));
     if (c->sn) { HIPCHK(hipMemsetAsync(c->dxs_dirty, 0, sizeof(int) * (size_t)c->batch, c->stream)); c->xs_lazy = false; }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1557,15 +1586,14 @@ extern "C" int tum_ocp_cold_start(tum_ocp *c)
 {
     if (!c) return fail("null capsule");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false; c->cold = true; prep_stale(c);
+    invalidate(c, CH_ITERATE);
     if (flush_inputs(c)) return 1;          // (the x0 it copies may still be in the pinned shadow)
     hipLaunchKernelGGL(cold_start_kernel, dim3(c->batch), dim3(64), 0, c->stream, c->dX, c->dU, c->dx0, c->N, c->batch, c->dqplam);
     if (c->sn && c->fanout && sn_fanout(c)) return 1;
     if (c->sn) hipLaunchKernelGGL(snmpc_cold_start_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->dXS, c->dxs0, c->N, c->sa.ns, c->batch);
     if (c->sn) { HIPCHK(hipMemsetAsync(c->dxs_dirty, 0, sizeof(int) * (size_t)c->batch, c->stream)); c->xs_lazy = false; }
     HIPCHK(hipGetLastError());
-    c->iter_uniform = true;          // (X_k = x0, U_k = 0 at every stage)
-    lin_uniform_rearm(c);
+    invalidate(c, CH_RESTART);          // (X_k = x0, U_k = 0 at every stage)
     return 0;
 }
 
@@ -1643,10 +1671,12 @@ extern "C" int tum_ocp_get_device(tum_ocp *c, const char *field, void *dst, int 
     if (f == "qp_iter") { HIPCHK(hipMemcpyAsync(dst, c->dqpiter + b0, 4 * (size_t)nb, hipMemcpyDeviceToDevice, s)); return 0; }
     if (f == "qp_vec") {      // gradient q and row constants d of the condensed QP in the pipeline's workspace, read-only
         if (!c->dvec) return fail("get_device qp_vec: no pipeline solve or preparation yet");
-        const int nt = tiles_of(c);
-        const size_t nvp = nt == 7 ? PD<7>::NVP : nt == 6 ? PD<6>::NVP : PD<5>::NVP, pvec = nt == 7 ? PD<7>::PVEC : nt == 6 ? PD<6>::PVEC : PD<5>::PVEC;
-        HIPCHK(hipMemcpy2DAsync(dst, 2 * nvp * 8, c->dvec + (size_t)b0 * pvec, pvec * 8, 2 * nvp * 8, nb, hipMemcpyDeviceToDevice, s));
-        return 0;
+        return with_tiles(c, [&](auto ntc) {
+            using D = PD<decltype(ntc)::value>;
+            const size_t nvp = D::NVP, pvec = D::PVEC;
+            HIPCHK(hipMemcpy2DAsync(dst, 2 * nvp * 8, c->dvec + (size_t)b0 * pvec, pvec * 8, 2 * nvp * 8, nb, hipMemcpyDeviceToDevice, s));
+            return 0;
+        });
     }
     return fail("get_device: unknown field '" + f + "'");
 }
@@ -1764,7 +1794,6 @@ extern "C" int tum_ocp_step_async(tum_ocp *c, const double *x0, const double *yr
     const int rc = launch(c, !clocked);
     c->skip_ipm_events = false;
     if (rc) return 1;
-    c->ipm_timed = c->time_ipm;
     c->ts_slot = clocked ? w : -1;
     const int rr = results_enqueue(c, with_iterate, true);
     if (rr) c->ts_slot = -1;
@@ -1780,18 +1809,18 @@ extern "C" int tum_ocp_put_device(tum_ocp *c, const char *field, const void *src
     const std::string f(field);
     DevGuard guard(c->d.device); GUARD_OK(guard);
     hipStream_t s = c->stream;
-    c->cache_valid = false;
-    if (f != "x0") prep_stale(c);
+    const unsigned what = f == "x0" ? CH_X0 : f == "yref" ? CH_REF : (f == "X" || f == "U") ? CH_ITERATE : 0u;
+    if (!what) return fail("put_device: unknown field '" + f + "'");
+    invalidate(c, what | CH_UPLOAD);
     if (flush_inputs(c)) return 1;          // (setters older than this upload)
     if (f == "x0") {
         if (c->sn) { if (!c->have_offs) return fail("put_device x0: an SNMPC capsule needs its sample offsets (tum_ocp_snmpc_set_offsets)"); c->fanout = true; }
         HIPCHK(hipMemcpyAsync(c->dx0 + (size_t)b0 * NX, src, 8 * (size_t)nb * NX, hipMemcpyDeviceToDevice, s)); return 0;
     }
     if (f == "yref") { HIPCHK(hipMemcpyAsync(c->dyref + (size_t)b0 * (N + 1) * 6, src, 8 * (size_t)nb * (N + 1) * 6, hipMemcpyDeviceToDevice, s)); return 0; }
-    if (f == "X" || f == "U") iterate_changed(c);
     if (f == "X") { HIPCHK(hipMemcpyAsync(c->dX + (size_t)b0 * (N + 1) * NX, src, 8 * (size_t)nb * (N + 1) * NX, hipMemcpyDeviceToDevice, s)); return 0; }
-    if (f == "U") { HIPCHK(hipMemcpyAsync(c->dU + (size_t)b0 * N * NU, src, 8 * (size_t)nb * N * NU, hipMemcpyDeviceToDevice, s)); return 0; }
-    return fail("put_device: unknown field '" + f + "'");
+    HIPCHK(hipMemcpyAsync(c->dU + (size_t)b0 * N * NU, src, 8 * (size_t)nb * N * NU, hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 
 // Zero-copy inputs for callers whose batches are resident in HBM already (scenario fan-outs, sweeps: bench.py rotates resident batches):
@@ -1804,14 +1833,13 @@ extern "C" int tum_ocp_bind_device(tum_ocp *c, const char *field, void *dev_ptr)
     if (!c || !field) return fail("null argument");
     const std::string f(field);
     if (f != "x0" && f != "yref") return fail("bind_device: field must be 'x0' or 'yref'");
-    prep_stale(c);
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if (flush_inputs(c)) return 1;          // (setters parked in the pinned shadow belong to the array in use until now)
     if (f == "x0") {
         if (c->sn && dev_ptr) { if (!c->have_offs) return fail("bind_device x0: an SNMPC capsule needs its sample offsets (tum_ocp_snmpc_set_offsets)"); c->fanout = true; }
         c->dx0 = dev_ptr ? (double *)dev_ptr : c->dx0_own; c->ka.x0 = c->dx0;
     } else { c->dyref = dev_ptr ? (double *)dev_ptr : c->dyref_own; c->ka.yref = c->dyref; }
-    c->epoch++;          // (a captured closed-loop chunk holds the pointers by value)
+    invalidate(c, (f == "x0" ? CH_X0 : CH_REF) | CH_VARIANT | CH_CAPTURED);          // (a captured closed-loop chunk holds the pointers by value)
     return 0;
 }
 
@@ -1842,32 +1870,34 @@ extern "C" int tum_ocp_debug_dump(tum_ocp *c, int b, double *out, int len)
     if (c->N > NMAX) return fail("debug_dump: the condensed-QP dump is built for N <= 40");
     if (launch(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
-    using D = PD<5>;
-    const int N = c->N;
-    std::vector<double> hw((size_t)D::NTT * 256), cw((size_t)D::NCH * 64), vv(D::PVEC), o(DBG_STRIDE, 0.0);
-    HIPCHK(hipMemcpy(hw.data(), c->dhws + (size_t)b * D::NTT * 256, sizeof(double) * hw.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cw.data(), c->dcws + (size_t)b * D::NCH * 64, sizeof(double) * cw.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(vv.data(), c->dvec + (size_t)b * D::PVEC, sizeof(double) * vv.size(), hipMemcpyDeviceToHost));
-    for (int K = 0; K < D::NT; K++)
-        for (int I = K; I < D::NT; I++)
-            for (int l = 0; l < 64; l++)
-                for (int jj = 0; jj < 4; jj++) {         // accumulator layout: row (l >> 4) + 4 jj, column l & 15
-                    const int row = 16 * K + (l >> 4) + 4 * jj, col = 16 * I + (l & 15);
-                    const double v = hw[((size_t)D::tidx(K, I) * 64 + l) * 4 + jj];
-                    o[row * 80 + col] = v; o[col * 80 + row] = v;
-                }
-    for (int i = 0; i < 80; i++) o[6400 + i] = vv[D::PV_Q + i];
-    for (int s = 1; s <= N; s++)
-        for (int col = 0; col < 80; col++) {
-            o[6480 + (2 * (s - 1)) * 80 + col] = ((col & 1) && col < 2 * s) ? c->ka.dt : 0.0;
-            const int cc = (s - 1) >> 2, lq = (s - 1) & 3, T = col >> 4;       // operand layout: chunk cc, DPP row lq, tile column T
-            o[6480 + (2 * (s - 1) + 1) * 80 + col] = (cc >= 2 * T) ? cw[(size_t)D::cidx(cc, T) * 64 + 16 * lq + (col & 15)] : 0.0;
-        }
-    for (int i = 0; i < 2 * N; i++) o[12880 + i] = vv[D::PV_D + i];
-    // (development aid: the tail of the dump area carries the phase cycle counters of the SNMPC prologue kernels, SnArgs::dbg)
-    HIPCHK(hipMemcpy(o.data() + 20000, c->ddbg + (size_t)b * DBG_STRIDE + 20000, sizeof(double) * (DBG_STRIDE - 20000), hipMemcpyDeviceToHost));
-    memcpy(out, o.data(), sizeof(double) * len);
-    return 0;
+    return with_tiles(c, [&](auto ntc) {          // (the 80 variables of N <= 40, whichever instantiation TUM_FORCE_TILES made the solve run)
+        using D = PD<decltype(ntc)::value>;
+        const int N = c->N;
+        std::vector<double> hw((size_t)D::NTT * 256), cw((size_t)D::NCH * 64), vv(D::PVEC), o(DBG_STRIDE, 0.0);
+        HIPCHK(hipMemcpy(hw.data(), c->dhws + (size_t)b * D::NTT * 256, sizeof(double) * hw.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cw.data(), c->dcws + (size_t)b * D::NCH * 64, sizeof(double) * cw.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(vv.data(), c->dvec + (size_t)b * D::PVEC, sizeof(double) * vv.size(), hipMemcpyDeviceToHost));
+        for (int K = 0; K < 5; K++)
+            for (int I = K; I < 5; I++)
+                for (int l = 0; l < 64; l++)
+                    for (int jj = 0; jj < 4; jj++) {         // accumulator layout: row (l >> 4) + 4 jj, column l & 15
+                        const int row = 16 * K + (l >> 4) + 4 * jj, col = 16 * I + (l & 15);
+                        const double v = hw[((size_t)D::tidx(K, I) * 64 + l) * 4 + jj];
+                        o[row * 80 + col] = v; o[col * 80 + row] = v;
+                    }
+        for (int i = 0; i < 80; i++) o[6400 + i] = vv[D::PV_Q + i];
+        for (int s = 1; s <= N; s++)
+            for (int col = 0; col < 80; col++) {
+                o[6480 + (2 * (s - 1)) * 80 + col] = ((col & 1) && col < 2 * s) ? c->ka.dt : 0.0;
+                const int cc = (s - 1) >> 2, lq = (s - 1) & 3, T = col >> 4;       // operand layout: chunk cc, DPP row lq, tile column T
+                o[6480 + (2 * (s - 1) + 1) * 80 + col] = (cc >= 2 * T) ? cw[(size_t)D::cidx(cc, T) * 64 + 16 * lq + (col & 15)] : 0.0;
+            }
+        for (int i = 0; i < 2 * N; i++) o[12880 + i] = vv[D::PV_D + i];
+        // (development aid: the tail of the dump area carries the phase cycle counters of the SNMPC prologue kernels, SnArgs::dbg)
+        HIPCHK(hipMemcpy(o.data() + 20000, c->ddbg + (size_t)b * DBG_STRIDE + 20000, sizeof(double) * (DBG_STRIDE - 20000), hipMemcpyDeviceToHost));
+        memcpy(out, o.data(), sizeof(double) * len);
+        return 0;
+    });
 }
 
 // development aid: one solve with the in-kernel phase timers on; out = batch x 12 cycle counters
@@ -2018,7 +2048,7 @@ extern "C" int tum_ocp_r2_attach(tum_ocp *c, const double *Sigma0, const double 
                                  double delta_min, double delta_max, double uh_nom)
 {
     if (!c) return fail("null capsule");
-    if (uph == 0) { if (c->r2) c->epoch++; c->r2 = false; return 0; }
+    if (uph == 0) { if (c->r2) invalidate(c, CH_CAPTURED); c->r2 = false; return 0; }
     if (!Sigma0 || !BWB) return fail("null argument");
     if (!c->d.store_qp_in) return fail("r2_attach: capsule created without store_qp_in");
     if (c->sn) return fail("r2_attach: not available for an SNMPC capsule");
@@ -2029,7 +2059,7 @@ extern "C" int tum_ocp_r2_attach(tum_ocp *c, const double *Sigma0, const double 
     HIPCHK(hipMemcpy(c->dr2B, BWB, 64 * 8, hipMemcpyHostToDevice));
     c->r2_uph = uph; c->r2_dmin = delta_min; c->r2_dmax = delta_max; c->r2_uh = uh_nom;
     c->r2 = true;
-    c->epoch++;
+    invalidate(c, CH_CAPTURED);
     return 0;
 }
 
@@ -2139,7 +2169,7 @@ extern "C" int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *
     if (!s || !x_sim || !x_mpc) return fail("null argument");
     tum_ocp *c = s->c; const size_t B = c->batch;
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false; prep_stale(c);
+    invalidate(c, CH_X0 | CH_REF | CH_UPLOAD);
     if (flush_inputs(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(s->dxsim, x_sim, sizeof(double) * B * 7, hipMemcpyHostToDevice));
@@ -2163,6 +2193,7 @@ extern "C" int tum_sim_plan(tum_sim *s)
     tum_ocp *c = s->c;
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if (flush_inputs(c)) return 1;
+    invalidate(c, CH_REF);
     hipLaunchKernelGGL(planner_kernel, dim3(c->batch), dim3(64), 0, c->stream, s->dtrack, s->n_track, s->dpose, 2, c->N + 1, s->Tp,
                        s->loop_circuit, c->dyref, 6, s->dref0, s->dclosest, s->derr, c->batch, (int *)nullptr);
     HIPCHK(hipGetLastError());
@@ -2175,21 +2206,13 @@ extern "C" int tum_sim_advance(tum_sim *s)
     tum_ocp *c = s->c;
     if (!c->solved) return fail("sim_advance: no solve yet");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false;          // (the plant re-initialises the iterate of an instance whose solve failed, and writes the next x0)
-    iterate_changed(c);
+    invalidate(c, CH_ITERATE | CH_X0);          // (the plant re-initialises the iterate of an instance whose solve failed, and writes the next x0)
     if (flush_inputs(c)) return 1;
     SimArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.N = c->N; sa.batch = c->batch; sa.n_elem = s->n_elem; sa.step_counter = s->dstep; sa.log_cap = s->log_cap; sa.Ts = s->Ts;
     for (int i = 0; i < 8; i++) sa.win[i] = s->win[i];
-    const tum_ocp_desc &d = c->d;
-    PlantModel &p = sa.pm;
-    p.lf = d.lf; p.lr = d.lr; p.m = d.m; p.inv_m = 1.0 / d.m; p.inv_Iz = 1.0 / d.Iz; p.ka = 0.5 * d.ro * d.S * d.Cd;
-    p.Bf = d.Bf; p.Cf = d.Cf; p.Df = d.Df; p.Ef = d.Ef; p.Br = d.Br; p.Cr = d.Cr; p.Dr = d.Dr; p.Er = d.Er;
-    p.Fz_f = d.m * d.lr * d.g / (d.lf + d.lr); p.Fz_r = d.m * d.lf * d.g / (d.lf + d.lr);
-    p.invFmax_f = 1.0 / std::sqrt(p.Fz_f * p.Fz_f + (d.Cf * p.Fz_f) * (d.Cf * p.Fz_f));
-    p.invFmax_r = 1.0 / std::sqrt(p.Fz_r * p.Fz_r + (d.Cr * p.Fz_r) * (d.Cr * p.Fz_r));
-    p.fr0 = d.fr0; p.fr1 = d.fr1; p.fr4 = d.fr4;
+    vehicle_constants(sa.pm, c->d);
     sa.X = c->dX; sa.U = c->dU; sa.cost = c->dcost; sa.status = c->dstatus; sa.qp_iter = c->dqpiter;
     sa.ns = c->sn ? c->sa.ns : 0; sa.XS = c->dXS; sa.xs0 = c->dxs0;
     sa.bnd = c->dbnd; sa.r2 = c->r2 ? 1 : 0; sa.r2_dmin = c->r2_dmin; sa.r2_dmax = c->r2_dmax; sa.r2_uh = c->r2_uh;
@@ -2241,8 +2264,7 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
     if (c->nlp_type) return fail("sim_run: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
     if (c->rti_phase) return fail("sim_run: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->cache_valid = false;
-    iterate_changed(c);          // (the closed loop keeps the general linearisation: its chunks are captured and replayed)
+    invalidate(c, CH_ITERATE);          // (the closed loop keeps the general linearisation: its chunks are captured and replayed)
     if (flush_inputs(c)) return 1;            // (pending host setters go up before anything is captured)
     if (resolve_kernel(c)) return 1;          // (workspace allocation must not happen inside the capture below)
     // ... nor the reallocation / synchronisation a changed SNMPC parameter vector can trigger, nor the deferred freeze
@@ -2277,9 +2299,7 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
         while (s->graph && nsteps - done >= s->graph_steps) {
             HIPCHK(hipGraphLaunch(s->graph, c->stream));
             done += s->graph_steps; s->step += s->graph_steps;
-            // what launch() records on the host for every solve holds for the replayed solves as well
-            if (c->sn) c->xs_lazy = true;
-            c->solved = true; c->solved_pipe = c->pipe; c->cold = false; if (c->lpt && c->batch > 1024) c->order_valid = true;
+            if (solve_done(c, SOLVE_REPLAY, false)) return 1;
         }
     }
     for (; done < nsteps; done++)
