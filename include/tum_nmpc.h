@@ -136,7 +136,7 @@ int tum_ocp_solve(tum_ocp *c);
  * In SQP mode (tum_ocp_options_set) it returns behind the enqueue of the last iteration: the host reads the number of active
  * instances between two iterations. */
 int tum_ocp_solve_async(tum_ocp *c);
-/* acados_solver.options_set(field, value) for the NLP solver (acados_ocp_SNMPC.json: nlp_solver_*; globalization FIXED_STEP):
+/* acados_solver.options_set(field, value) for the NLP solver (acados_ocp_SNMPC.json: nlp_solver_*) and its globalization:
  * "nlp_solver_type"        0 SQP_RTI (default: one QP per solve, as before), 1 SQP (full solves)
  * "nlp_solver_max_iter"    1..10000 QPs per SQP solve (default 100)
  * "nlp_solver_tol_stat" | "nlp_solver_tol_eq" | "nlp_solver_tol_ineq" | "nlp_solver_tol_comp"   >= 0 (default 1e-6 each)
@@ -146,6 +146,28 @@ int tum_ocp_solve_async(tum_ocp *c);
  * Per-instance status: 0 converged, 2 max_iter reached (ACADOS_MAXITER), 4 a QP failed (the iterate stays at the last good one).
  * SQP is refused for a capsule with the R2NMPC tightening attached, for the coupled SNMPC OCP, for the development kernels "fused" /
  * "pipeline4", by tum_ocp_step_async and by the device closed loop (tum_sim_*): those stay SQP-RTI.
+ *
+ * "globalization"          0 FIXED_STEP (default: every instance moves by nlp_solver_step_length), 1 MERIT_BACKTRACKING: a step length per
+ *                          instance and per iteration, chosen by a line search on an L1 merit function. Read by an SQP solve only (an
+ *                          SQP-RTI solve and rti_phase are unaffected).
+ * "alpha_min"              in (0, 1] (default 0.05, acados')      "alpha_reduction"   in (0, 1) (default 0.7, acados')
+ * "merit_weight_eq"        finite, >= 0 (default 1): the weight mu_eq of the shooting defects. Not an acados name: acados weights them
+ *                          with the multipliers of the dynamics, which condensing does not keep.
+ * The candidates are alpha_j = alpha_reduction^j (formed as j products), j = 0 .. K - 1, K = 1 + floor(log alpha_min / log alpha_reduction):
+ *   9 with the defaults, the smallest 0.7^8 = 0.0576. A solve with K > 16 is refused, and so is one with MERIT_BACKTRACKING and
+ *   nlp_solver_step_length != 1.
+ * Merit function at z = (X, U, sl, su):  phi(z) = cost(z) + mu_eq E(z) + mu_in V(z), with cost the value get_cost reports (wrapped yaw,
+ *   stage terms scaled by dt, diagonal or full W, z s + Z s^2 / 2 per row side), E = |x0 - X_0|_1 + sum_k |f(X_k, U_k) - X_{k+1}|_1 with f the
+ *   ERK4 x nsub integrator of the model, V = the sum over the row sides of max(0, -t), t = value - lo + s_l (lower) or hi - value + s_u
+ *   (upper), with the row's value -- U[k][1], X[s][6], the gg expression at X_s -- AT z, not its linearisation. mu_in is kept per
+ *   instance: 0 at the start of every SQP solve, then the largest |multiplier| of the rows over the QPs of this solve, the QP just solved
+ *   included.
+ * Line search: with z_prev the iterate in front of the QP and z_qp what the interior point method and the expansion return,
+ *   z(alpha) = z_prev + alpha (z_qp - z_prev). Accepted is the first j with phi(z(alpha_j)) < phi(z(0)) (simple decrease, acados'
+ *   line_search_use_sufficient_descent = 0), else alpha_{K-1}. X, U, slacks and multipliers move by the accepted alpha; an instance that
+ *   took alpha < 1 starts its next QP cold (interpolated multipliers are no warm start). All candidates of all instances are evaluated
+ *   by ONE kernel launch per iteration (sqp_merit_kernel). Finished instances and failed QPs are treated as under FIXED_STEP. The
+ *   reported cost is that of the returned iterate.
  *
  * "rti_phase"              acados' split of the real-time iteration: 0 preparation and feedback in one solve (default, as before),
  *                          1 PREPARATION, 2 FEEDBACK; any other value is an error.
@@ -190,6 +212,13 @@ int tum_ocp_get_cost(tum_ocp *c, double *out, int b0, int nb);
  * "status" -> nb ints, "qp_status" -> nb ints
  * "res" -> nb x 3 doubles (stat, ineq, comp residuals of the last QP)
  * "residuals" -> nb x 4 doubles (stat, eq, ineq, comp residuals of the NLP at the returned iterate; after an SQP solve only).
+ * After an SQP solve with globalization MERIT_BACKTRACKING only (refused otherwise):
+ * "merit_dims" -> 2 ints: K, the number of candidates, and M, the nlp_solver_max_iter of that solve
+ * "alpha" -> nb x M doubles: row b holds the accepted alpha of its QPs 1 .. sqp_iter[b], then zeros (a QP that failed has no line
+ *   search: its entry stays 0)
+ * "merit" -> nb x (K + 1) x 3 doubles: cost, E, V of the instance's own LAST line search at the candidates j = 0 .. K - 1 and, in row K,
+ *   at alpha = 0 (zeros for an instance that never searched)
+ * "merit_weights" -> nb x 2 doubles: mu_eq, mu_in
  * "lin_uniform" -> 1 int: linearisations of this capsule that took the uniform path (options_set "lin_dedup") since it was created. */
 int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b0, int nb);
 /* acados_solver.reset()   NMPC_class.py:251 -- zero the iterate of every instance */

@@ -1,6 +1,7 @@
 // sqp_kernels.hpp -- the kernels a full SQP solve adds around the unchanged SQP-RTI pipeline (tum_nmpc.hip: launch_sqp).
 //
 // One SQP iteration is   [lin, cond] -> nlp_residual_kernel -> sqp_snapshot_kernel -> [ipm, expand] -> sqp_commit_kernel
+// (globalization MERIT_BACKTRACKING: sqp_merit_kernel between the expansion and the commit chooses every instance's step length)
 // and behind the last QP one more [lin, cond] -> nlp_residual_kernel describes the iterate the solve returns (acados' order:
 // linearise, evaluate the residuals, test for termination, then solve the QP). The kernels of the pipeline are the RTI's own,
 // launched with the RTI's arguments: instances that have converged or failed ride along and are put back by the commit kernel.
@@ -25,6 +26,18 @@ struct SqpArgs {
     int last;               // 1: no QP follows this pass (iteration cap): the instances still active end with status 2
     int cost;               // 1: the cost of the iterate is evaluated here (alpha != 1: the expansion's is that of the full step; pass 0
                             //    of a cold-started solve: an instance that converges there has no expansion)
+};
+
+// globalization MERIT_BACKTRACKING: what sqp_merit_kernel reads and writes beside the SQP state
+constexpr int MERIT_KMAX = 16;          // candidates alpha_j = alpha_reduction^j, j < K <= MERIT_KMAX
+struct MeritArgs {
+    double *alpha;          // [b]              step length the line search of this iteration accepted (null: FIXED_STEP)
+    double *mu_in;          // [b]              weight of the row violations: largest |multiplier| of the QPs of this solve so far
+    double *table;          // [b][K + 1][3]    cost, E, V at the candidates j = 0 .. K - 1 and (row K) at alpha = 0, of the instance's last line search
+    double *hist;           // [b][hist_len]    accepted alpha of the QPs 1 .. sqp_iter (a failed QP leaves its 0)
+    int K, hist_len;
+    double mu_eq;           // weight of the shooting defects (merit_weight_eq)
+    double cand[MERIT_KMAX];
 };
 
 // Residuals of the NLP at the current iterate, with the multipliers of the previous QP, in the condensed form the pipeline
@@ -157,6 +170,170 @@ __global__ void __launch_bounds__(64) nlp_residual_kernel(const PArgs pa, const 
     }
 }
 
+// One shooting interval without sensitivities: the state part of rk4_sens (nmpc_device.hpp), operation for operation.
+__device__ __forceinline__ void rk4_state(const Model &p, const double x0[8], const double u[2], double dt, int nsub, double xn[8])
+{
+    double x[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) x[i] = x0[i];
+    const double h = dt / nsub;
+    for (int sub = 0; sub < nsub; sub++) {
+        double xacc[6], kp[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) { xacc[i] = 0.0; kp[i] = 0.0; }
+#pragma unroll 1
+        for (int st = 0; st < 4; st++) {
+            const double ci = (st == 0) ? 0.0 : (st == 3 ? 1.0 : 0.5);
+            const double bi = (st == 0 || st == 3) ? (1.0 / 6.0) : (2.0 / 6.0);
+            const double ch = ci * h;
+            const double psi = x[2] + ch * kp[2];
+            const double vl = x[3] + ch * kp[3], vt = x[4] + ch * kp[4], r = x[5] + ch * kp[5];
+            const double de = x[6] + ch * u[1], a = x[7] + ch * u[0];
+            double f[3], J[3][5];          // (the partials are dead code here)
+            stm_core(p, vl, vt, r, de, a, f, J);
+            double sn, cs;
+            fast_sincos(psi, &sn, &cs);
+            double k[6];
+            k[0] = vl * cs - vt * sn; k[1] = vl * sn + vt * cs; k[2] = r;
+            k[3] = f[0]; k[4] = f[1]; k[5] = f[2];
+#pragma unroll
+            for (int i = 0; i < 6; i++) { xacc[i] += bi * k[i]; kp[i] = k[i]; }
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) x[i] += h * xacc[i];
+        x[6] += h * u[1]; x[7] += h * u[0];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) xn[i] = x[i];
+}
+
+// The trial points of MERIT_BACKTRACKING, between the expansion and the commit kernel: one wavefront per (instance, candidate), lane =
+// stage. With z_prev the snapshot in front of the QP and z_qp what the interior point method and the expansion left, the trial point
+// is z(alpha) = z_prev + alpha (z_qp - z_prev) in X, U and the slacks, and the wavefront j of an instance evaluates there, for
+// alpha = cand[j] (j < K) or alpha = 0 (j = K),
+//   cost  the cost as nlp_residual_kernel forms it: wrapped yaw, dt scaling, diagonal or full W, z s + Z s^2 / 2 per row side
+//   E     | x0 - X_0 |_1 + sum_k | f(X_k, U_k) - X_{k+1} |_1   (f: ERK4 x nsub of the model, rk4_state)
+//   V     sum over the row sides of max(0, -t), t = value - lo + s_l or hi - value + s_u with the row's value AT the trial point
+//         (steering-rate box of stage k: U[k][1]; steering angle and gg row of stage s: X[s][6], h_con(X_s))
+// into row j of the instance's table. The commit kernel, behind it on the stream, reads the table and decides (merit_accept). An
+// instance that has finished, or whose QP failed, is left alone: its table stays.
+__global__ void __launch_bounds__(64) sqp_merit_kernel(const KArgs ka, const SqpArgs sq, const MeritArgs ma)
+{
+    const int b = blockIdx.x, j = blockIdx.y;
+    if (b >= ka.batch || j > ma.K) return;
+    if (sq.state[b] != 0 || ka.status[b] != 0) return;          // (uniform over the wavefront)
+    const int lane = threadIdx.x;
+    // the model's constants in LDS: held in scalar registers across the Runge-Kutta loop they do not fit (18 spilled)
+    __shared__ Model sM;
+    static_assert(sizeof(Model) % sizeof(double) == 0, "copied in doubles");
+    for (int i = lane; i < (int)(sizeof(Model) / sizeof(double)); i += 64)
+        reinterpret_cast<double *>(&sM)[i] = reinterpret_cast<const double *>(&ka.mp)[i];
+    wsync();
+    const int N = ka.N, NB = N + 1;
+    const int nx = NB * NX, nu = N * NU, nl = 6 * N + 2;
+    const double dt = ka.dt;
+    const double a = (j < ma.K) ? ma.cand[j] : 0.0;
+    // lane = stage. The lanes behind the horizon work on copies of the last stage and contribute nothing
+    const int s = (lane < NB) ? lane : N, k = (lane < N) ? lane : N - 1;
+    const bool has_x = lane < NB, has_u = lane < N, has_rows = lane >= 1 && lane < NB;
+    double x[8], u[2];
+    double cl = 0.0, e = 0.0, v = 0.0;
+    {
+        const double *snap = sq.snap + (size_t)b * sq.snap_len;
+        const double *Xq = ka.X + (size_t)b * nx + s * NX, *Uq = ka.U + (size_t)b * nu + k * NU, *Sq = ka.slack + (size_t)b * 6 * N;
+        const double *Xp = snap + s * NX, *Up = snap + nx + k * NU, *Sp = snap + nx + nu + nl;
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const double p = Xp[i]; x[i] = p + a * (Xq[i] - p); }
+#pragma unroll
+        for (int i = 0; i < 2; i++) { const double p = Up[i]; u[i] = p + a * (Uq[i] - p); }
+        if (lane == 0) {
+            const double *gx0 = ka.x0 + (size_t)b * NX;
+#pragma unroll
+            for (int i = 0; i < 8; i++) e += fabs(gx0[i] - x[i]);
+        }
+        // rows and slack cost: the box of stage k on the lanes < N, the steering angle and the gg row of stage s on the lanes 1 .. N
+        const double *gbnd = ka.bnd + (size_t)b * 6 * NB, *gpen = ka.pen + (size_t)b * 36;
+        double h, g3, g5, g7;
+        h_con(sM, x[3], x[5], x[7], h, g3, g5, g7);
+#pragma unroll
+        for (int ty = 0; ty < 3; ty++) {
+            const int st = (ty == 0) ? k : s;
+            const int idx = (ty == 0) ? k : N + 2 * (s - 1) + ((ty == 2) ? 1 : 0);
+            const bool on = (ty == 0) ? has_u : has_rows;
+            const double val = (ty == 0) ? u[1] : ((ty == 1) ? x[6] : h);
+            const double lo = gbnd[(2 * ty) * NB + st], hi = gbnd[(2 * ty + 1) * NB + st];
+            const int pc = (ty == 0) ? ((k == 0) ? 0 : 1) : ((st < N) ? 1 : 2);
+            const double sc = (ty == 0 || st < N) ? dt : 1.0;
+#pragma unroll
+            for (int sd = 0; sd < 2; sd++) {
+                const int si = on ? sd * 3 * N + idx : 0;
+                const double s0 = Sp[si], sl = s0 + a * (Sq[si] - s0);
+                const double z = sc * gpen[(pc * 3 + ty) * 4 + sd], Z = sc * gpen[(pc * 3 + ty) * 4 + 2 + sd];
+                const double t = sd ? hi - val + sl : val - lo + sl;
+                if (on) { v += fmax(-t, 0.0); cl += z * sl + 0.5 * Z * sl * sl; }
+            }
+        }
+        // least-squares cost of the stage
+        const double *yr = ka.yref + ((size_t)b * NB + s) * 6;
+        double rr[6];
+        rr[0] = x[0] - yr[0]; rr[1] = x[1] - yr[1]; rr[2] = wrap_yaw(x[2]) - yr[2]; rr[3] = x[3] - yr[3];
+        rr[4] = u[0] - yr[4]; rr[5] = u[1] - yr[5];
+        const int ny = (s < N) ? 6 : 4;
+        double acc = 0.0;
+        if (ka.Wf) {
+            const double *Wk = ka.Wf + ((size_t)b * NB + s) * 36;
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int i2 = 0; i2 < 6; i2++) if (i < ny && i2 < ny) acc += Wk[i * 6 + i2] * rr[i] * rr[i2];
+        } else {
+            const double *Wd = ka.W + ((size_t)b * NB + s) * 6;
+#pragma unroll
+            for (int i = 0; i < 6; i++) if (i < ny) acc += Wd[i] * rr[i] * rr[i];
+        }
+        if (has_x) cl += 0.5 * ((s < N) ? dt : 1.0) * acc;
+    }
+    // shooting defects: the lane's interval against the trial state of the lane above
+    {
+        double xn[8];
+        rk4_state(sM, x, u, dt, ka.nsub, xn);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const double nxt = lane_gather(x[i], ((lane + 1) & 63) * 4);
+            if (has_u) e += fabs(xn[i] - nxt);
+        }
+    }
+    cl = wave_sum(cl); e = wave_sum(e); v = wave_sum(v);
+    if (lane == 0) {
+        double *t = ma.table + ((size_t)b * (ma.K + 1) + j) * 3;
+        t[0] = cl; t[1] = e; t[2] = v;
+    }
+}
+
+// The decision of the line search, by the first wavefront of the commit kernel for an instance that takes its step: the weight mu_in
+// becomes the largest |multiplier| of the QPs of this solve so far, this one included; the merit function is
+// phi = cost + mu_eq E + mu_in V on the rows of the table; accepted is the first j with phi(alpha_j) < phi(0), else the smallest
+// candidate. Writes alpha, mu_in and the history entry of this QP; returns alpha (on every lane).
+__device__ __forceinline__ double merit_accept(const KArgs &ka, const MeritArgs &ma, int b, int it, int lane)
+{
+    const int N = ka.N, K = ma.K;
+    const double *glm = ka.qp_lam + (size_t)b * (6 * N + 2);
+    double m = 0.0;
+    for (int i = lane; i < 6 * N; i += 64) m = fmax(m, fabs(glm[i]));
+    const double mu = fmax(ma.mu_in[b], wave_max(m));
+    const double *t = ma.table + (size_t)b * (K + 1) * 3;
+    const double phi0 = t[3 * K] + ma.mu_eq * t[3 * K + 1] + mu * t[3 * K + 2];
+    int acc = K - 1;
+    for (int j = 0; j < K; j++)
+        if (t[3 * j] + ma.mu_eq * t[3 * j + 1] + mu * t[3 * j + 2] < phi0) { acc = j; break; }
+    const double a = ma.cand[acc];
+    if (lane == 0) {
+        ma.alpha[b] = a; ma.mu_in[b] = mu;
+        if (it < ma.hist_len) ma.hist[(size_t)b * ma.hist_len + it] = a;
+    }
+    return a;
+}
+
 // what the commit kernel may have to put back: the iterate and the QP's outputs, in front of the QP
 __global__ void __launch_bounds__(256) sqp_snapshot_kernel(const KArgs ka, const SqpArgs sq)
 {
@@ -182,26 +359,34 @@ __global__ void __launch_bounds__(256) sqp_snapshot_kernel(const KArgs ka, const
 // Behind the QP and its expansion. An instance that had converged or failed before this iteration gets back everything the
 // snapshot holds (bit-identical); an active one whose QP failed gets back its iterate (status 4 and the QP's statistics stay) and
 // stops; an active one that took the step moves by alpha: z <- z_prev + alpha (z_new - z_prev) for X, U, slacks and multipliers.
-__global__ void __launch_bounds__(256) sqp_commit_kernel(const KArgs ka, const SqpArgs sq)
+// alpha is sq.alpha, or with globalization MERIT_BACKTRACKING (ma.alpha set) the instance's own, which the first wavefront decides here
+// from the table sqp_merit_kernel has written (merit_accept): an instance that took less than the full step also starts its next QP
+// cold (its warm-start word is cleared: interpolated multipliers are no warm start).
+__global__ void __launch_bounds__(256) sqp_commit_kernel(const KArgs ka, const SqpArgs sq, const MeritArgs ma)
 {
     __shared__ int mode;          // 0 restore all, 1 restore the iterate (QP failed), 2 step
+    __shared__ double step;       // its length
     const int b = blockIdx.x;
     if (b >= ka.batch) return;
-    if (threadIdx.x == 0) {
+    if (threadIdx.x < 64) {
         const int st = sq.state[b];
-        int m = 0;
-        if (st == 0) {
-            sq.sqp_iter[b] += 1;
-            if (ka.status[b] != 0) { m = 1; sq.state[b] = 2; } else m = 2;
+        const int m = (st != 0) ? 0 : ((ka.status[b] != 0) ? 1 : 2);
+        double al = sq.alpha;
+        if (ma.alpha && m == 2) al = merit_accept(ka, ma, b, sq.sqp_iter[b], threadIdx.x);
+        if (threadIdx.x == 0) {
+            if (st == 0) {
+                sq.sqp_iter[b] += 1;
+                if (m == 1) sq.state[b] = 2;
+            }
+            mode = m; step = al;
         }
-        mode = m;
     }
     __syncthreads();
     const int m = mode;
-    if (m == 2 && sq.alpha == 1.0) return;
+    const double a = step;
+    if (m == 2 && a == 1.0) return;
     const int N = ka.N, nx = (N + 1) * NX, nu = N * NU, nl = 6 * N + 2, ns = 6 * N;
     const double *o = sq.snap + (size_t)b * sq.snap_len;
-    const double a = sq.alpha;
     auto put = [&](double *dst, const double *prev, int n) {
         if (m == 2) { for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = prev[i] + a * (dst[i] - prev[i]); }
         else for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = prev[i];
@@ -210,6 +395,7 @@ __global__ void __launch_bounds__(256) sqp_commit_kernel(const KArgs ka, const S
     put(ka.U + (size_t)b * nu, o + nx, nu);
     put(ka.qp_lam + (size_t)b * nl, o + nx + nu, nl - 2);          // (the warm-start flag behind the multipliers: the QP's own)
     put(ka.slack + (size_t)b * ns, o + nx + nu + nl, ns);
+    if (m == 2 && ma.alpha && threadIdx.x == 0) ka.qp_lam[(size_t)b * nl + 6 * N] = 0.0;
     if (m != 2 && threadIdx.x == 0) {
         ka.qp_lam[(size_t)b * nl + 6 * N] = o[nx + nu + 6 * N];
         ka.cost[b] = o[nx + nu + nl + ns];

@@ -95,6 +95,13 @@ struct tum_ocp {
     double *dnlpres = nullptr, *dsnap = nullptr; int *dsqpstate = nullptr, *dsqpiter = nullptr, *dsnapi = nullptr;
     unsigned *dactive = nullptr, *hactive = nullptr; int active_cap = 0; hipEvent_t evpoll[2] = {};
     bool solved_sqp = false;
+    // globalization of an SQP solve (tum_ocp_options_set "globalization"): 0 FIXED_STEP (nlp_alpha), 1 MERIT_BACKTRACKING -- a line search
+    // per instance and iteration (sqp_merit_kernel) over the candidates merit_alpha_reduction^j >= merit_alpha_min. Device state of the
+    // line search (allocated by the first such solve): accepted alpha, weight mu_in, merit table, alpha history [b][merit_hist_cap];
+    // whether the LAST solve was one, and its number of candidates K and history length M (the nlp_solver_max_iter it ran with)
+    int globalization = 0; double merit_alpha_min = 0.05, merit_alpha_reduction = 0.7, merit_weight_eq = 1.0;
+    double *dmalpha = nullptr, *dmmu = nullptr, *dmtable = nullptr, *dmhist = nullptr; int merit_hist_cap = 0;
+    bool solved_merit = false; int merit_K = 0, merit_M = 0; double merit_weight_eq_used = 1.0;
     // no solve since the last cold start / reset: the multipliers and slacks on the device are those of an EARLIER problem. An SQP-RTI
     // solve never reads them (the warm-start word is 0); a full SQP solve evaluates pass 0 with them and damps towards them, so it clears
     // them first (acados' reset() zeroes them)
@@ -358,6 +365,7 @@ extern "C" void tum_ocp_free(tum_ocp *c)
     if (c->hlin_bad) (void)hipHostFree(c->hlin_bad);
     (void)hipFree(c->dnlpres); (void)hipFree(c->dsnap); (void)hipFree(c->dsqpstate); (void)hipFree(c->dsqpiter); (void)hipFree(c->dsnapi); (void)hipFree(c->dactive);
     if (c->hactive) (void)hipHostFree(c->hactive);
+    (void)hipFree(c->dmalpha); (void)hipFree(c->dmmu); (void)hipFree(c->dmtable); (void)hipFree(c->dmhist);
     for (hipEvent_t e : c->evpoll) if (e) (void)hipEventDestroy(e);
     if (c->hin_s) (void)hipHostFree(c->hin_s);
     if (c->hsum_s) (void)hipHostFree(c->hsum_s);
@@ -1220,7 +1228,7 @@ static int solve_done(tum_ocp *c, SolveKind kind, bool ipm_timed)
         }
         c->order_valid = true;
     }
-    c->solved = true; c->solved_pipe = c->pipe; c->solved_sqp = kind == SOLVE_SQP; c->cold = false;
+    c->solved = true; c->solved_pipe = c->pipe; c->solved_sqp = kind == SOLVE_SQP; c->solved_merit = false; c->cold = false;
     invalidate(c, CH_ITERATE);          // (whichever kernel variant ran: the solve wrote the new iterate)
     c->prep = 0; c->prep_timed = false;          // (a feedback consumes its preparation; a one-call solve discards a pending one)
     if (kind == SOLVE_REPLAY) { if (c->sn) c->xs_lazy = true; return 0; }          // (the epilogue kernel of the chunk, as launch_pipeline records it)
@@ -1294,8 +1302,9 @@ static int launch(tum_ocp *c, bool events = true)
 }
 
 // ---- full SQP solves (nlp_solver_type SQP)
-// acados' option fields (acados_ocp_SNMPC.json: nlp_solver_type, nlp_solver_max_iter, nlp_solver_tol_*, nlp_solver_step_length); globalization
-// is FIXED_STEP
+// acados' option fields (acados_ocp_SNMPC.json: nlp_solver_type, nlp_solver_max_iter, nlp_solver_tol_*, nlp_solver_step_length) and its
+// globalization: FIXED_STEP (the default) or MERIT_BACKTRACKING with alpha_min, alpha_reduction and -- not an acados name: the weight of the
+// shooting defects in the merit function, where acados takes the multipliers of the dynamics that condensing does not keep -- merit_weight_eq
 extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
 {
     if (!c || !field) return fail("null argument");
@@ -1328,6 +1337,26 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
         c->nlp_alpha = value;
         return 0;
     }
+    if (f == "globalization") {      // read by an SQP solve only; what does not go together with it is refused there
+        if (value != 0.0 && value != 1.0) return fail("options_set globalization: 0 (FIXED_STEP) or 1 (MERIT_BACKTRACKING)");
+        c->globalization = (int)value;
+        return 0;
+    }
+    if (f == "alpha_min") {
+        if (!(value > 0.0 && value <= 1.0)) return fail("options_set alpha_min: in (0, 1]");
+        c->merit_alpha_min = value;
+        return 0;
+    }
+    if (f == "alpha_reduction") {
+        if (!(value > 0.0 && value < 1.0)) return fail("options_set alpha_reduction: in (0, 1)");
+        c->merit_alpha_reduction = value;
+        return 0;
+    }
+    if (f == "merit_weight_eq") {
+        if (!(value >= 0.0) || std::isinf(value)) return fail("options_set merit_weight_eq: a finite value >= 0");
+        c->merit_weight_eq = value;
+        return 0;
+    }
     if (f == "rti_phase") {      // acados: 0 PREPARATION_AND_FEEDBACK, 1 PREPARATION, 2 FEEDBACK
         if (value != 0.0 && value != 1.0 && value != 2.0) return fail("options_set rti_phase: 0 (preparation and feedback), 1 (preparation) or 2 (feedback)");
         if (value != 0.0) { if (const char *why = rti_unsupported(c)) return fail(std::string("options_set rti_phase: ") + why); }
@@ -1340,13 +1369,24 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
         return 0;
     }
     return fail("options_set: unknown field '" + f + "' (lin_dedup | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
-                "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length | rti_phase)");
+                "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length | rti_phase), of the SQP globalization (globalization | "
+                "alpha_min | alpha_reduction | merit_weight_eq)");
 }
 
 // One full SQP solve: [lin, cond, residuals] then, while an instance is active and the cap is not reached, [snapshot, ipm, expand,
 // commit, lin, cond, residuals]. The host reads the number of active instances of every residual pass (a 4-byte copy into pinned
 // memory behind an event), one iteration behind the GPU; the kernels of the pipeline are the RTI's, launched as an SQP-RTI solve
-// launches them.
+// launches them. With globalization MERIT_BACKTRACKING sqp_merit_kernel stands between the expansion and the commit: all candidates
+// of every instance in ONE launch (the host reads the active count an iteration late; a backtracking loop on the host would stall the
+// stream), and the commit kernel accepts a step length for every instance from that table and moves the instance by it.
+
+// number of candidates alpha_reduction^j >= alpha_min, j = 0 ..: 1 + floor(log alpha_min / log alpha_reduction) (9 with acados' defaults)
+static int merit_candidates(const tum_ocp *c)
+{
+    const double k = std::floor(std::log(c->merit_alpha_min) / std::log(c->merit_alpha_reduction));
+    return (k < 1e6) ? 1 + (int)k : 1000000;
+}
+
 static int launch_sqp(tum_ocp *c)
 {
     DevGuard guard(c->d.device); GUARD_OK(guard);
@@ -1359,7 +1399,27 @@ static int launch_sqp(tum_ocp *c)
     if (c->kmode == 3) return fail("solve: SQP runs on the pipeline only, not on the development kernel 'pipeline4'");
 #endif
     const size_t B = c->batch; const int N = c->N;
+    const bool merit = c->globalization == 1;
+    const int K = merit ? merit_candidates(c) : 0;
+    if (merit) {
+        if (c->nlp_alpha != 1.0)
+            return fail("solve: globalization MERIT_BACKTRACKING chooses every step length itself and does not go together with "
+                        "nlp_solver_step_length != 1 (it is " + std::to_string(c->nlp_alpha) + "): set one of the two back");
+        if (K > MERIT_KMAX)
+            return fail("solve: globalization MERIT_BACKTRACKING: alpha_min " + std::to_string(c->merit_alpha_min) + " and alpha_reduction " +
+                        std::to_string(c->merit_alpha_reduction) + " give " + std::to_string(K) + " candidate step lengths; at most " +
+                        std::to_string(MERIT_KMAX) + " (1 + floor(log alpha_min / log alpha_reduction))");
+    }
     const int snap_len = (N + 1) * NX + N * NU + (6 * N + 2) + 6 * N + 4;
+    if (merit && !c->dmalpha) {
+        if (dalloc(&c->dmalpha, B) != hipSuccess || dalloc(&c->dmmu, B) != hipSuccess || dalloc(&c->dmtable, B * (MERIT_KMAX + 1) * 3) != hipSuccess)
+            return fail("solve: device allocation failed (SQP, MERIT_BACKTRACKING)");
+    }
+    if (merit && c->merit_hist_cap < c->nlp_max_iter) {
+        (void)hipFree(c->dmhist); c->dmhist = nullptr; c->merit_hist_cap = 0;
+        if (dalloc(&c->dmhist, B * (size_t)c->nlp_max_iter) != hipSuccess) return fail("solve: device allocation failed (SQP, MERIT_BACKTRACKING)");
+        c->merit_hist_cap = c->nlp_max_iter;
+    }
     if (!c->dnlpres) {
         if (dalloc(&c->dnlpres, B * 4) != hipSuccess || dalloc(&c->dsnap, B * snap_len) != hipSuccess || dalloc(&c->dsqpstate, B) != hipSuccess ||
             dalloc(&c->dsqpiter, B) != hipSuccess || dalloc(&c->dsnapi, B * 3) != hipSuccess) return fail("solve: device allocation failed (SQP)");
@@ -1392,10 +1452,21 @@ static int launch_sqp(tum_ocp *c)
     sq.snap = c->dsnap; sq.snapi = c->dsnapi; sq.snap_len = snap_len;
     sq.tol_stat = c->nlp_tol[0]; sq.tol_eq = c->nlp_tol[1]; sq.tol_ineq = c->nlp_tol[2]; sq.tol_comp = c->nlp_tol[3];
     sq.alpha = c->nlp_alpha;
+    MeritArgs ma{};          // (ma.alpha null: FIXED_STEP)
+    if (merit) {
+        // every solve starts with mu_in = 0, an empty table and an empty history
+        HIPCHK(hipMemsetAsync(c->dmmu, 0, sizeof(double) * B, c->stream));
+        HIPCHK(hipMemsetAsync(c->dmtable, 0, sizeof(double) * B * (size_t)(K + 1) * 3, c->stream));
+        HIPCHK(hipMemsetAsync(c->dmhist, 0, sizeof(double) * B * (size_t)c->nlp_max_iter, c->stream));
+        ma.alpha = c->dmalpha; ma.mu_in = c->dmmu; ma.table = c->dmtable; ma.hist = c->dmhist;
+        ma.K = K; ma.hist_len = c->nlp_max_iter; ma.mu_eq = c->merit_weight_eq;
+        ma.cand[0] = 1.0;
+        for (int j = 1; j < K; j++) ma.cand[j] = ma.cand[j - 1] * c->merit_alpha_reduction;          // (alpha_reduction^j as j products)
+    }
     const PArgs pa = pargs(c);
     auto residuals = [&](int pass) {
         sq.pass = pass; sq.last = (pass == c->nlp_max_iter) ? 1 : 0;
-        sq.cost = (c->nlp_alpha != 1.0 || (pass == 0 && cold)) ? 1 : 0;
+        sq.cost = (c->nlp_alpha != 1.0 || merit || (pass == 0 && cold)) ? 1 : 0;
         if (launch_pipeline(c, false, 1)) return 1;
         with_tiles(c, [&](auto ntc) { hipLaunchKernelGGL(nlp_residual_kernel<decltype(ntc)::value>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq); });
         HIPCHK(hipGetLastError());
@@ -1415,14 +1486,17 @@ static int launch_sqp(tum_ocp *c)
         hipLaunchKernelGGL(sqp_snapshot_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq);
         if (launch_pipeline(c, c->time_ipm, 2)) return 1;
         invalidate(c, CH_ITERATE);          // (the expansion wrote a new iterate: the residual pass below linearises the general way)
-        hipLaunchKernelGGL(sqp_commit_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq);
+        if (merit) hipLaunchKernelGGL(sqp_merit_kernel, dim3(c->batch, K + 1), dim3(64), 0, c->stream, c->ka, sq, ma);          // (one wavefront per trial point)
+        hipLaunchKernelGGL(sqp_commit_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq, ma);
         HIPCHK(hipGetLastError());
         if (residuals(it + 1) || count_copy(it + 1)) return 1;
         HIPCHK(hipEventSynchronize(c->evpoll[it & 1]));
         if (c->hactive[it & 1] == 0) break;
     }
     HIPCHK(hipEventRecord(c->ev1, c->stream));
-    return solve_done(c, SOLVE_SQP, c->time_ipm);
+    if (solve_done(c, SOLVE_SQP, c->time_ipm)) return 1;
+    c->solved_merit = merit; c->merit_K = K; c->merit_M = c->nlp_max_iter; c->merit_weight_eq_used = c->merit_weight_eq;
+    return 0;
 }
 
 // 1: dispatch instances longest-first using the previous solve's iteration counts (default), 0: natural order
@@ -1549,6 +1623,11 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
     if (chk_range(c, b0, nb)) return 1;
     if (f == "sqp_iter" && !c->solved_sqp) { int *o = (int *)out; for (int i = 0; i < nb; i++) o[i] = 1; return 0; }      // (SQP-RTI: one QP per solve)
     if (f == "residuals" && !c->solved_sqp) return fail("get_stats residuals: computed by a full SQP solve only (options_set nlp_solver_type 1)");
+    const bool merit_field = f == "alpha" || f == "merit" || f == "merit_weights" || f == "merit_dims";
+    if (merit_field && !(c->solved_sqp && c->solved_merit))
+        return fail("get_stats " + f + ": written by the line search of a full SQP solve with globalization MERIT_BACKTRACKING only "
+                    "(options_set nlp_solver_type 1, globalization 1)");
+    if (f == "merit_dims") { int *o = (int *)out; o[0] = c->merit_K; o[1] = c->merit_M; return 0; }
     if (c->cache_valid && (f == "qp_iter" || f == "status")) {
         int *o = (int *)out; const int col = (f == "status") ? 3 : 4;
         for (int i = 0; i < nb; i++) o[i] = (int)c->hsum_s[(size_t)(b0 + i) * 5 + col];
@@ -1563,6 +1642,22 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
     if (f == "res") { HIPCHK(hipMemcpy(out, c->dres + (size_t)b0 * 3, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "sqp_iter") { HIPCHK(hipMemcpy(out, c->dsqpiter + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "residuals") { HIPCHK(hipMemcpy(out, c->dnlpres + (size_t)b0 * 4, sizeof(double) * 4 * nb, hipMemcpyDeviceToHost)); return 0; }
+    if (f == "alpha") {
+        HIPCHK(hipMemcpy(out, c->dmhist + (size_t)b0 * c->merit_M, sizeof(double) * (size_t)c->merit_M * nb, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (f == "merit") {
+        const size_t row = (size_t)(c->merit_K + 1) * 3;
+        HIPCHK(hipMemcpy(out, c->dmtable + (size_t)b0 * row, sizeof(double) * row * nb, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (f == "merit_weights") {
+        std::vector<double> mu(nb);
+        HIPCHK(hipMemcpy(mu.data(), c->dmmu + b0, sizeof(double) * nb, hipMemcpyDeviceToHost));
+        double *o = (double *)out;
+        for (int i = 0; i < nb; i++) { o[2 * i] = c->merit_weight_eq_used; o[2 * i + 1] = mu[i]; }
+        return 0;
+    }
     return fail("get_stats: unknown field '" + f + "'");
 }
 

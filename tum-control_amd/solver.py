@@ -192,8 +192,10 @@ def _dp(a):
 _FIELD_BYTES = {}          # field name -> bytes, encoded once
 # acados' defaults of the NLP solver options as the reference's generated solver carries them (acados_ocp_SNMPC.json)
 _NLP_DEFAULTS = dict(nlp_solver_max_iter=100, nlp_solver_tol_stat=1e-6, nlp_solver_tol_eq=1e-6, nlp_solver_tol_ineq=1e-6,
-                     nlp_solver_tol_comp=1e-6, nlp_solver_step_length=1.0)
+                     nlp_solver_tol_comp=1e-6, nlp_solver_step_length=1.0, alpha_min=0.05, alpha_reduction=0.7, merit_weight_eq=1.0)
 _NLP_TYPES = {"SQP_RTI": 0, "SQP": 1}
+# acados' globalization of an SQP solve: the step length of nlp_solver_step_length, or a line search per instance on an L1 merit function
+_GLOBALIZATIONS = {"FIXED_STEP": 0, "MERIT_BACKTRACKING": 1}
 # acados' rti_phase values: 0 preparation and feedback in one solve(), 1 preparation, 2 feedback
 _RTI_PHASES = {0: "PREPARATION_AND_FEEDBACK", 1: "PREPARATION", 2: "FEEDBACK"}
 
@@ -205,13 +207,25 @@ def _rti_phase_value(value):
     return int(value)
 
 
+def _globalization_value(value):
+    """globalization as acados takes it, by name (or the library's 0 / 1); anything else is refused before the library sees it"""
+    if isinstance(value, str):
+        if value not in _GLOBALIZATIONS:
+            raise Exception(f"BatchedOcpSolver.options_set: globalization must be one of {sorted(_GLOBALIZATIONS)}, got '{value}'")
+        return _GLOBALIZATIONS[value]
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer, float, np.floating)) or value not in _GLOBALIZATIONS.values():
+        raise Exception(f"BatchedOcpSolver.options_set: globalization must be one of {sorted(_GLOBALIZATIONS)} (0 / 1), got {value!r}")
+    return int(value)
+
+
 class BatchedOcpSolver:
     """`batch` independent copies of the nominal NMPC OCP on one MI355X; acados method names."""
 
     def __init__(self, N=38, dt=0.08, nsub=3, batch=1, device=0, cfg=None, store_qp_in=False,
                  qp_iter_max=50, qp_tol=(1e-8, 1e-8, 1e-8), qp_mu0=0.05, qp_t0=0.05, qp_warm_start=None, qp_warm_mu=0.0,
                  qp_warm_flips=0, qp_warm_viol=0.0, nlp_solver_type="SQP_RTI", nlp_solver_max_iter=100, nlp_solver_tol_stat=1e-6,
-                 nlp_solver_tol_eq=1e-6, nlp_solver_tol_ineq=1e-6, nlp_solver_tol_comp=1e-6, nlp_solver_step_length=1.0):
+                 nlp_solver_tol_eq=1e-6, nlp_solver_tol_ineq=1e-6, nlp_solver_tol_comp=1e-6, nlp_solver_step_length=1.0,
+                 globalization="FIXED_STEP", alpha_min=0.05, alpha_reduction=0.7, merit_weight_eq=1.0):
         self._L = load_library()
         self.N, self.dt, self.nsub, self.batch = int(N), float(dt), int(nsub), int(batch)
         self.cfg = cfg or _config.default_config()
@@ -229,10 +243,13 @@ class BatchedOcpSolver:
         self.status = 0
         # NLP solver options (acados_ocp_SNMPC.json: nlp_solver_*); the defaults leave the capsule as created -- SQP_RTI
         nlp = dict(nlp_solver_max_iter=nlp_solver_max_iter, nlp_solver_tol_stat=nlp_solver_tol_stat, nlp_solver_tol_eq=nlp_solver_tol_eq,
-                   nlp_solver_tol_ineq=nlp_solver_tol_ineq, nlp_solver_tol_comp=nlp_solver_tol_comp, nlp_solver_step_length=nlp_solver_step_length)
+                   nlp_solver_tol_ineq=nlp_solver_tol_ineq, nlp_solver_tol_comp=nlp_solver_tol_comp, nlp_solver_step_length=nlp_solver_step_length,
+                   alpha_min=alpha_min, alpha_reduction=alpha_reduction, merit_weight_eq=merit_weight_eq)
         for k, v in nlp.items():
             if v != _NLP_DEFAULTS[k]:
                 self.options_set(k, v)
+        if globalization != "FIXED_STEP":
+            self.options_set("globalization", globalization)
         if nlp_solver_type != "SQP_RTI":
             self.options_set("nlp_solver_type", nlp_solver_type)
 
@@ -321,11 +338,14 @@ class BatchedOcpSolver:
 
     def options_set(self, field, value):
         """acados_solver.options_set(field, value) for the NLP solver: 'nlp_solver_type' ('SQP_RTI' | 'SQP'), 'nlp_solver_max_iter',
-        'nlp_solver_tol_stat' | '_eq' | '_ineq' | '_comp', 'nlp_solver_step_length' (include/tum_nmpc.h, tum_ocp_options_set);
+        'nlp_solver_tol_stat' | '_eq' | '_ineq' | '_comp', 'nlp_solver_step_length', 'globalization' ('FIXED_STEP' | 'MERIT_BACKTRACKING')
+        with 'alpha_min', 'alpha_reduction' and 'merit_weight_eq' (include/tum_nmpc.h, tum_ocp_options_set);
         'rti_phase' 0 | 1 | 2: the following solve() calls are whole SQP-RTI steps (default), preparations or feedbacks;
         'lin_dedup' 1 | 0: linearise a stage-uniform iterate (after cold_start() / reset()) once per instance (default) or per stage"""
         if field == "rti_phase":
             value = _rti_phase_value(value)
+        if field == "globalization":
+            value = _globalization_value(value)
         if field == "nlp_solver_type" and isinstance(value, str):
             if value not in _NLP_TYPES:
                 raise Exception(f"BatchedOcpSolver.options_set: nlp_solver_type must be one of {sorted(_NLP_TYPES)}, got '{value}'")
@@ -350,6 +370,22 @@ class BatchedOcpSolver:
     def get_residuals(self):
         """acados_solver.get_residuals(): [stat, eq, ineq, comp] of the NLP at the iterate of the last SQP solve; (batch, 4) for a batch"""
         return self.get_stats("residuals")
+
+    def _merit_dims(self):
+        """(K, M) of the last solve: candidates of its line search, its nlp_solver_max_iter (refused unless it was MERIT_BACKTRACKING)"""
+        o = (ctypes.c_int * 2)()
+        self._chk(self._L.tum_ocp_get_stats(self._h, b"merit_dims", o, 0, 1), "get_stats")
+        return int(o[0]), int(o[1])
+
+    def get_alpha(self):
+        """step lengths the line search of the last SQP solve accepted (globalization MERIT_BACKTRACKING): (batch, max_iter), row b
+        holds those of its QPs 1 .. sqp_iter[b], then zeros"""
+        return self.get_stats("alpha")
+
+    def get_merit(self):
+        """(table, weights) of each instance's own last line search: table (batch, K + 1, 3) with the columns cost, E, V at the
+        candidates alpha_reduction^j, j < K, and in row K at alpha = 0; weights (batch, 2): mu_eq, mu_in"""
+        return self.get_stats("merit"), self.get_stats("merit_weights")
 
     def get_cost(self):
         out = np.zeros(self.batch)
@@ -378,6 +414,11 @@ class BatchedOcpSolver:
         if field == "residuals":
             out = np.zeros((self.batch, 4))
             self._chk(self._L.tum_ocp_get_stats(self._h, b"residuals", out.ctypes.data_as(ctypes.c_void_p), 0, self.batch), "get_stats")
+            return self._out(out)
+        if field in ("alpha", "merit", "merit_weights"):
+            K, M = self._merit_dims()
+            out = np.zeros({"alpha": (self.batch, M), "merit": (self.batch, K + 1, 3), "merit_weights": (self.batch, 2)}[field])
+            self._chk(self._L.tum_ocp_get_stats(self._h, field.encode(), out.ctypes.data_as(ctypes.c_void_p), 0, self.batch), "get_stats")
             return self._out(out)
         raise Exception(f"BatchedOcpSolver.get_stats: unknown field '{field}'")
 
