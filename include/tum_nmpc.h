@@ -200,7 +200,15 @@ int tum_ocp_solve_async(tum_ocp *c);
  *                          coupled SNMPC OCP, not in the device closed loop (tum_sim_run captures and replays its steps). A caller who
  *                          captures solves into a graph of their own captures the cold_start() with them, or sets 0. The fill kernel compares every stage with stage 0: should the
  *                          library ever take the path on a non-uniform iterate, every synchronous call fails and says so until the next
- *                          cold_start() / reset(), which re-initialise the iterate and re-arm the check. */
+ *                          cold_start() / reset(), which re-initialise the iterate and re-arm the check.
+ * "uniform_records"        0 (default): a solve on the "lin_dedup" path does not materialise the stage records where nothing reads them:
+ *                          the condensing and the expansion form their operands from the once-per-instance linearisation and the
+ *                          reference (cond_uniform_kernel, expand_uniform_kernel; lin_fill_kernel is not launched, and the expansion
+ *                          holds the check of every stage against stage 0). Taken by a whole SQP-RTI step (rti_phase 0) of the nominal
+ *                          OCP with a diagonal W, created without store_qp_in, at batch sizes where the condensing runs one wavefront
+ *                          per OCP and the expansion is a kernel of its own (more than 1024 instances), without the debug dump or the
+ *                          phase timers; every other solve fills the records as before. Results are bit-identical either way.
+ *                          1: always fill the records (A/B runs, tests). */
 int tum_ocp_options_set(tum_ocp *c, const char *field, double value);
 int tum_ocp_synchronize(tum_ocp *c);
 
@@ -219,7 +227,8 @@ int tum_ocp_get_cost(tum_ocp *c, double *out, int b0, int nb);
  * "merit" -> nb x (K + 1) x 3 doubles: cost, E, V of the instance's own LAST line search at the candidates j = 0 .. K - 1 and, in row K,
  *   at alpha = 0 (zeros for an instance that never searched)
  * "merit_weights" -> nb x 2 doubles: mu_eq, mu_in
- * "lin_uniform" -> 1 int: linearisations of this capsule that took the uniform path (options_set "lin_dedup") since it was created. */
+ * "lin_uniform" -> 1 int: linearisations of this capsule that took the uniform path (options_set "lin_dedup") since it was created.
+ * "records_skipped" -> 1 int: solves of this capsule that ran without stage records (options_set "uniform_records") since it was created. */
 int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b0, int nb);
 /* acados_solver.reset()   NMPC_class.py:251 -- zero the iterate of every instance */
 int tum_ocp_reset(tum_ocp *c);

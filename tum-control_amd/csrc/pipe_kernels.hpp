@@ -470,9 +470,15 @@ __device__ __forceinline__ void apply_A_rows(const RecRows &R, double w[8], doub
 // iterate U | packed gg rows (staging for the operand layout)
 // REGF: the register form of the stage record (RecRows); the LDS form is kept for the coupled SNMPC OCP at long propagation horizons
 // (the host decides, tum_nmpc.hip: launch_pipeline)
-template <int NT_, bool SN, bool REGF = !SN>
-__global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArgs pa)
+// UNI (register form of the nominal OCP only): a STAGE-UNIFORM iterate condensed without stage records (cond_uniform_kernel below).
+// What lin_fill_kernel would write into the N + 1 records is formed here, by its operations on its operands: the fields 0..51 and
+// 56..60 of a stage slot are the same at every stage -- Sp, S from lin1, the defect lin1[44 + i] - X_0[i], the gg row, X_0[6] -- and
+// are formed ONCE, in one register set that the even and the odd stages share; only the four residual lanes of the fourth register
+// change with the stage: X_0[r] - yref_{k+1}[r] (the yaw wrapped, once), one 8-byte load per lane and stage, two stages ahead.
+template <int NT_, bool SN, bool REGF, bool UNI>
+__device__ __forceinline__ void cond_instance(const PArgs &pa, const double *lin1)
 {
+    static_assert(!UNI || (REGF && !SN), "the record-free form exists for the register form of the nominal OCP");
     PD_LOCALS
     constexpr int C_REC = D::C_REC, C_STAGE = D::C_STAGE, C_GS = D::C_GS, C_U0 = D::C_U0, C_WT = D::C_WT;
     __shared__ __attribute__((aligned(16))) double lds[D::C_LDS];
@@ -483,6 +489,7 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
     const double dt = ka.dt;
     double *sRec = lds + C_REC, *sStage = lds + C_STAGE, *sGs = lds + C_GS, *sU0 = lds + C_U0, *sWt = lds + C_WT;
     const double *grec = pa.rec + (size_t)b * (N + 1) * PREC;
+    const double *lin1b = UNI ? lin1 + (size_t)b * LIN1 : nullptr;
     const double *gx0 = ka.x0 + (size_t)b * NX;
     const double *gX = ka.X + (size_t)b * (N + 1) * NX;
     const double *gU = ka.U + (size_t)b * N * NU;
@@ -523,11 +530,31 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
     double bcol[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     auto fetch_bcol = [&](int j) {
 #pragma unroll
-        for (int i = 0; i < 6; i++) bcol[i] = (j < N) ? grec[(size_t)j * PREC + 2 + i * 7 + 5 + (lane & 1)] : 0.0;
+        for (int i = 0; i < 6; i++) {
+            // (record-free form: B_j is the same for every j < N -- fetched once; bank 1 only masks what it holds. Its stages exist for N > 32 only, where every lane of bank 0 held a column)
+            if constexpr (UNI) bcol[i] = (j < N) ? ((j < 32) ? lin1b[2 + i * 7 + 5 + (lane & 1)] : bcol[i]) : 0.0;
+            else bcol[i] = (j < N) ? grec[(size_t)j * PREC + 2 + i * 7 + 5 + (lane & 1)] : 0.0;
+        }
     };
     const double notg63 = (lane == 63) ? 0.0 : 1.0;
     const double b6c = (lane & 1) ? dt : 0.0, b7c = (lane & 1) ? 0.0 : dt;          // (rows 6, 7 of that column: the integrators of the two inputs)
-    if constexpr (REGF) {
+    // record-free form: the residual lanes of the fourth register (fields 52..55), what they subtract the reference from, and the
+    // reference two stages ahead (one value for the even stages, one for the odd ones, as the register sets of the record form)
+    const bool ures = UNI && (lane & 12) == 4;
+    double uxr = 0.0, uy[2] = {0.0, 0.0};
+    const double *uyp = gyref + (ures ? (lane & 3) : 0);
+    if constexpr (UNI) {
+        const int p_ = lane & 15;
+        const double x2w = wrap_yaw(gX[2]);
+        uxr = ((lane & 3) == 2) ? x2w : gX[lane & 3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) Ra.g[r] = (16 * r + p_ < L1_XN) ? lin1b[16 * r + p_] : lin1b[L1_XN + (p_ & 3)] - gX[p_ & 3];          // (the defect's fields 44..47: lanes 12..15 of the third register)
+        // fields 48..51 the defect | 52..55 the residuals of stage 1 | 56..59 the gg row | 60 delta_f | 61..63 not in use
+        Ra.g[3] = (p_ < 4) ? lin1b[L1_XN + 4 + (p_ & 3)] - gX[4 + (p_ & 3)] : ures ? uxr - uyp[6] : (p_ < 12) ? lin1b[L1_GH + (p_ & 3)] : (p_ == 12) ? gX[6] : 0.0;
+        if (2 <= N) uy[0] = uyp[2 * 6];          // (stage slot 1, taken behind stage 0)
+        if (3 <= N) uy[1] = uyp[3 * 6];
+        fetch_bcol(lane >> 1);
+    } else if constexpr (REGF) {
         fetch_rows(0, Ra);
         if (N > 1) fetch_rows(1, Rb); else Rb = Ra;
         fetch_bcol(lane >> 1);
@@ -593,7 +620,7 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
         constexpr bool PRO_AHEAD = SN && !REGF;
         if constexpr (PRO_AHEAD) { if (uph > 0) fetch_pro(0, lane); }
         // (two call sites per segment: inlined by force, or every captured array lives in scratch)
-        auto stage_body = [&](const int k, auto tsc, auto g0c, RecRows &R) __attribute__((always_inline)) {
+        auto stage_body = [&](const int k, auto tsc, auto g0c, RecRows &R, double &uyq) __attribute__((always_inline)) {
             constexpr int Ts = decltype(tsc)::value;
             // G0: the constant column rides on lane 63 of bank 0 and bank 1 is not issued. LATE: ... in a segment whose tiles reach
             // column 63 (the register form keeps g there through stage 31, whose input column is the first to need the lane): what
@@ -788,7 +815,12 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
                     Ht[tidx(K, I)] = mfma(aop, bop[I], Ht[tidx(K, I)]);
                 }
             }
-            if constexpr (REGF) {
+            if constexpr (UNI) {
+                // the residuals of the next stage slot (record k + 2) onto their four lanes, the reference of the slot two on behind them: a plain
+                // vector write of a DPP operand -- R.settle() at the top of the next stage stands between it and the first read
+                if (k + 1 < N) R.g[3] = ures ? uxr - uyq : R.g[3];
+                if (k + 3 < N) uyq = uyp[(size_t)(k + 4) * 6];
+            } else if constexpr (REGF) {
                 // the record two stages on, into the register set this stage is done with
                 if (k + 2 < N) fetch_rows(k + 2, R);
             } else {
@@ -799,6 +831,7 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
             wsync();
         };
         // stage s = k+1 touches columns < 2s, i.e. ceil(s/8) tiles: one instantiation of the stage per segment of 8 stages
+        RecRows &Ro = UNI ? Ra : Rb;          // (record-free form: one register set for the even and the odd stages)
         static_for<1, NT>([&](auto tsc) {
             constexpr int Ts = decltype(tsc)::value;
             constexpr bool G0S = Ts <= G0_SEGS;
@@ -813,22 +846,22 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
                 // without bank 1 (its column update, gg row, staging stores and gradient terms: ~60 of ~150 vector instructions a stage)
                 constexpr int kl = 8 * Ts - 1;          // the stage that needs the lane
                 for (int k = 8 * (Ts - 1); k < N && k < kl - 1; k += 2) {
-                    stage_body(k, tsc, yes(), Ra);
-                    if (k + 1 < N) stage_body(k + 1, tsc, yes(), Rb);
+                    stage_body(k, tsc, yes(), Ra, uy[0]);
+                    if (k + 1 < N) stage_body(k + 1, tsc, yes(), Ro, uy[1]);
                 }
-                if (kl - 1 < N) stage_body(kl - 1, tsc, yes(), Ra);
+                if (kl - 1 < N) stage_body(kl - 1, tsc, yes(), Ra, uy[0]);
                 move_g();
-                if (kl < N) stage_body(kl, tsc, no(), Rb);
+                if (kl < N) stage_body(kl, tsc, no(), Ro, uy[1]);
             } else {
                 if constexpr (G0_SEGS > 0 && Ts == G0_SEGS + 1) move_g();
                 if constexpr (REGF) {
                     if constexpr (Ts == 5) fetch_bcol(32 + (lane >> 1));          // (bank 1's input columns: the stages from 32 on)
                     for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k += 2) {
-                        stage_body(k, tsc, std::integral_constant<bool, G0S>(), Ra);
-                        if (k + 1 < N) stage_body(k + 1, tsc, std::integral_constant<bool, G0S>(), Rb);
+                        stage_body(k, tsc, std::integral_constant<bool, G0S>(), Ra, uy[0]);
+                        if (k + 1 < N) stage_body(k + 1, tsc, std::integral_constant<bool, G0S>(), Ro, uy[1]);
                     }
                 } else {
-                    for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k++) stage_body(k, tsc, std::integral_constant<bool, G0S>(), Ra);
+                    for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k++) stage_body(k, tsc, std::integral_constant<bool, G0S>(), Ra, uy[0]);
                 }
             }
         });
@@ -871,6 +904,19 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
         gvec[PV_Q + lane] = q0;
         if (lane < NB1) gvec[PV_Q + 64 + lane] = q1;
     }
+}
+
+template <int NT_, bool SN, bool REGF = !SN>
+__global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArgs pa)
+{
+    cond_instance<NT_, SN, REGF, false>(pa, nullptr);
+}
+// K2 of a stage-uniform iterate: reads lin1 (lin_uniform_kernel) and the reference instead of stage records, which are not written
+// (tum_nmpc.hip: launch_pipeline decides); H, C, q, d as cond_kernel<NT_, false, true> hands them over, to the bit
+template <int NT_>
+__global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_kernel(const PArgs pa, const double *lin1)
+{
+    cond_instance<NT_, false, true, true>(pa, lin1);
 }
 
 // ---- K2 for small batches: six (N <= 40) or seven wavefronts per OCP.
@@ -1223,9 +1269,13 @@ __global__ void __launch_bounds__(64 * cw_waves<NT_>()) cond_wide_kernel(const P
 // The expansion of ONE instance by one wavefront: dx recursion, full step, cost at the new iterate. `lds` holds PD::E_LDS doubles;
 // FUSED: the caller (the tail of ipm_kernel) has put the step of the inputs into lds[E_DV ..] and passes status / slack cost in
 // registers; otherwise both come from the workspace the interior point kernel wrote.
-template <int NT_, bool SN, bool FUSED>
-__device__ __forceinline__ void expand_instance(const PArgs &pa, const int b, double *lds, int status, double slack_cost)
+// UNI: a STAGE-UNIFORM old iterate expanded without stage records (expand_uniform_kernel below): A_k, B_k are the same at every stage and
+// the defect is xn - X_0 (the OLD X_0), so a lane keeps its row of lin1 in registers and the recursion runs without a load in the loop.
+template <int NT_, bool SN, bool FUSED, bool UNI = false>
+__device__ __forceinline__ void expand_instance(const PArgs &pa, const int b, double *lds, int status, double slack_cost,
+                                                const double *lin1 = nullptr, int *bad = nullptr)
 {
+    static_assert(!UNI || (!SN && !FUSED), "the record-free form exists for the expansion kernel of the nominal OCP");
     PD_LOCALS
     constexpr int E_REC = D::E_REC, E_X = D::E_X, E_U = D::E_U, E_DV = D::E_DV;
     const KArgs &ka = pa.ka;
@@ -1251,18 +1301,57 @@ __device__ __forceinline__ void expand_instance(const PArgs &pa, const int b, do
     // as the tail of the interior point kernel)
     constexpr int EX_AHEAD = 8;
     double pre[EX_AHEAD];
+    // record-free form: row ri of A, B and of xn, loaded once (the selects of the stage loop below, on the fields a record would hold)
+    double ucpsi = 0.0, uc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, uxn = 0.0, udv0 = 0.0, udv1 = 0.0;
+    if constexpr (UNI) {
+        const int ri = (lane < 8) ? lane : 0;
+        const double *l1 = lin1 + (size_t)b * LIN1, *Si = l1 + 2 + ((ri < 6) ? ri : 0) * 7;
+        ucpsi = (ri < 2) ? l1[ri] : 0.0;
+#pragma unroll
+        for (int c = 0; c < 7; c++) uc[c] = Si[c];
+        if (ri >= 6) { uc[0] = uc[1] = uc[2] = uc[3] = uc[4] = 0.0; uc[5] = (ri == 7) ? dt : 0.0; uc[6] = (ri == 6) ? dt : 0.0; }
+        uxn = l1[L1_XN + ri];
+        udv0 = gvec[PV_DV + lane]; udv1 = (lane < NB1) ? gvec[PV_DV + 64 + lane] : 0.0;          // (the step of the inputs, read by lane index in the loop)
+    } else {
     sRec[lane] = (lane < PR_RES) ? grec[lane] : 0.0;
 #pragma unroll
     for (int j = 0; j < EX_AHEAD; j++) pre[j] = (lane < PR_RES && 1 + j <= N) ? grec[(size_t)(1 + j) * PREC + lane] : 0.0;          // records 1 .. EX_AHEAD
+    }
     const double gx0r = gx0[(lane < 8) ? lane : 0];
     wsync();
+    if constexpr (UNI) {
+        // the safety net lin_fill_kernel holds where records are written: the whole old iterate is here, every stage against stage 0 bit for bit
+        bool differs = false;
+        for (int i = lane; i < (N + 1) * NX; i += 64) differs |= __double_as_longlong(sX[i]) != __double_as_longlong(sX[i & (NX - 1)]);
+        for (int i = lane; i < nv; i += 64) differs |= __double_as_longlong(sU1[i]) != __double_as_longlong(sU1[i & (NU - 1)]);
+        if (differs) *bad = 1;
+    }
     if (status == 0) {
         const int ri = (lane < 8) ? lane : 0;
         const bool core = ri < 6;
         const double diag = (ri < 3 || ri >= 6) ? 1.0 : 0.0;
         double dxi = gx0r - sX[ri];
+        const double ubi = UNI ? uxn - sX[ri] : 0.0;          // (record-free form: xn - X_{k+1} of the OLD iterate, the same at every stage)
         wsync();
         if (lane < 8) sX[lane] += dxi;
+        if constexpr (UNI) {
+            // each lane below 8 touches its own slots of sX only: no exchange through LDS, no barrier in the loop
+            for (int k = 0; k < N; k++) {
+                const double du0 = (k < 32) ? rl(udv0, (2 * k) & 63) : rl(udv1, (2 * k) & 63), du1 = (k < 32) ? rl(udv0, (2 * k + 1) & 63) : rl(udv1, (2 * k + 1) & 63);
+                const double cpsi = ucpsi, c0 = uc[0], c1 = uc[1], c2 = uc[2], c3 = uc[3], c4 = uc[4], c5 = uc[5], c6 = uc[6], bi = ubi;
+                const double x2 = rl(dxi, 2), x3 = rl(dxi, 3), x4 = rl(dxi, 4), x5 = rl(dxi, 5), x6 = rl(dxi, 6), x7 = rl(dxi, 7);
+                // the record form's expression (below) AS THE COMPILER CONTRACTS IT THERE, spelled out: cpsi x2 and c5 du0 are rounded, every other
+                // product is fused onto the sum in front of it. Left to the compiler, the same source came out with c6 du1 rounded and c5 du0 fused
+                // here (du0, du1 are scalar operands in this form) -- one ulp on X
+                double acc0 = __builtin_fma(diag, dxi, cpsi * x2) + bi;
+                double acc1 = __builtin_fma(c6, du1, c5 * du0);
+                acc0 = __builtin_fma(c0, x3, acc0); acc1 = __builtin_fma(c1, x4, acc1);
+                acc0 = __builtin_fma(c2, x5, acc0); acc1 = __builtin_fma(c3, x6, acc1);
+                acc0 = __builtin_fma(c4, x7, acc0);
+                dxi = acc0 + acc1;
+                if (lane < 8) sX[(k + 1) * NX + lane] += dxi;
+            }
+        } else {
         if (SN && uph > 0) {
             // stages 1..uph of the nominal copy have been stepped by the epilogue kernel (PCE mean of the stepped sample copies),
             // which runs in front of this one; the recursion continues from its step of stage uph
@@ -1293,6 +1382,7 @@ __device__ __forceinline__ void expand_instance(const PArgs &pa, const int b, do
             sRec[((k + 1) & 1) * PREC + lane] = pre[j];          // record k + 1 (requested EX_AHEAD stages ago)
             if (k + 1 + EX_AHEAD < N) pre[j] = (lane < PR_RES) ? grec[(size_t)(k + 1 + EX_AHEAD) * PREC + lane] : 0.0;
             wsync();
+        }
         }
         sU1[lane] += sDv[lane];
         if (lane < NB1) sU1[64 + lane] += sDv[64 + lane];
@@ -1343,6 +1433,17 @@ __global__ void __launch_bounds__(64) expand_kernel(const PArgs pa)
     const int b = blockIdx.x;
     if (b >= pa.ka.batch) return;
     expand_instance<NT_, SN, false>(pa, b, lds, 0, 0.0);
+}
+// K4 behind cond_uniform_kernel: the old iterate is the same at every stage (checked here, *bad as lin_fill_kernel sets it) and no
+// records exist; the new iterate and the cost as expand_kernel<NT_, false> writes them, to the bit
+template <int NT_>
+__global__ void __launch_bounds__(64) expand_uniform_kernel(const PArgs pa, const double *lin1, int *bad)
+{
+    using D = PD<NT_>;
+    __shared__ __attribute__((aligned(16))) double lds[D::E_LDS];
+    const int b = blockIdx.x;
+    if (b >= pa.ka.batch) return;
+    expand_instance<NT_, false, false, true>(pa, b, lds, 0, 0.0, lin1, bad);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- K3

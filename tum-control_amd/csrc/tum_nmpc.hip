@@ -118,6 +118,10 @@ struct tum_ocp {
     // stage 0 -- an invalidation missed here; checked at the synchronous entry points (lin_uniform_check).
     // capturing: tum_sim_run is recording a chunk of the closed loop into a graph (a captured launch is replayed on other iterates)
     bool iter_uniform = false, capturing = false; int lin_dedup = 1; int n_lin_uniform = 0; double *dlin1 = nullptr; int *hlin_bad = nullptr;
+    // uniform_records: options_set "uniform_records", 0 by default -- a whole SQP-RTI step on a stage-uniform iterate writes NO stage
+    // records where nothing behind it reads them (launch_pipeline: cond_uniform_kernel and expand_uniform_kernel take lin1 and the
+    // reference; the expansion holds the safety net then); 1: lin_fill_kernel always. n_records_skipped: get_stats "records_skipped"
+    int uniform_records = 0; int n_records_skipped = 0;
 };
 
 // cold_start() / reset() re-initialise the iterate: a capsule the safety net has failed works again from there. The word may only be
@@ -1092,6 +1096,19 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, int part)
     const bool cols = use_lin_cols(c);
     const dim3 g_cols((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), g_lane((unsigned)((items + 63) / 64));
     const bool lin_done = c->lin_ahead;
+    // The expansion as the tail of the interior point kernel pays where a batch is at most one round of resident wavefronts (one
+    // launch less: 0.424 against 0.432 ms per solve() call at 26 instances, 0.457 against 0.469 at 1024); beyond that its
+    // loads run at the interior point kernel's occupancy -- one wavefront per SIMD, four OCPs per CU -- and hold that slot:
+    // 3.72 against 3.96 M solves/s on config 2 (three streams). TUM_FUSED_EXPAND=0 / 1 forces it off / on (development aid).
+    static const int fuse_env = env_int("TUM_FUSED_EXPAND", -1);
+    const bool no_fuse = fuse_env == 0 || (fuse_env < 0 && c->batch > 1024);
+    // The record-free path of a stage-uniform iterate: lin_uniform_kernel, cond_uniform_kernel, ipm_kernel, expand_uniform_kernel -- drec is
+    // not written. Taken for a whole SQP-RTI step of the nominal OCP (diagonal W) on the pipeline kernels, with the expansion a kernel of its
+    // own and one wavefront per OCP in the condensing. Everyone else who reads drec -- nlp_residual_kernel (SQP), rti_feedback_kernel (the split
+    // iteration), the fused tail of ipm_kernel, cond_wide_kernel, and behind a solve get_from_qp_in and the R2 back-off (store_qp_in) -- is
+    // reached only where one of these conditions is false.
+    const bool no_records = !lin_done && !cols && use_lin_uniform(c) && part == 3 && !c->uniform_records && c->nlp_type == 0 && !c->sn && !c->dWf &&
+                            !c->d.store_qp_in && !(c->ka.flags & 6) && no_fuse && !use_cond_wide(c) && c->kmode != 3;
     if (part & 1) {
     c->lin_ahead = false;
     if (lin_done) pa.ka.flags |= 8;          // (launch_lin_ahead ran it on another stream; the caller has joined that stream)
@@ -1106,19 +1123,14 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, int part)
         else if (use_lin_uniform(c)) {
             // a stage-uniform iterate (cold_start(), reset()): the Runge-Kutta pass once per instance, then the records of every stage
             hipLaunchKernelGGL(lin_uniform_kernel, dim3((unsigned)((c->batch + 63) / 64)), dim3(64), 0, c->stream, pa, c->dlin1);
-            hipLaunchKernelGGL(lin_fill_kernel, dim3((unsigned)((c->batch + LF_WAVES - 1) / LF_WAVES)), dim3(64 * LF_WAVES), 0, c->stream, pa, c->dlin1, c->hlin_bad);
+            if (!no_records) hipLaunchKernelGGL(lin_fill_kernel, dim3((unsigned)((c->batch + LF_WAVES - 1) / LF_WAVES)), dim3(64 * LF_WAVES), 0, c->stream, pa, c->dlin1, c->hlin_bad);
             c->n_lin_uniform++;
+            if (no_records) c->n_records_skipped++;
         }
         else hipLaunchKernelGGL(lin_kernel<false>, g_lane, dim3(64), 0, c->stream, pa);
     }
     }
     // (development aid: a larger LDS request lowers the number of OCPs that share a CU)
-    // The expansion as the tail of the interior point kernel pays where a batch is at most one round of resident wavefronts (one
-    // launch less: 0.424 against 0.432 ms per solve() call at 26 instances, 0.457 against 0.469 at 1024); beyond that its
-    // loads run at the interior point kernel's occupancy -- one wavefront per SIMD, four OCPs per CU -- and hold that slot:
-    // 3.72 against 3.96 M solves/s on config 2 (three streams). TUM_FUSED_EXPAND=0 / 1 forces it off / on (development aid).
-    static const int fuse_env = env_int("TUM_FUSED_EXPAND", -1);
-    const bool no_fuse = fuse_env == 0 || (fuse_env < 0 && c->batch > 1024);
     static const int lds_req = [] { const int v = env_int("TUM_IPM_LDS", 0); return (v > 0 && v <= 64 * 1024) ? v : 0; }();
     with_tiles(c, [&](auto ntc) {
         constexpr int NTv = decltype(ntc)::value;
@@ -1137,6 +1149,7 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, int part)
                 // (coupled SNMPC: the register form of the stage record pays behind stage uph and costs in front of it, pipe_kernels.hpp)
                 if (c->sn && 2 * c->sa.uph <= c->N) hipLaunchKernelGGL((cond_kernel<NTv, true, true>), dim3(c->batch), dim3(64), 0, c->stream, pa);
                 else if (c->sn) hipLaunchKernelGGL((cond_kernel<NTv, true, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
+                else if (no_records) hipLaunchKernelGGL((cond_uniform_kernel<NTv>), dim3(c->batch), dim3(64), 0, c->stream, pa, c->dlin1);
                 else hipLaunchKernelGGL((cond_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
             }
         }
@@ -1171,7 +1184,8 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, int part)
             else hipLaunchKernelGGL((snmpc_epilogue_kernel<>), dim3(c->batch), dim3(64), 0, c->stream, sa);
             c->xs_lazy = true;
             hipLaunchKernelGGL((expand_kernel<NTv, true>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-        } else if (!expanded) hipLaunchKernelGGL((expand_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
+        } else if (no_records) hipLaunchKernelGGL((expand_uniform_kernel<NTv>), dim3(c->batch), dim3(64), 0, c->stream, pa, c->dlin1, c->hlin_bad);
+        else if (!expanded) hipLaunchKernelGGL((expand_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
     });
     return 0;
 }
@@ -1368,7 +1382,12 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
         c->lin_dedup = (int)value;
         return 0;
     }
-    return fail("options_set: unknown field '" + f + "' (lin_dedup | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
+    if (f == "uniform_records") {      // 0: a stage-uniform iterate is condensed and expanded without stage records where nothing else reads them (default); 1: lin_fill_kernel always
+        if (value != 0.0 && value != 1.0) return fail("options_set uniform_records: 0 or 1");
+        c->uniform_records = (int)value;
+        return 0;
+    }
+    return fail("options_set: unknown field '" + f + "' (lin_dedup | uniform_records | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
                 "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length | rti_phase), of the SQP globalization (globalization | "
                 "alpha_min | alpha_reduction | merit_weight_eq)");
 }
@@ -1619,6 +1638,7 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
         if (hipEventSynchronize(c->evi1) != hipSuccess || hipEventElapsedTime(&ms, c->evi0, c->evi1) != hipSuccess) return fail("get_stats time_ipm: no timing");
         *(double *)out = ms * 1e-3; return 0;
     }
+    if (f == "records_skipped") { *(int *)out = c->n_records_skipped; return 0; }      // solves that ran without stage records (one int)
     if (f == "lin_uniform") { *(int *)out = c->n_lin_uniform; return 0; }      // linearisations that took the uniform path (one int)
     if (chk_range(c, b0, nb)) return 1;
     if (f == "sqp_iter" && !c->solved_sqp) { int *o = (int *)out; for (int i = 0; i < nb; i++) o[i] = 1; return 0; }      // (SQP-RTI: one QP per solve)

@@ -341,7 +341,8 @@ class BatchedOcpSolver:
         'nlp_solver_tol_stat' | '_eq' | '_ineq' | '_comp', 'nlp_solver_step_length', 'globalization' ('FIXED_STEP' | 'MERIT_BACKTRACKING')
         with 'alpha_min', 'alpha_reduction' and 'merit_weight_eq' (include/tum_nmpc.h, tum_ocp_options_set);
         'rti_phase' 0 | 1 | 2: the following solve() calls are whole SQP-RTI steps (default), preparations or feedbacks;
-        'lin_dedup' 1 | 0: linearise a stage-uniform iterate (after cold_start() / reset()) once per instance (default) or per stage"""
+        'lin_dedup' 1 | 0: linearise a stage-uniform iterate (after cold_start() / reset()) once per instance (default) or per stage;
+        'uniform_records' 0 | 1: such a solve writes no stage records where nothing reads them (default), or always fills them"""
         if field == "rti_phase":
             value = _rti_phase_value(value)
         if field == "globalization":
@@ -403,7 +404,7 @@ class BatchedOcpSolver:
             if field == "sqp_iter" and self.batch == 1:
                 return int(out[0])
             return out            # acados returns an array for qp_iter; callers take np.max
-        if field == "lin_uniform":      # linearisations that took the uniform path (options_set('lin_dedup', 0 | 1))
+        if field in ("lin_uniform", "records_skipped"):      # linearisations that took the uniform path (options_set('lin_dedup', 0 | 1)); solves without stage records ('uniform_records')
             o = ctypes.c_int(0)
             self._chk(self._L.tum_ocp_get_stats(self._h, field.encode(), ctypes.byref(o), 0, 1), "get_stats")
             return o.value
