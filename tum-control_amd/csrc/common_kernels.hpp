@@ -5,7 +5,7 @@
 
 namespace tum {
 
-// optional in-kernel phase timers (flags & 4): cycles per phase accumulated into ka.prof[b][12]
+// optional in-kernel phase timers (KF_PROF): cycles per phase accumulated into ka.prof[b][12]
 #define TUM_TICK(slot) do { asm volatile("; TUM_MARK " #slot); if (PROF) { const long long t_ = __builtin_readcyclecounter(); pacc[slot] += t_ - tprev; tprev = t_; } } while (0)
 
 __device__ __forceinline__ int acados_status(int qp_status) { return (qp_status == 0 || qp_status == 1) ? 0 : 4; }

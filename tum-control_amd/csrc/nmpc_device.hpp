@@ -95,8 +95,14 @@ struct Model {
     double ggv_v[16], ggv_ax[16], ggv_ay[16];
 };
 
+// bits of KArgs::flags
+constexpr int KF_STORE_QP_IN = 1;           // the fused kernel writes A | B | b of every stage to qpin
+constexpr int KF_DEBUG = 2;                 // debug dump of the condensed QP (instrumented instantiations)
+constexpr int KF_PROF = 4;                  // in-kernel phase timers (instrumented instantiations)
+constexpr int KF_LIN_AHEAD = 8;             // the linearisation ran beside the planner: the residuals of the cost are cond_wide_kernel's to form
+
 struct KArgs {
-    int N, nsub, batch, flags;                        // flags: 1 store_qp_in, 2 debug dump, 4 phase timers
+    int N, nsub, batch, flags;                        // flags: KF_* below
     double dt;
     int iter_max;
     double tol_stat, tol_ineq, tol_comp, mu0, t0, reg;
@@ -106,9 +112,9 @@ struct KArgs {
     double *cost, *res, *slack;                       // [b], [b][3], [b][6N]
     int *status, *qp_iter, *qp_status;                // [b]
     double *qpin;                                     // [b][N][88]  (A 64 | B 16 | b 8), row-major
-    double *dbg;                                      // debug dump, instance 0.. (flags&2)
+    double *dbg;                                      // debug dump, instance 0.. (KF_DEBUG)
     int dbg_stride;
-    long long *prof;                                  // [b][12] phase cycle counters (flags&4)
+    long long *prof;                                  // [b][12] phase cycle counters (KF_PROF)
     double *ws;                                       // [b][WS_DOUBLES] linearisation records parked during the IPM
     const int *order;                                 // [batch] workgroup -> instance map (longest-first schedule) or null
     // coupled SNMPC OCP only (nmpc_rti_kernel<., true>, snmpc_kernels.hpp)

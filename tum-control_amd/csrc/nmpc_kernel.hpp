@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(64, 1) nmpc_rti_kernel(const KArgs ka)
                     for (int c = 0; c < 7; c++) rec[2 + i * 7 + c] = S[i][c];
 #pragma unroll
                 for (int i = 0; i < 8; i++) rec[44 + i] = xn[i] - sX[(k + 1) * NX + i];
-                if (ka.flags & 1) {   // full A (8x8), B (8x2), b (8) of this linearisation, row-major
+                if (ka.flags & KF_STORE_QP_IN) {   // full A (8x8), B (8x2), b (8) of this linearisation, row-major
                     double *q = ka.qpin + ((size_t)b * N + k) * 88;
                     for (int i = 0; i < 64; i++) q[i] = 0.0;
                     q[0 * 8 + 0] = 1.0; q[1 * 8 + 1] = 1.0; q[2 * 8 + 2] = 1.0; q[6 * 8 + 6] = 1.0; q[7 * 8 + 7] = 1.0;
@@ -329,7 +329,7 @@ __global__ void __launch_bounds__(64, 1) nmpc_rti_kernel(const KArgs ka)
     }
     }   // Wd, We
 
-    if (PROF && (ka.flags & 2) && b < 4) {   // debug dump of the condensed QP
+    if (PROF && (ka.flags & KF_DEBUG) && b < 4) {   // debug dump of the condensed QP
         double *dbg = ka.dbg + (size_t)b * ka.dbg_stride;
 #pragma unroll
         for (int K = 0; K < NT; K++)
@@ -524,7 +524,7 @@ __global__ void __launch_bounds__(64, 1) nmpc_rti_kernel(const KArgs ka)
                 }
         }
         wsync();
-        if (PROF && (ka.flags & 2) && b < 4 && it == 0) {
+        if (PROF && (ka.flags & KF_DEBUG) && b < 4 && it == 0) {
             double *dbg = ka.dbg + (size_t)b * ka.dbg_stride;
             for (int i = lane; i < LPK; i += 64) dbg[13300 + i] = sM[i];
         }
@@ -627,7 +627,7 @@ __global__ void __launch_bounds__(64, 1) nmpc_rti_kernel(const KArgs ka)
             }
         }
         if (!(dmin > 1e-300)) { qp_status = 3; break; }
-        if (PROF && (ka.flags & 2) && b < 4 && it == 0) {
+        if (PROF && (ka.flags & KF_DEBUG) && b < 4 && it == 0) {
             double *dbg = ka.dbg + (size_t)b * ka.dbg_stride;
             for (int i = lane; i < LPK; i += 64) dbg[16540 + i] = sM[i];
         }
@@ -702,7 +702,7 @@ __global__ void __launch_bounds__(64, 1) nmpc_rti_kernel(const KArgs ka)
             double b0, b1;
             ctw(b0, b1);
             b0 = v0on ? -rv0 - b0 : 0.0; b1 = v1on ? -rv1 - b1 : 0.0;
-            if (PROF && (ka.flags & 2) && b < 4 && it == 0 && pass == 0) {
+            if (PROF && (ka.flags & KF_DEBUG) && b < 4 && it == 0 && pass == 0) {
                 double *dbg = ka.dbg + (size_t)b * ka.dbg_stride;
                 dbg[19780 + lane] = b0;
                 if (lane < 16) dbg[19780 + 64 + lane] = b1;
@@ -790,7 +790,7 @@ __global__ void __launch_bounds__(64, 1) nmpc_rti_kernel(const KArgs ka)
             sDv[lane] = dv0;
             if (lane < 16) sDv[64 + lane] = dv1;
             wsync();
-            if (PROF && (ka.flags & 2) && b < 4 && it == 0 && pass == 0) {
+            if (PROF && (ka.flags & KF_DEBUG) && b < 4 && it == 0 && pass == 0) {
                 double *dbg = ka.dbg + (size_t)b * ka.dbg_stride;
                 dbg[19860 + lane] = dv0;
                 if (lane < 16) dbg[19860 + 64 + lane] = dv1;

@@ -22,6 +22,7 @@
 #pragma once
 #include "common_kernels.hpp"
 #include "snmpc_kernels.hpp"
+#include "pipe_plan.hpp"
 
 // wavefronts per SIMD the interior point kernel is bounded to (1: the whole register file; 2: an experiment build, HISTORY.md (round-4 document, section 7))
 
@@ -190,8 +191,8 @@ __global__ void __launch_bounds__(64, 1) lin_kernel(const PArgs pa)
 // The state recursion comes out bit-identical to lin_kernel's (b_k); the sensitivity columns agree to <= 3e-15 relative, not
 // to the bit: lin_kernel's column loop is unrolled with the column index known, so a factor 1.0 folds away and the product
 // behind it is contracted into an FMA there and not here (tests/test_gpu_parity.py::test_linearisation_eight_lanes_...).
-// Launched when batch x (N + 1) x 8 lanes still fit one round of the chip (tum_nmpc.hip: launch_pipeline).
-constexpr int LC_LANES = 8, LC_ITEMS = 64 / LC_LANES;
+// Launched when batch x (N + 1) x 8 lanes still fit one round of the chip (pipe_plan.hpp: plan_pipeline).
+constexpr int LC_ITEMS = 64 / LC_LANES;          // (LC_LANES: pipe_plan.hpp, the host decides by it)
 template <bool SN>
 __global__ void __launch_bounds__(64, 1) lin_cols_kernel(const PArgs pa)
 {
@@ -209,9 +210,9 @@ __global__ void __launch_bounds__(64, 1) lin_cols_kernel(const PArgs pa)
     double xk[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) xk[i] = gX[i];
-    // flags & 8 (the device closed loop, nominal OCP): this launch runs BESIDE the planner that writes yref for this solve -- the
+    // KF_LIN_AHEAD (the device closed loop, nominal OCP): this launch runs BESIDE the planner that writes yref for this solve -- the
     // residuals of the cost are left to cond_wide_kernel, which forms them while it loads the records, and yref is not touched
-    const bool late_res = !SN && (ka.flags & 8);
+    const bool late_res = !SN && (ka.flags & KF_LIN_AHEAD);
     const double *yr = ka.yref + ((size_t)b * NB + k) * 6;
     double *rw = sT + li * L_PITCH;
     // the fields outside the sensitivity block are computed by every lane of the group (same loads, same operations) and
@@ -469,7 +470,7 @@ __device__ __forceinline__ void apply_A_rows(const RecRows &R, double w[8], doub
 // LDS of the condensing kernel (PD::C_*): stage record double buffer | 4 staging rows of the SYRK | g_s of the current stage |
 // iterate U | packed gg rows (staging for the operand layout)
 // REGF: the register form of the stage record (RecRows); the LDS form is kept for the coupled SNMPC OCP at long propagation horizons
-// (the host decides, tum_nmpc.hip: launch_pipeline)
+// (the host decides, pipe_plan.hpp: plan_pipeline)
 // UNI (register form of the nominal OCP only): a STAGE-UNIFORM iterate condensed without stage records (cond_uniform_kernel below).
 // What lin_fill_kernel would write into the N + 1 records is formed here, by its operations on its operands: the fields 0..51 and
 // 56..60 of a stage slot are the same at every stage -- Sp, S from lin1, the defect lin1[44 + i] - X_0[i], the gg row, X_0[6] -- and
@@ -912,7 +913,7 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
     cond_instance<NT_, SN, REGF, false>(pa, nullptr);
 }
 // K2 of a stage-uniform iterate: reads lin1 (lin_uniform_kernel) and the reference instead of stage records, which are not written
-// (tum_nmpc.hip: launch_pipeline decides); H, C, q, d as cond_kernel<NT_, false, true> hands them over, to the bit
+// (pipe_plan.hpp: plan_pipeline decides); H, C, q, d as cond_kernel<NT_, false, true> hands them over, to the bit
 template <int NT_>
 __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_kernel(const PArgs pa, const double *lin1)
 {
@@ -933,7 +934,7 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_kernel(co
 //            the gradient q of the columns 0..63 / 64...
 // Tiles are dealt to the four wavefronts longest-first (tile (K, I) is touched by the 8 (NT - I) stages behind block column I).
 // The results are the ones cond_kernel writes, to the last bit (tests/test_gpu_parity.py::test_condensing_six_wavefronts_...).
-// Launched while the batch is at most one workgroup per CU (tum_nmpc.hip: launch_pipeline); the nominal OCP only.
+// Launched while the batch is at most one workgroup per CU (pipe_plan.hpp: plan_pipeline); the nominal OCP only.
 constexpr int CW_SYRK = 4;
 template <int NT_> constexpr int cw_waves() { return (4 * (PD<NT_>::NVP + 1) + 63) / 64 > CW_SYRK + 2 ? (4 * (PD<NT_>::NVP + 1) + 63) / 64 : CW_SYRK + 2; }
 template <int NT_> struct CondWideTab { int own[PD<NT_>::NTT]; };
@@ -992,9 +993,9 @@ __global__ void __launch_bounds__(64 * cw_waves<NT_>()) cond_wide_kernel(const P
     const int uph = SN ? ka.uph : 0;
     const int PP = SN ? sn_pro_pitch(uph) : 64, PSTAGE = 9 * PP;
     const double *gpro = SN ? ka.pro + (size_t)b * uph * PSTAGE : nullptr;
-    // (flags & 8: the linearisation ran beside the planner and left the residuals of the cost to this kernel -- the same
+    // (KF_LIN_AHEAD: the linearisation ran beside the planner and left the residuals of the cost to this kernel -- the same
     //  differences lin_cols_kernel forms, from the iterate and the reference of THIS solve)
-    const bool late_res = !SN && (ka.flags & 8);
+    const bool late_res = !SN && (ka.flags & KF_LIN_AHEAD);
     for (int i = tid; i < (N + 1) * PREC; i += 64 * CW_WAVES) {
         double v = grec[i];
         const int f = i & (PREC - 1), r = f - PR_RES;

@@ -24,8 +24,22 @@
 
 using namespace tum;
 
-// an integer switch of the environment (include/tum_nmpc.h lists them)
+// the integer switches of the environment (include/tum_nmpc.h lists them), read once
 static int env_int(const char *name, int fallback) { const char *e = getenv(name); return e ? atoi(e) : fallback; }
+struct Env {
+    PlanEnv plan;          // TUM_LIN_COLS, TUM_COND_WIDE, TUM_SIM_FORK, TUM_FUSED_EXPAND: -1 the library's choice, 0 never, 1 always (pipe_plan.hpp)
+    int ipm_lds;           // TUM_IPM_LDS (development aid: a larger LDS request lowers the number of OCPs that share a CU), 0: the kernel's own
+    int force_tiles;       // TUM_FORCE_TILES (development aid, tiles_of)
+};
+static const Env &env()
+{
+    static const Env e = [] {
+        const int lds = env_int("TUM_IPM_LDS", 0);
+        return Env{{env_int("TUM_LIN_COLS", -1), env_int("TUM_COND_WIDE", -1), env_int("TUM_SIM_FORK", -1), env_int("TUM_FUSED_EXPAND", -1)},
+                   (lds > 0 && lds <= 64 * 1024) ? lds : 0, env_int("TUM_FORCE_TILES", 0)};
+    }();
+    return e;
+}
 
 static thread_local std::string g_err;
 static int fail(const std::string &m) { g_err = m; return 1; }
@@ -45,7 +59,7 @@ struct tum_ocp {
     bool lpt = true, order_valid = false;
     long long *dprof = nullptr;
     double *dws = nullptr, *dhws = nullptr;
-    int kmode = 0;                 // 0 auto (= the pipeline), 1 fused, 2 pipeline, 3 pipeline with the four-wavefront interior point kernel
+    KMode kmode = KMode::AUTO;     // auto (= the pipeline), fused, pipeline, pipeline with the four-wavefront interior point kernel (pipe_plan.hpp)
     unsigned epoch = 0;            // bumped by everything a captured launch bakes into its kernel arguments (kernel variant, schedule,
                                    // SNMPC horizon / risk parameter / work buffers, R2 attachment): tum_sim_run re-captures its graph
     bool pipe = false;             // this solve runs the four-kernel pipeline (resolved from kmode at launch)
@@ -119,7 +133,7 @@ struct tum_ocp {
     // capturing: tum_sim_run is recording a chunk of the closed loop into a graph (a captured launch is replayed on other iterates)
     bool iter_uniform = false, capturing = false; int lin_dedup = 1; int n_lin_uniform = 0; double *dlin1 = nullptr; int *hlin_bad = nullptr;
     // uniform_records: options_set "uniform_records", 0 by default -- a whole SQP-RTI step on a stage-uniform iterate writes NO stage
-    // records where nothing behind it reads them (launch_pipeline: cond_uniform_kernel and expand_uniform_kernel take lin1 and the
+    // records where nothing behind it reads them (pipe_plan.hpp: plan_pipeline; cond_uniform_kernel and expand_uniform_kernel take lin1 and the
     // reference; the expansion holds the safety net then); 1: lin_fill_kernel always. n_records_skipped: get_stats "records_skipped"
     int uniform_records = 0; int n_records_skipped = 0;
 };
@@ -297,9 +311,9 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
 #ifdef TUM_DEV_KERNELS      // (linearisation records parked by the fused kernel during its interior point loop)
     ok &= dalloc(&c->dws, B * WS_DOUBLES) == hipSuccess;
 #endif
-    { const char *e = getenv("TUM_NMPC_KERNEL"); const std::string k(e ? e : "auto"); c->kmode = (k == "pipeline") ? 2 : 0;
+    { const char *e = getenv("TUM_NMPC_KERNEL"); const std::string k(e ? e : "auto"); c->kmode = (k == "pipeline") ? KMode::PIPELINE : KMode::AUTO;
 #ifdef TUM_DEV_KERNELS
-      if (k == "fused") c->kmode = 1; else if (k == "pipeline4") c->kmode = 3;
+      if (k == "fused") c->kmode = KMode::FUSED; else if (k == "pipeline4") c->kmode = KMode::PIPELINE4;
 #endif
     }
     ok &= hipEventCreate(&c->evi0) == hipSuccess && hipEventCreate(&c->evi1) == hipSuccess;
@@ -307,7 +321,7 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
 
     KArgs &ka = c->ka;
     memset(&ka, 0, sizeof(ka));
-    ka.N = N; ka.nsub = desc->nsub; ka.batch = c->batch; ka.flags = desc->store_qp_in ? 1 : 0; ka.dt = desc->dt;
+    ka.N = N; ka.nsub = desc->nsub; ka.batch = c->batch; ka.flags = desc->store_qp_in ? KF_STORE_QP_IN : 0; ka.dt = desc->dt;
     ka.iter_max = desc->qp_iter_max > 0 ? desc->qp_iter_max : 50;
     ka.tol_stat = desc->qp_tol_stat > 0 ? desc->qp_tol_stat : 1e-8;
     ka.tol_ineq = desc->qp_tol_ineq > 0 ? desc->qp_tol_ineq : 1e-8;
@@ -493,9 +507,8 @@ static void sn_launch_lin(tum_ocp *c)
 {
     const long long items = (long long)c->batch * c->sa.uph * c->sa.ns;
     if (items <= 0) return;
-    // eight lanes per item while that still is one round of wavefronts on the chip (the same rule as launch_pipeline's for lin_cols_kernel)
-    static const int cols_env = env_int("TUM_LIN_COLS", -1);
-    const int want = (c->lin_cols >= 0) ? c->lin_cols : cols_env;
+    // eight lanes per item while that still is one round of wavefronts on the chip (the same rule as plan_pipeline's for lin_cols_kernel, pipe_plan.hpp)
+    const int want = (c->lin_cols >= 0) ? c->lin_cols : env().plan.lin_cols;
     if (want > 0 || (want < 0 && items * SLC_LANES <= 64LL * 1024))
         hipLaunchKernelGGL(snmpc_lin_cols_kernel, dim3((unsigned)((items + SLC_ITEMS - 1) / SLC_ITEMS)), dim3(64), 0, c->stream, c->sa);
     else hipLaunchKernelGGL(snmpc_lin_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, c->stream, c->sa);
@@ -923,7 +936,7 @@ extern "C" int tum_ocp_cost_set(tum_ocp *c, int stage, const char *field, const 
 // (TUM_FORCE_TILES: development aid -- a larger instantiation at a horizon a smaller one covers: the padding variables must not change the answer.)
 static int tiles_of(const tum_ocp *c)
 {
-    static const int force = env_int("TUM_FORCE_TILES", 0);
+    const int force = env().force_tiles;
     const int need = c->N > 48 ? 7 : (c->N > NMAX ? 6 : 5);
     return (force > need && force <= 7 && !c->sn) ? force : need;
 }
@@ -969,8 +982,8 @@ extern "C" int tum_ocp_set_kernel(tum_ocp *c, const char *name)
     const std::string n(name);
     if (n == "time-ipm") { c->time_ipm = true; return 0; }            // (timing options, not kernels: the events around the interior point kernel on EVERY solve)
     if (n == "no-time-ipm") { c->time_ipm = false; return 0; }
-    if (n == "auto") { c->kmode = 0; c->lin_cols = -1; c->cond_wide = -1; c->sim_fork = -1; }        // (the wide kernels of the latency path: the library decides by batch size again)
-    else if (n == "pipeline") c->kmode = 2;
+    if (n == "auto") { c->kmode = KMode::AUTO; c->lin_cols = -1; c->cond_wide = -1; c->sim_fork = -1; }        // (the wide kernels of the latency path: the library decides by batch size again)
+    else if (n == "pipeline") c->kmode = KMode::PIPELINE;
     // the prologue of the coupled SNMPC OCP: the matrix-core kernel (default where n_samples <= 10) or the column-slot / pass variants
     // the linearisation: one lane per (instance, stage) or eight (default: eight while the batch is one round of wavefronts)
     else if (n == "loop-serial") c->sim_fork = 0;
@@ -988,8 +1001,8 @@ extern "C" int tum_ocp_set_kernel(tum_ocp *c, const char *name)
         c->sn_prologue = (n == "prologue-passes") ? 0 : 2;
     }
 #ifdef TUM_DEV_KERNELS
-    else if (n == "fused") c->kmode = 1;
-    else if (n == "pipeline4") c->kmode = 3;
+    else if (n == "fused") c->kmode = KMode::FUSED;
+    else if (n == "pipeline4") c->kmode = KMode::PIPELINE4;
 #else
     else if (n == "fused" || n == "pipeline4")
         return fail("set_kernel: kernel '" + n + "' exists in the development build only (libtumnmpc_dev.so); this library is the pipeline");
@@ -1003,13 +1016,13 @@ extern "C" int tum_ocp_set_kernel(tum_ocp *c, const char *name)
 static int resolve_kernel(tum_ocp *c)
 {
 #ifdef TUM_DEV_KERNELS
-    c->pipe = !(c->ka.flags & 2) && c->kmode != 1;
-    if (c->dWf && c->kmode == 1) return fail("solve: a full W (cost_set 'W' with off-diagonal entries) runs on the pipeline only, not on the development kernel 'fused'");
-    if (c->ka.warm_mu > 0.0 && (c->kmode == 1 || c->kmode == 3))
+    c->pipe = !(c->ka.flags & KF_DEBUG) && c->kmode != KMode::FUSED;
+    if (c->dWf && c->kmode == KMode::FUSED) return fail("solve: a full W (cost_set 'W' with off-diagonal entries) runs on the pipeline only, not on the development kernel 'fused'");
+    if (c->ka.warm_mu > 0.0 && (c->kmode == KMode::FUSED || c->kmode == KMode::PIPELINE4))
         return fail("solve: the development kernels 'fused' / 'pipeline4' always cold-start the interior point method: create the capsule with qp_warm_start = 0");
     if (c->N > NMAX) {      // the fused kernel covers N <= 40; longer horizons exist as a pipeline instantiation only
-        if (c->ka.flags & 2) return fail("debug_dump: the condensed-QP dump is built for N <= 40");
-        if (c->kmode == 1) return fail("solve: kernel 'fused' is built for N <= 40 (use 'auto' or 'pipeline')");
+        if (c->ka.flags & KF_DEBUG) return fail("debug_dump: the condensed-QP dump is built for N <= 40");
+        if (c->kmode == KMode::FUSED) return fail("solve: kernel 'fused' is built for N <= 40 (use 'auto' or 'pipeline')");
         c->pipe = true;
     }
 #else
@@ -1046,146 +1059,118 @@ static void sn_launch_prologue(tum_ocp *c)
     }
 }
 
-// do the wide kernels of the latency path run for this capsule (host's choice by batch size, tum_ocp_set_kernel, environment)
-static bool use_lin_cols(const tum_ocp *c)
+// the facts plan_pipeline decides on (pipe_plan.hpp), as this capsule holds them now
+static PlanIn plan_in(const tum_ocp *c, Part part)
 {
-    static const int cols_env = env_int("TUM_LIN_COLS", -1);
-    const int want = (c->lin_cols >= 0) ? c->lin_cols : cols_env;
-    return want > 0 || (want < 0 && (long long)c->batch * (c->N + 1) * LC_LANES <= 64LL * 1024);
+    PlanIn in;
+    in.N = c->N; in.tiles = tiles_of(c); in.batch = c->batch; in.sn = c->sn; in.uph = c->sa.uph;
+    in.full_w = c->dWf != nullptr; in.store_qp_in = c->d.store_qp_in != 0; in.debug = (c->ka.flags & KF_DEBUG) != 0; in.prof = (c->ka.flags & KF_PROF) != 0;
+    in.kmode = c->kmode; in.lin_cols = c->lin_cols; in.cond_wide = c->cond_wide; in.sim_fork = c->sim_fork; in.env = env().plan;
+    in.iter_uniform = c->iter_uniform; in.lin_dedup = c->lin_dedup != 0; in.uniform_records = c->uniform_records != 0; in.capturing = c->capturing;
+    in.nlp_type = c->nlp_type; in.ran_ahead = c->lin_ahead; in.part = part;
+    return in;
 }
-static bool use_cond_wide(const tum_ocp *c)
-{
-    static const int wide_env = env_int("TUM_COND_WIDE", -1);
-    const int want = (c->cond_wide >= 0) ? c->cond_wide : wide_env;
-    if (tiles_of(c) == 7) return false;          // (seven tiles: the six-wavefront kernel's row store does not fit a CU's LDS beside a full W; one wavefront per OCP at every batch size)
-    return want > 0 || (want < 0 && c->batch <= 256) || c->dWf != nullptr;          // (a full W exists as an instantiation of this kernel only)
-}
-// The device closed loop (tum_sim_run) can run the linearisation of a solve BESIDE the planner of the same control step: the
-// Runge-Kutta pass needs the iterate, not the reference -- only the four residuals of the cost do, and cond_wide_kernel forms those
-// while it loads the records (flags & 8). Nominal OCP on the latency path only (lin_cols_kernel + cond_wide_kernel).
+// the device closed loop: the linearisation of a step beside its planner (plan_lin_ahead, pipe_plan.hpp)
 static bool lin_ahead_ok(const tum_ocp *c)
 {
-    static const int fork_env = env_int("TUM_SIM_FORK", -1);
-    const int want = (c->sim_fork >= 0) ? c->sim_fork : fork_env;
-    // (off unless asked for: measured SLOWER -- 0.169 against 0.160 ms per control step at 26 vehicles, 0.158-0.162 against 0.156 at one:
-    //  the two cross-stream dependencies of a step cost more than the 15 us of planner the linearisation hides behind; HISTORY.md (round-4 document, section 7))
-    return want > 0 && c->pipe && !c->sn && !(c->ka.flags & 6) && use_lin_cols(c) && use_cond_wide(c);
+    PlanIn in = plan_in(c, Part::WHOLE);
+    in.ran_ahead = false;
+    return c->pipe && plan_lin_ahead(in);
 }
 static void launch_lin_ahead(tum_ocp *c, hipStream_t st)
 {
     PArgs pa = pargs(c);
-    pa.ka.flags |= 8;
+    pa.ka.flags |= KF_LIN_AHEAD;
     const long long items = (long long)c->batch * (c->N + 1);
     hipLaunchKernelGGL(lin_cols_kernel<false>, dim3((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), dim3(64), 0, st, pa);
     c->lin_ahead = true;          // the next launch_pipeline skips its linearisation and tells the condensing kernel (consumed there)
 }
 
-// The uniform linearisation replaces lin_kernel<false> only: the nominal OCP beyond the latency path, and never inside the capture of
-// a closed-loop chunk (a captured launch is replayed on iterates that are uniform no more; tum_sim_run clears the mark as well).
-static bool use_lin_uniform(const tum_ocp *c) { return c->iter_uniform && c->lin_dedup && !c->capturing; }
-
-// part: 1 the linearisation and the condensing, 2 the interior point method and the expansion, 3 both (an SQP-RTI solve;
-// a full SQP solve puts its residual pass between the two, launch_sqp)
+// One part of a solve on the pipeline kernels: plan_pipeline (pipe_plan.hpp) says which kernel every stage runs, this launches them.
 // ipm_events: the events around the interior point kernel (get_stats "time_ipm") are recorded
-static int launch_pipeline(tum_ocp *c, bool ipm_events, int part)
+static int launch_pipeline(tum_ocp *c, bool ipm_events, Part part)
 {
+    const PlanIn in = plan_in(c, part);
+    const PipePlan plan = plan_pipeline(in);
     PArgs pa = pargs(c);
-    const bool prof = (c->ka.flags & 4) != 0;
     const long long items = (long long)c->batch * (c->N + 1);
-    // linearisation: eight lanes per item while that still is one round of wavefronts on the chip (256 CUs x 4 SIMDs), see lin_cols_kernel
-    const bool cols = use_lin_cols(c);
-    const dim3 g_cols((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), g_lane((unsigned)((items + 63) / 64));
-    const bool lin_done = c->lin_ahead;
-    // The expansion as the tail of the interior point kernel pays where a batch is at most one round of resident wavefronts (one
-    // launch less: 0.424 against 0.432 ms per solve() call at 26 instances, 0.457 against 0.469 at 1024); beyond that its
-    // loads run at the interior point kernel's occupancy -- one wavefront per SIMD, four OCPs per CU -- and hold that slot:
-    // 3.72 against 3.96 M solves/s on config 2 (three streams). TUM_FUSED_EXPAND=0 / 1 forces it off / on (development aid).
-    static const int fuse_env = env_int("TUM_FUSED_EXPAND", -1);
-    const bool no_fuse = fuse_env == 0 || (fuse_env < 0 && c->batch > 1024);
-    // The record-free path of a stage-uniform iterate: lin_uniform_kernel, cond_uniform_kernel, ipm_kernel, expand_uniform_kernel -- drec is
-    // not written. Taken for a whole SQP-RTI step of the nominal OCP (diagonal W) on the pipeline kernels, with the expansion a kernel of its
-    // own and one wavefront per OCP in the condensing. Everyone else who reads drec -- nlp_residual_kernel (SQP), rti_feedback_kernel (the split
-    // iteration), the fused tail of ipm_kernel, cond_wide_kernel, and behind a solve get_from_qp_in and the R2 back-off (store_qp_in) -- is
-    // reached only where one of these conditions is false.
-    const bool no_records = !lin_done && !cols && use_lin_uniform(c) && part == 3 && !c->uniform_records && c->nlp_type == 0 && !c->sn && !c->dWf &&
-                            !c->d.store_qp_in && !(c->ka.flags & 6) && no_fuse && !use_cond_wide(c) && c->kmode != 3;
-    if (part & 1) {
-    c->lin_ahead = false;
-    if (lin_done) pa.ka.flags |= 8;          // (launch_lin_ahead ran it on another stream; the caller has joined that stream)
-    else if (c->sn) {   // coupled SNMPC OCP: sample fan-out and prologue first, the QP solution goes to the epilogue through the workspace
+    const dim3 g_cols((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), g_lane((unsigned)((items + 63) / 64)), g_ocp(c->batch), wave(64);
+    if (part != Part::FEEDBACK) c->lin_ahead = false;
+    if (plan.lin_ahead_flag) pa.ka.flags |= KF_LIN_AHEAD;          // (launch_lin_ahead ran it on another stream; the caller has joined that stream)
+    if (plan.lin == Lin::SN_LANE || plan.lin == Lin::SN_COLS) {   // coupled SNMPC OCP: sample fan-out and prologue first, the QP solution goes to the epilogue through the workspace
         if (c->fanout && sn_fanout(c)) return 1;
         sn_launch_lin(c);
         sn_launch_prologue(c);
-        if (cols) hipLaunchKernelGGL(lin_cols_kernel<true>, g_cols, dim3(64), 0, c->stream, pa);
-        else hipLaunchKernelGGL(lin_kernel<true>, g_lane, dim3(64), 0, c->stream, pa);
-    } else {
-        if (cols) hipLaunchKernelGGL(lin_cols_kernel<false>, g_cols, dim3(64), 0, c->stream, pa);
-        else if (use_lin_uniform(c)) {
-            // a stage-uniform iterate (cold_start(), reset()): the Runge-Kutta pass once per instance, then the records of every stage
-            hipLaunchKernelGGL(lin_uniform_kernel, dim3((unsigned)((c->batch + 63) / 64)), dim3(64), 0, c->stream, pa, c->dlin1);
-            if (!no_records) hipLaunchKernelGGL(lin_fill_kernel, dim3((unsigned)((c->batch + LF_WAVES - 1) / LF_WAVES)), dim3(64 * LF_WAVES), 0, c->stream, pa, c->dlin1, c->hlin_bad);
-            c->n_lin_uniform++;
-            if (no_records) c->n_records_skipped++;
-        }
-        else hipLaunchKernelGGL(lin_kernel<false>, g_lane, dim3(64), 0, c->stream, pa);
     }
+    switch (plan.lin) {
+    case Lin::NONE: break;
+    case Lin::LANE: hipLaunchKernelGGL(lin_kernel<false>, g_lane, wave, 0, c->stream, pa); break;
+    case Lin::COLS: hipLaunchKernelGGL(lin_cols_kernel<false>, g_cols, wave, 0, c->stream, pa); break;
+    case Lin::SN_LANE: hipLaunchKernelGGL(lin_kernel<true>, g_lane, wave, 0, c->stream, pa); break;
+    case Lin::SN_COLS: hipLaunchKernelGGL(lin_cols_kernel<true>, g_cols, wave, 0, c->stream, pa); break;
+    case Lin::UNIFORM_FILL: case Lin::UNIFORM:
+        // a stage-uniform iterate (cold_start(), reset()): the Runge-Kutta pass once per instance, then the records of every stage
+        // (UNIFORM: nobody reads them, cond_uniform_kernel and expand_uniform_kernel take lin1 and the reference)
+        hipLaunchKernelGGL(lin_uniform_kernel, dim3((unsigned)((c->batch + 63) / 64)), wave, 0, c->stream, pa, c->dlin1);
+        if (plan.lin == Lin::UNIFORM_FILL) hipLaunchKernelGGL(lin_fill_kernel, dim3((unsigned)((c->batch + LF_WAVES - 1) / LF_WAVES)), dim3(64 * LF_WAVES), 0, c->stream, pa, c->dlin1, c->hlin_bad);
+        c->n_lin_uniform++;
+        if (plan.lin == Lin::UNIFORM) c->n_records_skipped++;
+        break;
     }
-    // (development aid: a larger LDS request lowers the number of OCPs that share a CU)
-    static const int lds_req = [] { const int v = env_int("TUM_IPM_LDS", 0); return (v > 0 && v <= 64 * 1024) ? v : 0; }();
     with_tiles(c, [&](auto ntc) {
         constexpr int NTv = decltype(ntc)::value;
-        const int ipm_lds = lds_req > PD<NTv>::I_LDS_BYTES ? lds_req : PD<NTv>::I_LDS_BYTES;
-        if (part & 1) {
-            bool wide = false;
-            if constexpr (NTv != 7) {      // (N = 49..56: a diagonal W, one wavefront per OCP at every batch size)
-                // six wavefronts per OCP while every OCP can have a CU's LDS to itself (cond_wide_kernel)
-                wide = use_cond_wide(c);
+        switch (plan.cond) {
+        case Cond::NONE: break;
+        case Cond::ONE_WAVE: hipLaunchKernelGGL((cond_kernel<NTv, false>), g_ocp, wave, 0, c->stream, pa); break;
+        case Cond::ONE_WAVE_UNIFORM: hipLaunchKernelGGL((cond_uniform_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1); break;
+        case Cond::SN_REGISTER: hipLaunchKernelGGL((cond_kernel<NTv, true, true>), g_ocp, wave, 0, c->stream, pa); break;
+        case Cond::SN_LDS: hipLaunchKernelGGL((cond_kernel<NTv, true, false>), g_ocp, wave, 0, c->stream, pa); break;
+        case Cond::WIDE: case Cond::WIDE_FULLW: case Cond::SN_WIDE:
+            if constexpr (NTv != 7) {      // (never planned at seven tiles: the instantiation does not exist)
                 const dim3 blk(64 * cw_waves<NTv>());
-                if (wide && c->sn) hipLaunchKernelGGL((cond_wide_kernel<NTv, true>), dim3(c->batch), blk, 0, c->stream, pa);
-                else if (wide && c->dWf) hipLaunchKernelGGL((cond_wide_kernel<NTv, false, true>), dim3(c->batch), blk, 0, c->stream, pa);
-                else if (wide) hipLaunchKernelGGL((cond_wide_kernel<NTv, false>), dim3(c->batch), blk, 0, c->stream, pa);
+                if (plan.cond == Cond::SN_WIDE) hipLaunchKernelGGL((cond_wide_kernel<NTv, true>), g_ocp, blk, 0, c->stream, pa);
+                else if (plan.cond == Cond::WIDE_FULLW) hipLaunchKernelGGL((cond_wide_kernel<NTv, false, true>), g_ocp, blk, 0, c->stream, pa);
+                else hipLaunchKernelGGL((cond_wide_kernel<NTv, false>), g_ocp, blk, 0, c->stream, pa);
             }
-            if (!wide) {
-                // (coupled SNMPC: the register form of the stage record pays behind stage uph and costs in front of it, pipe_kernels.hpp)
-                if (c->sn && 2 * c->sa.uph <= c->N) hipLaunchKernelGGL((cond_kernel<NTv, true, true>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-                else if (c->sn) hipLaunchKernelGGL((cond_kernel<NTv, true, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-                else if (no_records) hipLaunchKernelGGL((cond_uniform_kernel<NTv>), dim3(c->batch), dim3(64), 0, c->stream, pa, c->dlin1);
-                else hipLaunchKernelGGL((cond_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-            }
+            break;
         }
-        if (!(part & 2)) return;
+        if (plan.ipm == Ipm::NONE) return;
+        const int ipm_lds = env().ipm_lds > PD<NTv>::I_LDS_BYTES ? env().ipm_lds : PD<NTv>::I_LDS_BYTES;
         if (ipm_events) (void)hipEventRecord(c->evi0, c->stream);
-        bool expanded = false;
+        switch (plan.ipm) {
+        case Ipm::NONE: break;
+        case Ipm::PLAIN: hipLaunchKernelGGL((ipm_kernel<false, NTv>), g_ocp, wave, ipm_lds, c->stream, pa); break;
+        case Ipm::FUSED_TAIL:      // the nominal OCP: the expansion runs as the tail of the interior point kernel
+            if constexpr (NTv != 7) hipLaunchKernelGGL((ipm_kernel<false, NTv, true>), g_ocp, wave, ipm_lds, c->stream, pa);
+            break;
+        case Ipm::INSTRUMENTED:      // (five tiles only, as the four-wavefront kernel)
+            if constexpr (NTv == 5) hipLaunchKernelGGL((ipm_kernel<true, 5>), g_ocp, wave, ipm_lds, c->stream, pa);
+            break;
+        case Ipm::FOUR_WAVE:
 #ifdef TUM_DEV_KERNELS
-        if (prof && c->kmode == 3 && NTv == 5) hipLaunchKernelGGL((ipm4_kernel<true>), dim3(c->batch), dim3(256), I4::BYTES, c->stream, pa);
-        else if (!prof && c->kmode == 3 && NTv == 5) hipLaunchKernelGGL((ipm4_kernel<false>), dim3(c->batch), dim3(256), I4::BYTES, c->stream, pa);
-        else
+            if (in.prof) hipLaunchKernelGGL((ipm4_kernel<true>), g_ocp, dim3(256), I4::BYTES, c->stream, pa);
+            else hipLaunchKernelGGL((ipm4_kernel<false>), g_ocp, dim3(256), I4::BYTES, c->stream, pa);
 #endif
-        // the nominal OCP: the expansion runs as the tail of the interior point kernel (ipm_kernel<., ., true>); the instrumented
-        // instantiation and the coupled SNMPC OCP keep the expansion kernel
-        if constexpr (NTv == 5) {      // (the instrumented instantiation exists for the five-tile build only)
-            if (prof) hipLaunchKernelGGL((ipm_kernel<true, 5>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa);
-            else if (c->sn || no_fuse) hipLaunchKernelGGL((ipm_kernel<false, 5>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa);
-            else { hipLaunchKernelGGL((ipm_kernel<false, 5, true>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa); expanded = true; }
-        } else if constexpr (NTv == 7) {      // (seven tiles: the expansion stays a kernel of its own)
-            hipLaunchKernelGGL((ipm_kernel<false, NTv>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa);
-        } else {
-            if (c->sn || no_fuse) hipLaunchKernelGGL((ipm_kernel<false, NTv>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa);
-            else { hipLaunchKernelGGL((ipm_kernel<false, NTv, true>), dim3(c->batch), dim3(64), ipm_lds, c->stream, pa); expanded = true; }
+            break;
         }
         if (ipm_events) (void)hipEventRecord(c->evi1, c->stream);
-        if (c->sn) {
+        switch (plan.expand) {
+        case Expand::NONE: break;
+        case Expand::RECORDS: hipLaunchKernelGGL((expand_kernel<NTv, false>), g_ocp, wave, 0, c->stream, pa); break;
+        case Expand::UNIFORM: hipLaunchKernelGGL((expand_uniform_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1, c->hlin_bad); break;
+        case Expand::SN_RECORDS: {
             // the epilogue steps the sample copies AND the nominal copy of the stages 1..uph (their PCE mean); the expansion
             // kernel behind it takes the nominal recursion from stage uph to the end of the horizon and evaluates the cost
             SnArgs sa = c->sa;
             sa.dv = c->dvec + PD<NTv>::PV_DV; sa.dv_stride = PD<NTv>::PVEC;
             sa.Xn = c->dX; sa.dxu = c->dvec + PD<NTv>::PV_SC + 8;
-            if (sn_nsb(sa.ns, sa.L) != SN_B16) hipLaunchKernelGGL((snmpc_epilogue_kernel<SN_NSMAX>), dim3(c->batch), dim3(64), 0, c->stream, sa);
-            else hipLaunchKernelGGL((snmpc_epilogue_kernel<>), dim3(c->batch), dim3(64), 0, c->stream, sa);
+            if (sn_nsb(sa.ns, sa.L) != SN_B16) hipLaunchKernelGGL((snmpc_epilogue_kernel<SN_NSMAX>), g_ocp, wave, 0, c->stream, sa);
+            else hipLaunchKernelGGL((snmpc_epilogue_kernel<>), g_ocp, wave, 0, c->stream, sa);
             c->xs_lazy = true;
-            hipLaunchKernelGGL((expand_kernel<NTv, true>), dim3(c->batch), dim3(64), 0, c->stream, pa);
-        } else if (no_records) hipLaunchKernelGGL((expand_uniform_kernel<NTv>), dim3(c->batch), dim3(64), 0, c->stream, pa, c->dlin1, c->hlin_bad);
-        else if (!expanded) hipLaunchKernelGGL((expand_kernel<NTv, false>), dim3(c->batch), dim3(64), 0, c->stream, pa);
+            hipLaunchKernelGGL((expand_kernel<NTv, true>), g_ocp, wave, 0, c->stream, pa);
+            break;
+        }
+        }
     });
     return 0;
 }
@@ -1198,8 +1183,8 @@ static const char *rti_unsupported(const tum_ocp *c)
     if (c->r2) return "the split real-time iteration is not available for a capsule with the R2NMPC tightening attached (the back-off follows every whole solve): rti_phase 0 only";
     if (c->dWf) return "the split real-time iteration is not available for a capsule with a full W (cost_set 'W' with off-diagonal entries: x0 then enters the input rows of the gradient as well): rti_phase 0 only";
     if (c->nlp_type) return "the split real-time iteration is one SQP-RTI step; this capsule is in SQP mode (nlp_solver_type 1)";
-    if (c->kmode == 1 || c->kmode == 3) return "the split real-time iteration runs on the pipeline only, not on the development kernels 'fused' / 'pipeline4'";
-    if (c->ka.flags & 6) return "the split real-time iteration does not run with the debug dump or the phase timers";
+    if (c->kmode == KMode::FUSED || c->kmode == KMode::PIPELINE4) return "the split real-time iteration runs on the pipeline only, not on the development kernels 'fused' / 'pipeline4'";
+    if (c->ka.flags & (KF_DEBUG | KF_PROF)) return "the split real-time iteration does not run with the debug dump or the phase timers";
     return nullptr;
 }
 // may a solve in the capsule's phase start: nothing is touched when it may not
@@ -1262,7 +1247,7 @@ static int launch_prepare(tum_ocp *c)
     c->prep = 0;
     if (flush_inputs(c)) return 1;
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-    if (launch_pipeline(c, false, 1)) return 1;
+    if (launch_pipeline(c, false, Part::PREPARE)) return 1;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->dx0prep, c->dx0, sizeof(double) * (size_t)c->batch * NX, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev1, c->stream));
@@ -1282,7 +1267,7 @@ static int launch(tum_ocp *c, bool events = true)
     // the instrumented instantiation carries the phase timers (flag 4) and the debug dump (flag 2)
     if (c->sn && sn_apply_p(c)) return 1;
 #ifdef TUM_DEV_KERNELS
-    const bool prof = (c->ka.flags & 6) != 0;
+    const bool prof = (c->ka.flags & (KF_DEBUG | KF_PROF)) != 0;
     auto fused = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(c->batch), dim3(64), LDS_BYTES, c->stream, c->ka); };
     if (c->sn && !c->pipe && sn_nsb(c->sa.ns, c->sa.L) != SN_B16)
         return fail("solve: kernel 'fused' takes at most 16 samples / PCE terms (use 'auto' or 'pipeline')");
@@ -1302,7 +1287,7 @@ static int launch(tum_ocp *c, bool events = true)
 #endif
     {
         if (feedback) launch_rti_feedback(c);
-        if (launch_pipeline(c, ipm_events, feedback ? 2 : 3)) return 1;
+        if (launch_pipeline(c, ipm_events, feedback ? Part::FEEDBACK : Part::WHOLE)) return 1;
     }
     HIPCHK(hipGetLastError());
     if (c->r2) {   // constraint tightening for the NEXT solve from this one's linearisation (skipped per instance on failure)
@@ -1411,11 +1396,11 @@ static int launch_sqp(tum_ocp *c)
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if (c->r2) return fail("solve: SQP is not available for a capsule with the R2NMPC tightening attached (nlp_solver_type SQP_RTI only)");
     if (c->sn) return fail("solve: SQP is not available for the coupled SNMPC OCP (nlp_solver_type SQP_RTI only)");
-    if (c->ka.flags & 6) return fail("solve: SQP does not run with the debug dump or the phase timers");
+    if (c->ka.flags & (KF_DEBUG | KF_PROF)) return fail("solve: SQP does not run with the debug dump or the phase timers");
     if (resolve_kernel(c)) return 1;
     if (!c->pipe) return fail("solve: SQP runs on the pipeline only, not on the development kernel 'fused'");
 #ifdef TUM_DEV_KERNELS
-    if (c->kmode == 3) return fail("solve: SQP runs on the pipeline only, not on the development kernel 'pipeline4'");
+    if (c->kmode == KMode::PIPELINE4) return fail("solve: SQP runs on the pipeline only, not on the development kernel 'pipeline4'");
 #endif
     const size_t B = c->batch; const int N = c->N;
     const bool merit = c->globalization == 1;
@@ -1486,7 +1471,7 @@ static int launch_sqp(tum_ocp *c)
     auto residuals = [&](int pass) {
         sq.pass = pass; sq.last = (pass == c->nlp_max_iter) ? 1 : 0;
         sq.cost = (c->nlp_alpha != 1.0 || merit || (pass == 0 && cold)) ? 1 : 0;
-        if (launch_pipeline(c, false, 1)) return 1;
+        if (launch_pipeline(c, false, Part::PREPARE)) return 1;
         with_tiles(c, [&](auto ntc) { hipLaunchKernelGGL(nlp_residual_kernel<decltype(ntc)::value>, dim3(c->batch), dim3(64), 0, c->stream, pa, sq); });
         HIPCHK(hipGetLastError());
         return 0;
@@ -1503,7 +1488,7 @@ static int launch_sqp(tum_ocp *c)
     // instances only -- the commit kernel has put every one of them back -- and the solve ends behind it.
     for (int it = 0; it < c->nlp_max_iter; it++) {
         hipLaunchKernelGGL(sqp_snapshot_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq);
-        if (launch_pipeline(c, c->time_ipm, 2)) return 1;
+        if (launch_pipeline(c, c->time_ipm, Part::FEEDBACK)) return 1;
         invalidate(c, CH_ITERATE);          // (the expansion wrote a new iterate: the residual pass below linearises the general way)
         if (merit) hipLaunchKernelGGL(sqp_merit_kernel, dim3(c->batch, K + 1), dim3(64), 0, c->stream, c->ka, sq, ma);          // (one wavefront per trial point)
         hipLaunchKernelGGL(sqp_commit_kernel, dim3(c->batch), dim3(256), 0, c->stream, c->ka, sq, ma);
@@ -1972,10 +1957,10 @@ extern "C" int tum_ocp_debug_dump(tum_ocp *c, int b, double *out, int len)
     DevGuard guard(c->d.device); GUARD_OK(guard);
     if (len > DBG_STRIDE) len = DBG_STRIDE;
 #ifdef TUM_DEV_KERNELS
-    if (c->kmode != 2 && c->kmode != 3) {
-        c->ka.flags |= 2;
+    if (c->kmode != KMode::PIPELINE && c->kmode != KMode::PIPELINE4) {
+        c->ka.flags |= KF_DEBUG;
         const int rc = launch(c);
-        c->ka.flags &= ~2;
+        c->ka.flags &= ~KF_DEBUG;
         if (rc) return 1;
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpy(out, c->ddbg + (size_t)b * DBG_STRIDE, sizeof(double) * len, hipMemcpyDeviceToHost));
@@ -2022,9 +2007,9 @@ extern "C" int tum_ocp_profile_phases(tum_ocp *c, long long *out)
     if (c->N > NMAX) return fail("profile_phases: the instrumented kernels are built for N <= 40");
     if (c->rti_phase) return fail("profile_phases: the split real-time iteration does not run with the debug dump or the phase timers (set rti_phase 0)");
     DevGuard guard(c->d.device); GUARD_OK(guard);
-    c->ka.flags |= 4;
+    c->ka.flags |= KF_PROF;
     int rc = launch(c);
-    c->ka.flags &= ~4;
+    c->ka.flags &= ~KF_PROF;
     if (rc) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(out, c->dprof, sizeof(long long) * 12 * (size_t)c->batch, hipMemcpyDeviceToHost));
