@@ -208,7 +208,11 @@ int tum_ocp_solve_async(tum_ocp *c);
  *                          OCP with a diagonal W, created without store_qp_in, at batch sizes where the condensing runs one wavefront
  *                          per OCP and the expansion is a kernel of its own (more than 1024 instances), without the debug dump or the
  *                          phase timers; every other solve fills the records as before. Results are bit-identical either way.
- *                          1: always fill the records (A/B runs, tests). */
+ *                          1: always fill the records (A/B runs, tests).
+ * "uniform_powers"         1 (default): the condensing of that record-free path computes what is the same on every lane once per
+ *                          instance -- the sequences A^m B and g_{s+1} = A g_s + defect -- and its stages read them from tables
+ *                          (cond_uniform_kernel). 0: every lane carries its column of G through every stage
+ *                          (cond_uniform_columns_kernel; A/B runs, tests). Results are bit-identical either way. */
 int tum_ocp_options_set(tum_ocp *c, const char *field, double value);
 int tum_ocp_synchronize(tum_ocp *c);
 

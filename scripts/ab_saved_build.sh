@@ -1,11 +1,12 @@
 #!/bin/bash
 # A/B of a SAVED build of the parent commit against the library of the working tree, run from the same tree on one box
 # (the protocol of profiles/lin_uniform_ab.txt and profiles/uniform_records_ab.txt):
-#   scripts/ab_saved_build.sh <parent libtumnmpc.so> [headline] [trace] [full]
+#   scripts/ab_saved_build.sh <parent libtumnmpc.so> [headline] [trace] [full] | [ktrace] [onestream] [dump] [fullbench]
 #     headline  python bench.py, six fresh processes each, interleaved parent / change
 #     trace     rocprofv3 --kernel-trace --stats -- python bench.py --streams 1 (kernel trace only, no counters) for each build: average and
 #               standard deviation per kernel; then bench.py --full --no-other-configs --no-cpu-baseline for each (value_single_stream)
 #     full      bench.py --dump-outputs (--steps 20 --warmup 3) for each build and the bitwise comparison of every .npy, then bench.py --full
+#     ktrace, onestream | dump, fullbench: the two halves of trace | of full on their own
 # The parent's library is built by the same compiler from `git archive <parent>` with the command line of __graft_entry__.build() and
 # loaded through TUM_NMPC_LIB. Every process runs under its own timeout; the chain stops at the first non-zero exit.
 # Results under $AB_OUT (default: ab_out/, which git ignores).
@@ -16,7 +17,9 @@ OUT=${AB_OUT:-ab_out}; mkdir -p $OUT
 export TMPDIR=/tmp
 use() { if [ "$1" = parent ]; then export TUM_NMPC_LIB=$PARENT; else unset TUM_NMPC_LIB; fi; }
 die() { echo "$1 rc=$2"; exit "$2"; }
-for leg in $LEGS; do
+EXP=""
+for leg in $LEGS; do case $leg in trace) EXP="$EXP ktrace onestream" ;; full) EXP="$EXP dump fullbench" ;; *) EXP="$EXP $leg" ;; esac; done
+for leg in $EXP; do
 case $leg in
 headline)
   for i in 1 2 3 4 5 6; do for w in parent change; do
@@ -25,7 +28,7 @@ headline)
     grep metric $OUT/${w}_$i.out > $OUT/${w}_$i.json
     python -c "import json; d = json.load(open('$OUT/${w}_$i.json')); print('$w', $i, 'value', round(d['value']), 'ms/step', round(d['ms_per_step'], 4))"
   done; done ;;
-trace)
+ktrace)
   for w in parent change; do
     use $w
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$w -o s -- python bench.py --streams 1 --no-cpu-baseline \
@@ -42,14 +45,15 @@ for k, v in sorted(d.items(), key=lambda kv: -sum(kv[1])):
 EOF
     rm -rf $OUT/stats_$w
     echo "$w: traced value $(grep metric $OUT/trace_$w.log | python -c "import json, sys; print(round(json.loads(sys.stdin.read())['value']))")"; cat $OUT/kernel_avg_std_$w.txt
-  done
+  done ;;
+onestream)
   for w in parent change; do
     use $w
     timeout -k 10 420 python bench.py --full --no-other-configs --no-cpu-baseline > $OUT/full1_$w.out 2> $OUT/full1_$w.err < /dev/null || die "one-stream leg $w" $?
     grep metric $OUT/full1_$w.out > $OUT/full1_$w.json
     python -c "import json; d = json.load(open('$OUT/full1_$w.json')); print('$w', {k: round(v) for k, v in d.items() if k.startswith('value')})"
   done ;;
-full)
+dump)
   for w in parent change; do
     use $w
     rm -rf /tmp/ab_dump_$w
@@ -69,6 +73,8 @@ for f in fa:
     bad += not same
 print("files", len(fa), "different", bad)
 EOF
+  ;;
+fullbench)
   for w in parent change; do
     use $w
     timeout -k 10 600 python bench.py --full > $OUT/full_$w.out 2> $OUT/full_$w.err < /dev/null || die "full $w" $?

@@ -471,7 +471,7 @@ __device__ __forceinline__ void apply_A_rows(const RecRows &R, double w[8], doub
 // iterate U | packed gg rows (staging for the operand layout)
 // REGF: the register form of the stage record (RecRows); the LDS form is kept for the coupled SNMPC OCP at long propagation horizons
 // (the host decides, pipe_plan.hpp: plan_pipeline)
-// UNI (register form of the nominal OCP only): a STAGE-UNIFORM iterate condensed without stage records (cond_uniform_kernel below).
+// UNI (register form of the nominal OCP only): a STAGE-UNIFORM iterate condensed without stage records (cond_uniform_columns_kernel below).
 // What lin_fill_kernel would write into the N + 1 records is formed here, by its operations on its operands: the fields 0..51 and
 // 56..60 of a stage slot are the same at every stage -- Sp, S from lin1, the defect lin1[44 + i] - X_0[i], the gg row, X_0[6] -- and
 // are formed ONCE, in one register set that the even and the odd stages share; only the four residual lanes of the fourth register
@@ -913,11 +913,249 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_kernel(const PArg
     cond_instance<NT_, SN, REGF, false>(pa, nullptr);
 }
 // K2 of a stage-uniform iterate: reads lin1 (lin_uniform_kernel) and the reference instead of stage records, which are not written
-// (pipe_plan.hpp: plan_pipeline decides); H, C, q, d as cond_kernel<NT_, false, true> hands them over, to the bit
+// (pipe_plan.hpp: plan_pipeline decides); H, C, q, d as cond_kernel<NT_, false, true> hands them over, to the bit.
+// This is the COLUMN form: every lane carries its column of G through every stage (options_set "uniform_powers" 0; the default is
+// cond_uniform_kernel below).
+template <int NT_>
+__global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_columns_kernel(const PArgs pa, const double *lin1)
+{
+    cond_instance<NT_, false, true, true>(pa, lin1);
+}
+
+// ---- K2 of a stage-uniform iterate, POWER form (options_set "uniform_powers" 1, the default).
+// With A_k = A, B_k = B and the defect the same at every stage, column 2 j + r of G_s is P_m[., r] = A^m B[., r] with m = s - 1 - j: the
+// column form's lane 2 j + r inserts B at stage j and applies A by the same instructions afterwards, so at stage s it holds, bit for bit,
+// what lane 2 j + r - 2 held at stage s - 1. All of it is ONE sequence of N two-column blocks, and the constant column is a second one,
+// g_{s+1} = A g_s + defect. Here
+//   phase 1  the sequences, once: a DPP row of 16 lanes per vector (row 0: P[., 0], row 1: P[., 1], row 2: g), lane i of the row the
+//            entry i of the vector and the coefficients of row i of A; the entries a row sum reads are `row_newbcast` operands of the
+//            vector's own register. Every entry is formed by the column form's FMAs on its operands in its order (apply_A_rows and
+//            the insertion behind it): Sp w2 first on rows 0 / 1, then S[i][0..4] w[3..7], rows 3..5 from zero, rows 6 / 7 carried
+//            (selected, not summed with zero coefficients: a NaN of a failed linearisation stays where the column form has it), the
+//            defect added behind the sum on the g row. Seven dependent FMAs a step where
+//            a stage of the column form issues 32 (48 with bank 1) 64 lanes wide. Of every P_m the four cost rows (0..3) and the gg-row
+//            entry g5 w5 (rounded), g3 w3 and g7 w7 fused onto it, go to LDS tables indexed so that column c of stage s is entry
+//            2 (NMAX - s) + c of a row: m < 0 -- the column is not there yet -- is a read of the zero pad behind the table. Of g_s: rows
+//            0..3, row 6 and the gg-row sum, from which d of the two rows of every stage goes out behind the phase.
+//   phase 2  the stages read: the B operands of the Hessian tiles in the operand layout, the gg row's share for the workspace and the
+//            lane's own four rows for the gradient sum. No staging stores, no synchronisation inside the stage loop, no second bank
+//            before stage 33, no lane-63 arrangement. Weights, residual lanes (the reference two stages ahead), aop = bop wl ahead of
+//            the matrix instructions and the order of the matrix instructions are the column form's; q0 / q1 add the same products in
+//            the same order. Hand-over unchanged (tests/test_gpu_uniform_powers.py holds it against the column form, to the bit).
+template <int NT_> struct CondPow {
+    static constexpr int NVP = 16 * NT_, NMAX = 8 * NT_;
+    static constexpr int PAD = 2;               // in front of a row: the one step the P rows run beyond m = N - 1 lands here at N = NMAX
+    // pitch of a table row: PAD | 2 NMAX entries (m = NMAX - 1 .. 0, two columns each) | NVP zeros; 16 mod 32, so that two rows read
+    // by the two halves of 32 lanes (the operand reads: row lane >> 4) fall into different halves of the LDS banks
+    static constexpr int ROW = ((PAD + 2 * NMAX + NVP - 16 + 31) & ~31) + 16;
+    static constexpr int R_HR = 4, NROW = 5;    // rows 0..3: the cost rows, row 4: the gg-row entry
+    static constexpr int TAB = 0, GS = TAB + NROW * ROW;          // g_s: 8 doubles per s = 0..NMAX (entry 4: its gg-row sum)
+    static constexpr int DUMP = GS + (NMAX + 1) * 8;              // where the idle lanes of phase 1 store
+    static constexpr int U0 = DUMP + 64, WT = U0 + NVP, LDS = (WT + (NMAX + 1) * 6 + 1) & ~1;
+    static_assert(LDS * 8 <= 20 * 1024, "eight workgroups per CU");
+};
+// acc += (lane L of the row of b) * x      (b must be settled: two wait states behind the vector instruction that wrote it)
+template <int L> __device__ __forceinline__ void fmac_bc(double &acc, double b, double x)
+{
+    static_assert(L >= 0 && L < 16, "lane of the row");
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(b), "v"(x), "n"(L));
+}
+__device__ __forceinline__ void settle_dpp(double &v) { asm volatile("s_nop 1" : "+v"(v)); }
+
+template <int NT_>
+__device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const double *lin1)
+{
+    PD_LOCALS
+    using T = CondPow<NT_>;
+    constexpr int ROW = T::ROW, PAD = T::PAD;
+    __shared__ __attribute__((aligned(16))) double lds[T::LDS];
+    const KArgs &ka = pa.ka;
+    const int lane = threadIdx.x, b = blockIdx.x;
+    if (b >= ka.batch) return;
+    const int N = ka.N, nv = 2 * N;
+    const double dt = ka.dt;
+    double *sTab = lds + T::TAB, *sG = lds + T::GS, *sU0 = lds + T::U0, *sWt = lds + T::WT;
+    const double *lin1b = lin1 + (size_t)b * LIN1;
+    const double *gx0 = ka.x0 + (size_t)b * NX;
+    const double *gX = ka.X + (size_t)b * (N + 1) * NX;
+    const double *gU = ka.U + (size_t)b * N * NU;
+    const double *gyref = ka.yref + (size_t)b * (N + 1) * 6;
+    const double *gW = ka.W + (size_t)b * (N + 1) * 6;
+    double *gvec = pa.vec + (size_t)b * PVEC;
+    // the weights as the sums take them: dt W_s of the stages s < N, W_e of stage N
+    for (int i = lane; i < (N + 1) * 6; i += 64) sWt[i] = ((i < 6 * N) ? dt : 1.0) * gW[i];
+    sU0[lane] = (lane < nv) ? gU[lane] : 0.0;
+    if (lane < NB1) sU0[64 + lane] = (64 + lane < nv) ? gU[64 + lane] : 0.0;
+    // the zero pad behind every table row: the columns that are not there yet
+#pragma unroll
+    for (int r = 0; r < T::NROW; r++)
+        for (int i = lane; i < ROW - PAD - 2 * NMAX; i += 64) sTab[r * ROW + PAD + 2 * NMAX + i] = 0.0;
+    // the residual lanes (fields 52..55 of the column form's fourth register: lanes 4..7 of every row), what they subtract the reference
+    // from, and the reference two stages ahead (one value for the even stages, one for the odd ones)
+    const bool ures = (lane & 12) == 4;
+    const double *uyp = gyref + (ures ? (lane & 3) : 0);
+    const double x2w = wrap_yaw(gX[2]);
+    const double uxr = ((lane & 3) == 2) ? x2w : gX[lane & 3];
+    double res = ures ? uxr - uyp[6] : 0.0;          // stage 1
+    double uy[2] = {0.0, 0.0};
+    if (2 <= N) uy[0] = uyp[2 * 6];
+    if (3 <= N) uy[1] = uyp[3 * 6];
+
+    // ---- phase 1: the sequences
+    {
+        const int p = lane & 15, i = lane & 7, vrow = lane >> 4, r = vrow & 1;
+        const bool isP = vrow < 2;
+        const bool keep = i < 3 || i >= 6;          // rows 0..2 are updated in place, 6 / 7 are the integrators; 3..5 start from zero
+        const double c2 = (i < 2) ? lin1b[i] : 0.0;          // Sp
+        double cS[5];
+#pragma unroll
+        for (int c = 0; c < 5; c++) cS[c] = (i < 6) ? lin1b[2 + i * 7 + c] : 0.0;
+        const double dsel = isP ? 0.0 : lin1b[L1_XN + i] - gX[i];          // the defect, on the rows that carry g
+        const double g3 = lin1b[L1_GH + 0], g5 = lin1b[L1_GH + 1], g7 = lin1b[L1_GH + 2];
+        // P_0: column r of B over the integrator of input r; g_0 = x0 - X_0
+        double w = isP ? ((i < 6) ? lin1b[2 + i * 7 + 5 + r] : (((i == 6) == (r == 1)) ? dt : 0.0)) : gx0[i] - gX[i];
+        // what a lane stores of its vector: P rows the entries 0..3 and the gg-row entry (lane 4), towards smaller indices (m grows);
+        // the g row its entries 0..7 (lane 4: the gg-row sum), s upwards; everybody else into a slot of its own
+        const bool act = isP ? p < T::NROW : (vrow == 2 && p < 8);
+        int sidx = !act ? T::DUMP + lane : isP ? T::TAB + p * ROW + PAD + 2 * (NMAX - 1) + r : T::GS + p;
+        const int sstep = !act ? 0 : isP ? -2 : 8;
+        const bool ishr = p == 4;
+        auto derive_store = [&]() __attribute__((always_inline)) {
+            double hr = 0.0;
+            fmac_bc<5>(hr, w, g5); fmac_bc<3>(hr, w, g3); fmac_bc<7>(hr, w, g7);
+            lds[sidx] = ishr ? hr : w;
+            sidx += sstep;
+        };
+        settle_dpp(w);
+        derive_store();                              // P_0 (g_0 is not read)
+        for (int t = 0; t < N; t++) {                // P_{t+1} (P_N is not read), g_{t+1}
+            // (a linearisation that failed -- the vehicle at rest after reset() -- carries NaN in Sp, S, B and the defect of the rows 0..5:
+            //  the column form keeps the rows 6 / 7 clear of them, and so does this: no product with a zero coefficient where the column
+            //  form has no product at all -- Sp w2 on the rows 0 / 1 only, the integrators carried, not summed)
+            const double base = keep ? w : 0.0;
+            double acc = base;
+            fmac_bc<2>(acc, w, c2);
+            acc = (i < 2) ? acc : base;
+            fmac_bc<3>(acc, w, cS[0]); fmac_bc<4>(acc, w, cS[1]); fmac_bc<5>(acc, w, cS[2]); fmac_bc<6>(acc, w, cS[3]); fmac_bc<7>(acc, w, cS[4]);
+            w = ((i < 6) ? acc : w) + dsel;
+            settle_dpp(w);
+            derive_store();
+        }
+    }
+    wsync();
+    // d of the two rows of every stage: X_0[6] + g_s[6] and h + the gg-row sum of g_s
+    if (lane < N) {
+        gvec[PV_D + 2 * lane] = sG[(lane + 1) * 8 + 6] + gX[6];
+        gvec[PV_D + 2 * lane + 1] = sG[(lane + 1) * 8 + 4] + lin1b[L1_GH + 3];
+    }
+
+    // ---- phase 2: the stages
+    const int j0 = lane >> 1, r0 = lane & 1;
+    const int lq = lane >> 4, lc = lane & 15;
+    const int l1 = (lane < NB1) ? 64 + lane : 0;          // the lane's column of bank 1
+    double q0 = 0.0, q1 = 0.0;
+    d4 Ht[NTT];
+#pragma unroll
+    for (int i = 0; i < NTT; i++) Ht[i] = d4{0.0, 0.0, 0.0, 0.0};
+    // (two call sites per segment: inlined by force)
+    auto stage_body = [&](const int k, auto tsc, double &uyq) __attribute__((always_inline)) {
+        constexpr int Ts = decltype(tsc)::value;
+        constexpr bool B1 = Ts >= 5;                 // columns 64.. exist from stage 33 on
+        const int s = k + 1;
+        const double *tb = sTab + PAD + 2 * (NMAX - s);
+        const double one = 1.0;
+        settle_dpp(res);
+        // the gg row of stage s goes straight to the workspace in the MFMA operand layout the interior point kernel loads it in
+        {
+            const int c_ = (s - 1) >> 2;
+            double *gcs = pa.cws + (size_t)b * NCH * 64 + 16 * ((s - 1) & 3) + lc;
+            if (2 * lq <= c_) gcs[cidx(c_, lq) * 64] = tb[T::R_HR * ROW + lane];
+            if constexpr (B1) {
+                const int T1 = 4 + lq;
+                if (lane < NB1 && 2 * T1 <= c_) gcs[cidx(c_, T1) * 64] = tb[T::R_HR * ROW + l1];
+            }
+        }
+        double wl, wr[4], gsr[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) wr[r] = sWt[s * 6 + r];          // (the stage's own weights, scaled; stage N: W_e)
+        wl = sWt[s * 6 + lq];
+#pragma unroll
+        for (int r = 0; r < 4; r++) gsr[r] = sG[s * 8 + r];
+        {
+            double a0 = 0.0, a1 = 0.0;
+            static_for<0, 3>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                double gs = gsr[r];
+                fmac_bc<4 + r>(gs, res, one);          // residual + g_s
+                const double e = wr[r] * gs;
+                a0 += e * tb[r * ROW + lane];
+                if constexpr (B1) a1 += e * tb[r * ROW + l1];
+            });
+            q0 += a0;
+            if constexpr (B1) q1 += (lane < NB1) ? a1 : 0.0;
+        }
+        double bop[Ts];
+#pragma unroll
+        for (int Tc = 0; Tc < Ts; Tc++) bop[Tc] = tb[lq * ROW + 16 * Tc + lc];
+        // the weighted operands of the stage: all of them AHEAD of the matrix instructions (as the column form)
+        double aopv[Ts];
+#pragma unroll
+        for (int K = 0; K < Ts; K++) aopv[K] = bop[K] * wl;
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int K = 0; K < Ts; K++)
+#pragma unroll
+            for (int I = K; I < Ts; I++) Ht[tidx(K, I)] = mfma(aopv[K], bop[I], Ht[tidx(K, I)]);
+        // the residuals of the next stage onto their four lanes, the reference of the stage two on behind them: a plain vector write of
+        // a DPP operand -- settle_dpp at the top of the next stage stands between it and the first read
+        if (k + 1 < N) res = ures ? uxr - uyq : res;
+        if (k + 3 < N) uyq = uyp[(size_t)(k + 4) * 6];
+    };
+    // stage s = k+1 touches columns < 2s, i.e. ceil(s/8) tiles: one instantiation of the stage per segment of 8 stages
+    static_for<1, NT>([&](auto tsc) {
+        constexpr int Ts = decltype(tsc)::value;
+        for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k += 2) {
+            stage_body(k, tsc, uy[0]);
+            if (k + 1 < N) stage_body(k + 1, tsc, uy[1]);
+        }
+    });
+    for (int s = N + 1; s <= NMAX; s++) {          // rows beyond the horizon: zeros
+        const int c_ = (s - 1) >> 2;
+        double *gcs = pa.cws + (size_t)b * NCH * 64 + 16 * ((s - 1) & 3) + lc;
+        if (2 * lq <= c_) gcs[cidx(c_, lq) * 64] = 0.0;
+        const int T1 = 4 + lq;
+        if (lane < NB1 && 2 * T1 <= c_) gcs[cidx(c_, T1) * 64] = 0.0;
+    }
+    // input cost (R) and padding on the diagonal, gradient of the input cost
+#pragma unroll
+    for (int K = 0; K < NT; K++)
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) {
+            const int row = lq + 4 * jj;
+            if (row == lc) {
+                const int idx = 16 * K + row;
+                Ht[tidx(K, K)][jj] += (idx < nv) ? sWt[(idx >> 1) * 6 + 4 + (idx & 1)] : 1.0;
+            }
+        }
+    if (lane < nv) q0 += sWt[j0 * 6 + 4 + r0] * (sU0[lane] - gyref[j0 * 6 + 4 + r0]);
+    {
+        const int j1 = 32 + j0;
+        if (lane < NB1 && 64 + lane < nv) q1 += sWt[j1 * 6 + 4 + r0] * (sU0[64 + lane] - gyref[j1 * 6 + 4 + r0]);
+    }
+    // ---- hand-over: H tiles, q (the gg rows went out stage by stage)
+    {
+        d4 *gh = reinterpret_cast<d4 *>(pa.hws) + (size_t)b * NTT * 64 + lane;
+#pragma unroll
+        for (int t = 0; t < NTT; t++) gh[t * 64] = Ht[t];
+        gvec[PV_Q + lane] = q0;
+        if (lane < NB1) gvec[PV_Q + 64 + lane] = q1;
+    }
+}
+
 template <int NT_>
 __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_kernel(const PArgs pa, const double *lin1)
 {
-    cond_instance<NT_, false, true, true>(pa, lin1);
+    cond_powers_instance<NT_>(pa, lin1);
 }
 
 // ---- K2 for small batches: six (N <= 40) or seven wavefronts per OCP.

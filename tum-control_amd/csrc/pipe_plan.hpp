@@ -31,6 +31,7 @@ struct PlanIn {
     int nlp_type = 0;                         // 1: a full SQP solve (its residual pass reads drec)
     bool ran_ahead = false;                   // launch_lin_ahead has run this solve's linearisation on another stream
     Part part = Part::WHOLE;
+    bool uniform_powers = true;               // options_set "uniform_powers": which body condenses a stage-uniform iterate without records
 };
 
 // NONE: the stage is not part of this call (or, Lin: it ran ahead; Expand: it is the tail of the interior point kernel)
@@ -43,6 +44,9 @@ struct PipePlan {
     Lin lin = Lin::NONE; Cond cond = Cond::NONE; Ipm ipm = Ipm::NONE; Expand expand = Expand::NONE;
     bool records_written = true;          // drec holds this linearisation's records for whoever reads it, in this call or behind it
     bool lin_ahead_flag = false;          // KF_LIN_AHEAD for the condensing kernel: it forms the residuals of the cost itself
+    // Cond::ONE_WAVE_UNIFORM only: cond_uniform_kernel (the sequences A^m B and g_s once per instance, the stages read them) or
+    // cond_uniform_columns_kernel (every lane carries its column through every stage); the same hand-over, to the bit
+    bool cond_powers = true;
 };
 
 // who reads drec (the CPU check holds every plan against this)
@@ -88,6 +92,7 @@ inline PipePlan plan_pipeline(const PlanIn &in)
         // (coupled SNMPC: the register form of the stage record pays behind stage uph and costs in front of it, pipe_kernels.hpp)
         else if (in.sn) p.cond = 2 * in.uph <= in.N ? Cond::SN_REGISTER : Cond::SN_LDS;
         else p.cond = record_free ? Cond::ONE_WAVE_UNIFORM : Cond::ONE_WAVE;
+        p.cond_powers = in.uniform_powers;
     }
     if (feedback) {
         // the four-wavefront kernel and the instrumented instantiation exist for the five-tile build only: other tile counts get the

@@ -136,6 +136,9 @@ struct tum_ocp {
     // records where nothing behind it reads them (pipe_plan.hpp: plan_pipeline; cond_uniform_kernel and expand_uniform_kernel take lin1 and the
     // reference; the expansion holds the safety net then); 1: lin_fill_kernel always. n_records_skipped: get_stats "records_skipped"
     int uniform_records = 0; int n_records_skipped = 0;
+    // uniform_powers: options_set "uniform_powers", 1 by default -- the record-free condensing forms the sequences A^m B and g_s once per
+    // instance (cond_uniform_kernel); 0: every lane carries its column through every stage (cond_uniform_columns_kernel). Same results, to the bit.
+    int uniform_powers = 1;
 };
 
 // cold_start() / reset() re-initialise the iterate: a capsule the safety net has failed works again from there. The word may only be
@@ -1068,6 +1071,7 @@ static PlanIn plan_in(const tum_ocp *c, Part part)
     in.kmode = c->kmode; in.lin_cols = c->lin_cols; in.cond_wide = c->cond_wide; in.sim_fork = c->sim_fork; in.env = env().plan;
     in.iter_uniform = c->iter_uniform; in.lin_dedup = c->lin_dedup != 0; in.uniform_records = c->uniform_records != 0; in.capturing = c->capturing;
     in.nlp_type = c->nlp_type; in.ran_ahead = c->lin_ahead; in.part = part;
+    in.uniform_powers = c->uniform_powers != 0;
     return in;
 }
 // the device closed loop: the linearisation of a step beside its planner (plan_lin_ahead, pipe_plan.hpp)
@@ -1122,7 +1126,10 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, Part part)
         switch (plan.cond) {
         case Cond::NONE: break;
         case Cond::ONE_WAVE: hipLaunchKernelGGL((cond_kernel<NTv, false>), g_ocp, wave, 0, c->stream, pa); break;
-        case Cond::ONE_WAVE_UNIFORM: hipLaunchKernelGGL((cond_uniform_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1); break;
+        case Cond::ONE_WAVE_UNIFORM:
+            if (plan.cond_powers) hipLaunchKernelGGL((cond_uniform_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1);
+            else hipLaunchKernelGGL((cond_uniform_columns_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1);
+            break;
         case Cond::SN_REGISTER: hipLaunchKernelGGL((cond_kernel<NTv, true, true>), g_ocp, wave, 0, c->stream, pa); break;
         case Cond::SN_LDS: hipLaunchKernelGGL((cond_kernel<NTv, true, false>), g_ocp, wave, 0, c->stream, pa); break;
         case Cond::WIDE: case Cond::WIDE_FULLW: case Cond::SN_WIDE:
@@ -1372,7 +1379,12 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
         c->uniform_records = (int)value;
         return 0;
     }
-    return fail("options_set: unknown field '" + f + "' (lin_dedup | uniform_records | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
+    if (f == "uniform_powers") {      // 1: the record-free condensing computes the sequences A^m B, g_s once per instance (default); 0: every lane carries its column (A/B runs, tests)
+        if (value != 0.0 && value != 1.0) return fail("options_set uniform_powers: 0 or 1");
+        c->uniform_powers = (int)value;
+        return 0;
+    }
+    return fail("options_set: unknown field '" + f + "' (lin_dedup | uniform_records | uniform_powers | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
                 "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length | rti_phase), of the SQP globalization (globalization | "
                 "alpha_min | alpha_reduction | merit_weight_eq)");
 }

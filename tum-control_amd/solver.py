@@ -342,7 +342,8 @@ class BatchedOcpSolver:
         with 'alpha_min', 'alpha_reduction' and 'merit_weight_eq' (include/tum_nmpc.h, tum_ocp_options_set);
         'rti_phase' 0 | 1 | 2: the following solve() calls are whole SQP-RTI steps (default), preparations or feedbacks;
         'lin_dedup' 1 | 0: linearise a stage-uniform iterate (after cold_start() / reset()) once per instance (default) or per stage;
-        'uniform_records' 0 | 1: such a solve writes no stage records where nothing reads them (default), or always fills them"""
+        'uniform_records' 0 | 1: such a solve writes no stage records where nothing reads them (default), or always fills them;
+        'uniform_powers' 1 | 0: its condensing computes the sequences A^m B once per instance (default) or carries every column through every stage"""
         if field == "rti_phase":
             value = _rti_phase_value(value)
         if field == "globalization":
