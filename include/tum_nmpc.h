@@ -364,7 +364,11 @@ int tum_ocp_snmpc_set_offsets(tum_ocp *c, const double *offs);
 /* R2NMPC constraint tightening after a solve (Reduced_Robustified_NMPC_class.py:286-366): propagates
  * Sigma_{k+1} = A_k Sigma_k A_k' + B W B' with the A_k of the last linearisation (needs store_qp_in) and rewrites the
  * capsule's lbx/ubx (steering angle) and uh (gg circle) of stages 1..N-1 for the NEXT solve.
- * Sigma0, BWB: 8x8 row-major (host); backoff (optional, host): batch x N x 2 (steering, gg) back-offs. */
+ * Sigma0, BWB: 8x8 row-major (host); backoff (optional, host): batch x N x 2 (steering, gg) back-offs.
+ * uph >= 1, the reference's uncertainty_propagation_horizon: the stages 1..min(uph, N)-1 get the back-offs of their own
+ * Sigma_k, the stages from uph on repeat the last pair, and a uph beyond N acts as N. uph = 1 propagates nothing: both
+ * back-offs are 0 and the stages 1..N-1 get the nominal delta_min / delta_max / uh_nom. uph < 1 is refused. An instance whose
+ * last solve failed keeps all its bounds; its rows of `backoff` read 0. */
 int tum_ocp_r2_backoff(tum_ocp *c, const double *Sigma0, const double *BWB, int uph,
                        double delta_min, double delta_max, double uh_nom, double *backoff);
 /* The same tightening as part of EVERY solve (Reduced_Robustified_NMPC_class.py:276-378 runs it after each successful acados
