@@ -422,6 +422,26 @@ int tum_sim_steps(const tum_sim *s);
  * "simREF" (steps*B*4), "simSolverDebug" (steps*B*5: cost, 0, sqp_iter, qp_iter, status). len must match. */
 int tum_sim_get(tum_sim *s, const char *field, double *out, long long len);
 
+/* ---- track segments: what a weight sweep runs the loop for (Learning_To_Adapt/SafeRL_WMPC/BO_WMPC/objective_function.py:57-200,
+ * the same termination rules as RL_WMPC/environment.py:152-165,239-240) ------------------------------------------------
+ * Once attached, every control step scores every instance whose segment is still active, between the solve and the plant step, from
+ * what the loop holds there (Utils/Logging_Plotting.py:152-179): lat_dev and vel_dev of the plant state against the first reference
+ * point, a_comb from the gg table of the capsule. It accumulates steps, max |lat_dev|, sum vel_dev^2, max a_comb and the failed solves,
+ * then sets the bits of the segment's state word, which are never cleared: 1 done (planner index == end_idx[b], an equality;
+ * end_idx[b] < 0: never), 2 crash by lat_dev > max_lat_dev (signed), 4 crash by a_comb > max_a_comb. The step that sets a bit is
+ * counted; an instance with a non-zero state is not scored any further but keeps driving. An infinite threshold disables its test.
+ * end_idx: batch ints (host). group_offsets: n_groups + 1 ints, 0 = first < ... < last = batch (contiguous groups of instances;
+ * NULL: one group per instance). end_idx == NULL detaches. Either way a captured chunk of the run function is dropped and captured again.
+ * The state function (set_state) zeroes scores and state words: a new run is a new evaluation. */
+int tum_sim_segments_attach(tum_sim *s, const int *end_idx, const int *group_offsets, int n_groups, double max_lat_dev, double max_a_comb);
+/* the run function in chunks of check_every control steps (<= 0: 100) until no segment is active or max_steps have run. Segments still
+ * active then have timed out: they are neither done nor crashed (the reference's loop has no cap, a batched one needs it).
+ * More fields of the get function, B values each unless noted, an error when nothing is attached: "seg_steps", "seg_state",
+ * "seg_max_lat_dev", "seg_rms_vel_dev" (sqrt(sum vel_dev^2 / steps)), "seg_max_a_comb", "seg_qp_failures", "seg_active" (1 value),
+ * "seg_groups" (n_groups x 4: mean of -max|lat_dev|, mean of -rms(vel_dev), segments, segments not cleanly done -- crashed or
+ * still active; one reduction kernel per read, fixed summation order). */
+int tum_sim_run_segments(tum_sim *s, int max_steps, int check_every);
+
 /* development aid: one solve with in-kernel phase timers; out = batch x 12 shader-cycle counters
  * [linearise, condense, ipm-residuals, M assembly, Cholesky, rhs, tri-solves, row updates, (iteration tail), expand+cost] */
 int tum_ocp_profile_phases(tum_ocp *c, long long *out);

@@ -15,8 +15,8 @@ Every instance may carry its own cost weights / penalties (the BO / RL weight sw
 import numpy as np
 
 from . import config as _config
-from .planner import load_track, planner_emulator, yref_from_ref
-from .solver import BatchedOcpSolver, CoupledSnmpcSolver, DeviceClosedLoop
+from .planner import closest_index, load_track, planner_emulator, yref_from_ref
+from .solver import BatchedOcpSolver, CoupledSnmpcSolver, DeviceClosedLoop, segment_flags
 
 WINDOWS = (1, 1, 4, 2, 2, 3, 4, 2)          # SimulationMode_main_class.py:86
 
@@ -194,9 +194,25 @@ class MovingAverageEstimator:
         return out
 
 
+def start_states(track, idx_start, batch):
+    """X0_MPC (batch, 8) of loops that start on the race line at waypoint idx_start (SimulationMode_main_class.py:60-75 with
+    idx_ref_start): position, yaw in [0, 2 pi), reference speed, everything else 0. idx_start: one index or (batch,) indices."""
+    idx = np.asarray(idx_start)
+    if idx.ndim == 0:
+        i = idx_start
+        x0 = np.array([track[i, 0], track[i, 1], np.mod(track[i, 2], 2 * np.pi), track[i, 3], 0, 0, 0, 0.0])
+        return np.tile(x0, (batch, 1))
+    if idx.shape != (batch,) or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("idx_start: one index or an integer array of length batch")
+    x = np.zeros((batch, 8))
+    x[:, 0], x[:, 1], x[:, 2], x[:, 3] = track[idx, 0], track[idx, 1], np.mod(track[idx, 2], 2 * np.pi), track[idx, 3]
+    return x
+
+
 class ClosedLoopBatch:
     """B independent closed loops on one track, one OCP instance each; `params` (B,7) are per-instance
-    [q_xy, q_yaw, q_vel, r_jerk, r_steer, L1, L2] as in update_cost_function_weights (None: YAML defaults x0.01)."""
+    [q_xy, q_yaw, q_vel, r_jerk, r_steer, L1, L2] as in update_cost_function_weights (None: YAML defaults x0.01).
+    idx_start: the waypoint all loops start at, or one per instance."""
 
     def __init__(self, track_name, batch=1, params=None, N=38, Tp=3.04, Ts=0.02, idx_start=0, cfg=None, device=0,
                  on_device=False, log_capacity=0, controller="nominal", disturbances=None, disturbance_steps=0, seed=0,
@@ -205,9 +221,7 @@ class ClosedLoopBatch:
         kw = {} if qp_tol is None else dict(qp_tol=tuple(qp_tol))          # (termination tolerances of the interior point method; default: the solver's 1e-8)
         self.track = load_track(track_name)
         self.B, self.N, self.Tp, self.Ts = batch, N, Tp, Ts
-        tr = self.track
-        x0 = np.array([tr[idx_start, 0], tr[idx_start, 1], np.mod(tr[idx_start, 2], 2 * np.pi), tr[idx_start, 3], 0, 0, 0, 0.0])
-        self.x_mpc = np.tile(x0, (batch, 1))                     # X0_MPC
+        self.x_mpc = start_states(self.track, idx_start, batch)  # X0_MPC
         self.x_sim = self.x_mpc[:, :7].copy()                    # X0_sim
         self.pose = self.x_mpc[:, :2].copy()
         self.controller = controller
@@ -359,3 +373,115 @@ class ClosedLoopBatch:
             np.savez(f, **log_file_arrays(logs, b, self.w_deriv, self.e_est, T=T, Ts=self.Ts, drop_last_step=drop_last_step))
             out.append(f)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Track segments: what the weight sweep runs the loop for (Learning_To_Adapt/SafeRL_WMPC/BO_WMPC/objective_function.py:57-200;
+# the RL environment ends an episode by the same rules, RL_WMPC/environment.py:152-165,239-240)
+
+def gg_limits(vlong, cfg):
+    """(ax_lim, ay_lim) of the gg table at vlong: piecewise linear, the outer pieces extended (the interpolant the OCP's
+    constraint uses, NMPC_class.py:322-335; the same arithmetic as interp_lin of csrc/nmpc_device.hpp)"""
+    g = cfg["ggv"]
+    v, ax, ay = (np.asarray(g[k], dtype=float) for k in ("v", "ax", "ay"))
+    vlong = np.asarray(vlong, dtype=float)
+    i = np.clip(np.searchsorted(v, vlong, side="right") - 1, 0, len(v) - 2)
+    out = []
+    for y in (ax, ay):
+        sl = (y[i + 1] - y[i]) / (v[i + 1] - v[i])
+        out.append(y[i] + sl * (vlong - v[i]))
+    return out[0], out[1]
+
+
+def segment_step_channels(CiLX_s, simREF_s, a_next, cfg):
+    """What Logger.logging_step derives in control step s (Utils/Logging_Plotting.py:152-179) from the plant state BEFORE the step
+    (CiLX[s]), the first reference point of the step (simREF[s]) and x_next_MPC[7] (MPC_SimX[s + 1][7]): lat_dev (signed), vel_dev
+    (signed), a_comb. Arrays over a leading batch axis."""
+    _, lat = lon_lat_deviations(CiLX_s[..., 2], CiLX_s[..., 0], CiLX_s[..., 1], simREF_s[..., 0], simREF_s[..., 1])
+    vel = CiLX_s[..., 3] - simREF_s[..., 3]
+    ax, ay = gg_limits(CiLX_s[..., 3], cfg)
+    ax = np.where(a_next > 0, ax, cfg["veh"]["acc_min"])
+    alat = CiLX_s[..., 3] * CiLX_s[..., 5]
+    return lat, vel, np.sqrt((a_next / ax) ** 2 + (alat / ay) ** 2)
+
+
+def segment_scores_from_logs(logs, track, end_idx, max_lat_dev, max_a_comb, cfg=None, first_step=0):
+    """The scores DeviceClosedLoop.segments() keeps on the device, from the five raw logs of a run -- the host statement of the same
+    rules, and the path a caller without attach_segments has: per control step s >= first_step and instance b still active, the
+    channels of segment_step_channels, the accumulators (steps, max |lat_dev|, sum vel_dev^2, max a_comb, failed solves), then the
+    state bits, never cleared: 1 done (planner_emulator's index of the logged pose == end_idx[b]; end_idx[b] < 0: never),
+    2 lat_dev > max_lat_dev (signed), 4 a_comb > max_a_comb (objective_function.py:139-146,188-200). The step that sets a bit is
+    counted; nothing after it is. rms_vel_dev = sqrt(sum / steps) (0 before the first step)."""
+    cfg = cfg or _config.default_config()
+    CiLX, REF, SimX, DBG = (np.asarray(logs[k]) for k in ("CiLX", "simREF", "MPC_SimX", "simSolverDebug"))
+    S, B = REF.shape[0], REF.shape[1]
+    end_idx = np.broadcast_to(np.asarray(end_idx), (B,))
+    steps = np.zeros(B, dtype=np.int64); state = np.zeros(B, dtype=np.int64); qpf = np.zeros(B, dtype=np.int64)
+    max_lat = np.zeros(B); sumsq = np.zeros(B); max_ac = np.zeros(B)
+    for s in range(first_step, S):
+        act = state == 0
+        if not act.any():
+            break
+        lat, vel, ac = segment_step_channels(CiLX[s], REF[s], SimX[s + 1][:, 7], cfg)
+        closest = closest_index(track, CiLX[s][:, :2])
+        steps[act] += 1
+        max_lat[act] = np.maximum(max_lat[act], np.abs(lat[act]))
+        sumsq[act] = sumsq[act] + vel[act] ** 2
+        max_ac[act] = np.maximum(max_ac[act], ac[act])
+        qpf[act] += (DBG[s][act, 4] != 0)
+        bits = 1 * ((end_idx >= 0) & (closest == end_idx)) + 2 * (lat > max_lat_dev) + 4 * (ac > max_a_comb)
+        state[act] = bits[act]
+    rms = np.sqrt(np.divide(sumsq, steps, out=np.zeros(B), where=steps > 0))
+    d = dict(steps=steps, state=state, max_lat_dev=max_lat, rms_vel_dev=rms, max_a_comb=max_ac, qp_failures=qpf)
+    d.update(segment_flags(state))
+    return d
+
+
+def _objectives_from_groups(groups):
+    """groups (P, n_groups, 4) as DeviceClosedLoop.segment_groups() orders them -> objectives (P, n_groups, 2), feasible (P,):
+    a candidate with any segment not cleanly done is infeasible and ALL its objectives are NaN (objective_function.py:162-172)"""
+    groups = np.asarray(groups, dtype=float)
+    feasible = (groups[:, :, 3] == 0).all(axis=1)
+    objectives = groups[:, :, :2].copy()
+    objectives[~feasible] = np.nan
+    return objectives, feasible
+
+
+def segment_objectives(seg, n_candidates, group_sizes):
+    """(objectives (P, n_groups, 2), feasible (P,)) from a per-segment dict (segments() / segment_scores_from_logs) of a
+    candidate-major batch P x sum(group_sizes): per group the means of -max|lat_dev| and -rms(vel_dev)
+    (objective_function.py:163,178-185), NaN rows for infeasible candidates."""
+    P, sizes = int(n_candidates), [int(n) for n in group_sizes]
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    lat = np.asarray(seg["max_lat_dev"], dtype=float).reshape(P, off[-1])
+    rms = np.asarray(seg["rms_vel_dev"], dtype=float).reshape(P, off[-1])
+    bad = (np.asarray(seg["crashed"]) | np.asarray(seg["timed_out"])).reshape(P, off[-1])
+    groups = np.zeros((P, len(sizes), 4))
+    for g in range(len(sizes)):
+        sl = slice(off[g], off[g + 1])
+        groups[:, g, 0] = -lat[:, sl].mean(axis=1); groups[:, g, 1] = -rms[:, sl].mean(axis=1)
+        groups[:, g, 2] = sizes[g]; groups[:, g, 3] = bad[:, sl].sum(axis=1)
+    return _objectives_from_groups(groups)
+
+
+def evaluate_segments(track_name, params, segment_groups, max_lat_dev, max_a_comb, max_steps, N=38, Tp=3.04, controller="nominal",
+                      check_every=0, **loop_kw):
+    """objective_function (BO_WMPC/objective_function.py:57-175) for P candidate weight sets at once, on one track: params (P, 7) as in
+    update_cost_function_weights, segment_groups a list of groups of (start, end) waypoint index pairs. One device loop of
+    P x (number of segments) instances, candidate-major, every instance started at its segment's start and scored until the planner's
+    index equals its end, it crashes, or max_steps have run. Returns (objectives (P, n_groups, 2), feasible (P,), per-segment dict).
+    A candidate with a crashed or timed-out segment is infeasible and all its objectives are NaN. (The reference stops a candidate
+    at its first crash; here all its segments run, the returned values are the same.)"""
+    params = np.asarray(params, dtype=float).reshape(-1, 7)
+    P = len(params)
+    pairs = np.array([p for grp in segment_groups for p in grp], dtype=np.int64).reshape(-1, 2)
+    sizes = [len(grp) for grp in segment_groups]
+    S = len(pairs)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    offsets = np.concatenate([c * S + off[:-1] for c in range(P)] + [[P * S]])
+    cl = ClosedLoopBatch(track_name, batch=P * S, params=np.repeat(params, S, axis=0), N=N, Tp=Tp, idx_start=np.tile(pairs[:, 0], P),
+                         on_device=True, controller=controller, **loop_kw)
+    cl.dev.attach_segments(np.tile(pairs[:, 1], P), max_lat_dev, max_a_comb, group_offsets=offsets)
+    cl.dev.run_segments(max_steps, check_every)
+    objectives, feasible = _objectives_from_groups(cl.dev.segment_groups().reshape(P, len(sizes), 4))
+    return objectives, feasible, cl.dev.segments()

@@ -2,6 +2,9 @@
 //   K8 planner_kernel        local reference extraction for every instance (Utils/MPC_sim_utils.py:137-194 PlannerEmulator)
 //   K9 plant_advance_kernel  plant step + state estimation (Utils/SimulationMode_main_class.py:106-156 sim_step / StateEstimation,
 //                            Vehicle_Simulator/sim_model_dynamic_stm_pacejka.py:137-195, VehicleSimulator.py:73-77)
+//   K10 segment_score_kernel / segment_group_kernel  what a weight sweep runs the loop for: per-instance track segments with their own
+//                            end, the crash tests and the two objectives of the reference's Bayesian optimisation
+//                            (Learning_To_Adapt/SafeRL_WMPC/BO_WMPC/objective_function.py:139-146,178-200, Utils/Logging_Plotting.py:152-179)
 // With them a batch of closed loops runs planner -> solve -> plant without leaving HBM.
 #pragma once
 #include "nmpc_device.hpp"
@@ -354,6 +357,88 @@ __global__ void __launch_bounds__(64) plant_advance_kernel(const SimArgs sa)
     if (threadIdx.x == 0) {
         __threadfence();
         if (atomicAdd(&sa.step_counter[1], 1) == (int)gridDim.x - 1) { sa.step_counter[1] = 0; atomicAdd(&sa.step_counter[0], 1); }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- K10: segment scores
+// bits of the state word of a segment (never cleared; 0 = active)
+constexpr int SEG_DONE = 1;            // the planner's index reached the segment's end (objective_function.py:139: an equality)
+constexpr int SEG_CRASH_LAT = 2;       // lat_dev > max_lat_dev, signed (objective_function.py:192)
+constexpr int SEG_CRASH_ACOMB = 4;     // a_comb > max_a_comb (objective_function.py:193)
+
+struct SegArgs {
+    int N, batch, n_ggv;
+    const double *X; const int *status;               // the solver's outputs of this step: X[b][1][7] is x_next_MPC[7]
+    const double *x_sim, *ref0; const int *closest;   // plant state before this step (CiLX[s]), simREF[s], current_ref_idx
+    const int *end_idx;                               // [b] planner index that ends the segment (< 0: never)
+    const double *ggv;                                // [3][16] gg table of the capsule: v, ax, ay
+    double acc_min, max_lat_dev, max_a_comb;
+    int *steps, *state, *qp_failures;                 // [b] each
+    double *max_abs_lat, *sumsq_vel, *max_acomb;      // [b] each
+};
+
+// One lane per instance, once per control step between the solve and plant_advance_kernel. What Logger.logging_step derives per
+// step (Utils/Logging_Plotting.py:152-179) and what objective_function.py:139-146 tests after it, in their order; an instance
+// whose state word is non-zero is not scored any further (it keeps driving: nothing else in the loop knows about segments).
+__global__ void __launch_bounds__(64) segment_score_kernel(const SegArgs a)
+{
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    if (a.state[b] != 0) return;
+    const double *xs = a.x_sim + (size_t)b * 7, *rf = a.ref0 + (size_t)b * 4;
+    const double x = xs[0], y = xs[1], yaw = xs[2], vl = xs[3], r = xs[5];
+    const double acc = a.X[((size_t)b * (a.N + 1) + 1) * NX + 7];
+    // LonLatDeviations (Utils/MPC_sim_utils.py:102-112), lateral component; velocity deviation
+    double sn, cs;
+    fast_sincos(-yaw, &sn, &cs);
+    const double lat = sn * (rf[0] - x) + cs * (rf[1] - y);
+    const double vel = vl - rf[3];
+    // combined acceleration, normalised with the gg table (braking: acc_min)
+    double ax, ay, sl;
+    interp_lin(a.n_ggv, a.ggv, a.ggv + 32, vl, ay, sl);
+    if (acc > 0.0) interp_lin(a.n_ggv, a.ggv, a.ggv + 16, vl, ax, sl);
+    else ax = a.acc_min;
+    const double nlon = acc / ax, nlat = (vl * r) / ay;
+    const double acomb = sqrt(nlon * nlon + nlat * nlat);
+    a.steps[b] += 1;
+    a.max_abs_lat[b] = fmax(a.max_abs_lat[b], fabs(lat));
+    a.sumsq_vel[b] = a.sumsq_vel[b] + vel * vel;
+    a.max_acomb[b] = fmax(a.max_acomb[b], acomb);
+    if (a.status[b] != 0) a.qp_failures[b] += 1;
+    int st = 0;
+    if (a.end_idx[b] >= 0 && a.closest[b] == a.end_idx[b]) st |= SEG_DONE;
+    if (lat > a.max_lat_dev) st |= SEG_CRASH_LAT;
+    if (acomb > a.max_a_comb) st |= SEG_CRASH_ACOMB;
+    if (st) a.state[b] = st;
+}
+
+// One wavefront per group of segments (instances group_offsets[g] .. group_offsets[g + 1] - 1), launched on request. Lane l sums the
+// members l, l + 64, ... in that order and the 64 partial sums meet in a fixed butterfly: the result depends on nothing but the data.
+// out[g] = { mean(-max_abs_lat), mean(-rms(vel_dev)), number of segments, number not cleanly done (crashed or still active) }.
+__global__ void __launch_bounds__(64) segment_group_kernel(const int *group_offsets, int n_groups, const int *steps, const int *state,
+                                                           const double *max_abs_lat, const double *sumsq_vel, double *out)
+{
+#pragma clang fp contract(off)
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n_groups) return;
+    const int lo = group_offsets[g], hi = group_offsets[g + 1];
+    double s_lat = 0.0, s_rms = 0.0; int unclean = 0;
+    for (int i = lo + lane; i < hi; i += 64) {
+        s_lat = s_lat + max_abs_lat[i];
+        const int n = steps[i];
+        s_rms = s_rms + (n > 0 ? sqrt(sumsq_vel[i] / (double)n) : 0.0);
+        const int st = state[i];
+        unclean += ((st & (SEG_CRASH_LAT | SEG_CRASH_ACOMB)) != 0 || st == 0) ? 1 : 0;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        s_lat = s_lat + __shfl_xor(s_lat, off, 64);
+        s_rms = s_rms + __shfl_xor(s_rms, off, 64);
+        unclean += __shfl_xor(unclean, off, 64);
+    }
+    if (lane == 0) {
+        const double n = (double)(hi - lo);
+        out[4 * g] = -(s_lat / n); out[4 * g + 1] = -(s_rms / n); out[4 * g + 2] = n; out[4 * g + 3] = (double)unclean;
     }
 }
 

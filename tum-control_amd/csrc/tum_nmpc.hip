@@ -4,6 +4,7 @@
 // pipeline is held against: round 1's fused kernel and the four-wavefront interior point kernel.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2201,7 +2202,27 @@ struct tum_sim {
     double *lCiLX, *lSimX, *lU, *lREF, *lDBG;
     hipStream_t s2; hipEvent_t evF, evJ;              // side stream of the linearisation that runs beside the planner, fork / join events
     double *ddw, *dde; int dist_len;                  // disturbance realisation played back by the loop (tum_sim_set_disturbances)
+    // segment scoring (tum_sim_segments_attach): end index and accumulators per instance, groups of contiguous instances
+    bool seg; int seg_groups; double seg_max_lat, seg_max_acomb;
+    int *dseg_end, *dseg_off, *dseg_steps, *dseg_state, *dseg_qpf;
+    double *dseg_lat, *dseg_ssq, *dseg_acomb, *dseg_ggv, *dseg_out;
 };
+static void seg_release(tum_sim *s)
+{
+    (void)hipFree(s->dseg_end); (void)hipFree(s->dseg_off); (void)hipFree(s->dseg_steps); (void)hipFree(s->dseg_state); (void)hipFree(s->dseg_qpf);
+    (void)hipFree(s->dseg_lat); (void)hipFree(s->dseg_ssq); (void)hipFree(s->dseg_acomb); (void)hipFree(s->dseg_ggv); (void)hipFree(s->dseg_out);
+    s->dseg_end = s->dseg_off = s->dseg_steps = s->dseg_state = s->dseg_qpf = nullptr;
+    s->dseg_lat = s->dseg_ssq = s->dseg_acomb = s->dseg_ggv = s->dseg_out = nullptr;
+    s->seg = false; s->seg_groups = 0;
+}
+// a new evaluation: accumulators and state words of every segment back to zero (fills on the NULL stream: the caller synchronises)
+static int seg_zero(tum_sim *s)
+{
+    const size_t B = s->c->batch;
+    HIPCHK(hipMemset(s->dseg_steps, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->dseg_state, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->dseg_qpf, 0, sizeof(int) * B));
+    HIPCHK(hipMemset(s->dseg_lat, 0, sizeof(double) * B)); HIPCHK(hipMemset(s->dseg_ssq, 0, sizeof(double) * B)); HIPCHK(hipMemset(s->dseg_acomb, 0, sizeof(double) * B));
+    return 0;
+}
 
 extern "C" int tum_planner_emulate(const double *track, int n_track, const double *pose, int P, int n_points, double Tp,
                                    int loop_circuit, double *ref_out, int *closest_out, int device)
@@ -2241,6 +2262,7 @@ extern "C" void tum_sim_free(tum_sim *s)
     if (s->s2) { (void)hipStreamSynchronize(s->s2); (void)hipStreamDestroy(s->s2); (void)hipEventDestroy(s->evF); (void)hipEventDestroy(s->evJ); }
     (void)hipFree(s->lCiLX); (void)hipFree(s->lSimX); (void)hipFree(s->lU); (void)hipFree(s->lREF); (void)hipFree(s->lDBG);
     (void)hipFree(s->ddw); (void)hipFree(s->dde);
+    seg_release(s);
     delete s;
 }
 
@@ -2289,6 +2311,7 @@ extern "C" int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *
     HIPCHK(hipMemcpy2D(s->dpose, 2 * 8, x_mpc, 8 * 8, 2 * 8, B, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(s->dhist, 0, sizeof(double) * B * 32));
     HIPCHK(hipMemset(s->dstep, 0, 2 * sizeof(int)));
+    if (s->seg && seg_zero(s)) return 1;
     HIPCHK(hipDeviceSynchronize());          // (the fills run on the NULL stream, the loop on the capsule's non-blocking one)
     s->step = 0;
     if (s->log_cap > 0) {
@@ -2351,6 +2374,22 @@ static int sim_enqueue_step(tum_sim *s, bool events)
     if (rc) s->c->lin_ahead = false;
     return rc;
 }
+// scores the control step whose solve is on the stream and whose plant step is not yet (tum_sim_segments_attach)
+static int sim_enqueue_segment_score(tum_sim *s)
+{
+    tum_ocp *c = s->c;
+    SegArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = c->N; a.batch = c->batch; a.n_ggv = c->d.n_ggv;
+    a.X = c->dX; a.status = c->dstatus; a.x_sim = s->dxsim; a.ref0 = s->dref0; a.closest = s->dclosest;
+    a.end_idx = s->dseg_end; a.ggv = s->dseg_ggv;
+    a.acc_min = c->d.acc_min; a.max_lat_dev = s->seg_max_lat; a.max_a_comb = s->seg_max_acomb;
+    a.steps = s->dseg_steps; a.state = s->dseg_state; a.qp_failures = s->dseg_qpf;
+    a.max_abs_lat = s->dseg_lat; a.sumsq_vel = s->dseg_ssq; a.max_acomb = s->dseg_acomb;
+    hipLaunchKernelGGL(segment_score_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 static int sim_enqueue_step_body(tum_sim *s, bool events)
 {
     tum_ocp *c = s->c;
@@ -2366,6 +2405,7 @@ static int sim_enqueue_step_body(tum_sim *s, bool events)
         HIPCHK(hipStreamWaitEvent(c->stream, s->evJ, 0));
     } else if (tum_sim_plan(s)) return 1;
     if (launch(c, events)) return 1;
+    if (s->seg && sim_enqueue_segment_score(s)) return 1;
     return tum_sim_advance(s);
 }
 
@@ -2445,6 +2485,115 @@ extern "C" int tum_sim_set_disturbances(tum_sim *s, const double *w_deriv, const
     return 0;
 }
 
+// Track segments of a weight sweep (Learning_To_Adapt/SafeRL_WMPC/BO_WMPC/objective_function.py:57-200): instance b is scored every control
+// step until the planner's index equals end_idx[b] or a crash test fires; groups are contiguous runs of instances.
+extern "C" int tum_sim_segments_attach(tum_sim *s, const int *end_idx, const int *group_offsets, int n_groups, double max_lat_dev, double max_a_comb)
+{
+    if (!s) return fail("null argument");
+    tum_ocp *c = s->c; const int B = c->batch;
+    if (end_idx) {
+        if (max_lat_dev != max_lat_dev || max_a_comb != max_a_comb) return fail("segments_attach: a threshold is NaN (an infinite one disables its crash test)");
+        if (group_offsets) {
+            if (n_groups < 1) return fail("segments_attach: n_groups < 1");
+            if (group_offsets[0] != 0 || group_offsets[n_groups] != B) return fail("segments_attach: group_offsets must start at 0 and end at batch");
+            for (int g = 0; g < n_groups; g++)
+                if (group_offsets[g + 1] <= group_offsets[g]) return fail("segments_attach: group_offsets must increase (no empty group)");
+        }
+    }
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }          // (a captured chunk holds the extra launch, or lacks it)
+    seg_release(s);
+    if (!end_idx) return 0;
+    std::vector<int> off;
+    if (group_offsets) off.assign(group_offsets, group_offsets + n_groups + 1);
+    else { n_groups = B; off.resize(B + 1); for (int i = 0; i <= B; i++) off[i] = i; }
+    double ggv[48];
+    for (int i = 0; i < 16; i++) { ggv[i] = c->d.ggv_v[i]; ggv[16 + i] = c->d.ggv_ax[i]; ggv[32 + i] = c->d.ggv_ay[i]; }
+    bool ok = true;
+    ok &= dalloc(&s->dseg_end, (size_t)B) == hipSuccess && dalloc(&s->dseg_off, (size_t)n_groups + 1) == hipSuccess;
+    ok &= dalloc(&s->dseg_steps, (size_t)B) == hipSuccess && dalloc(&s->dseg_state, (size_t)B) == hipSuccess && dalloc(&s->dseg_qpf, (size_t)B) == hipSuccess;
+    ok &= dalloc(&s->dseg_lat, (size_t)B) == hipSuccess && dalloc(&s->dseg_ssq, (size_t)B) == hipSuccess && dalloc(&s->dseg_acomb, (size_t)B) == hipSuccess;
+    ok &= dalloc(&s->dseg_ggv, (size_t)48) == hipSuccess && dalloc(&s->dseg_out, (size_t)4 * n_groups) == hipSuccess;
+    ok = ok && hipMemcpy(s->dseg_end, end_idx, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(s->dseg_off, off.data(), sizeof(int) * (n_groups + 1), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(s->dseg_ggv, ggv, sizeof(ggv), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { seg_release(s); (void)hipGetLastError(); return fail("segments_attach: device allocation failed"); }
+    s->seg = true; s->seg_groups = n_groups; s->seg_max_lat = max_lat_dev; s->seg_max_acomb = max_a_comb;
+    return 0;
+}
+
+// segments whose state word is still 0 (the loop's stream is idle)
+static int seg_count_active(tum_sim *s, int *active)
+{
+    std::vector<int> st(s->c->batch);
+    HIPCHK(hipMemcpy(st.data(), s->dseg_state, sizeof(int) * st.size(), hipMemcpyDeviceToHost));
+    int n = 0;
+    for (int v : st) n += v == 0;
+    *active = n;
+    return 0;
+}
+
+// tum_sim_run in chunks of check_every control steps until no segment is active or max_steps have run. The reference's
+// `while not done and not crash` has no cap; segments still active at the end have timed out (neither done nor crashed).
+extern "C" int tum_sim_run_segments(tum_sim *s, int max_steps, int check_every)
+{
+    if (!s || max_steps < 0) return fail("bad argument");
+    if (!s->seg) return fail("sim_run_segments: no segments attached (tum_sim_segments_attach)");
+    if (check_every <= 0) check_every = 100;
+    DevGuard guard(s->c->d.device); GUARD_OK(guard);
+    for (int done = 0; done < max_steps;) {
+        const int n = std::min(check_every, max_steps - done);
+        if (tum_sim_run(s, n)) return 1;
+        done += n;
+        int active = 0;
+        if (seg_count_active(s, &active)) return 1;
+        if (active == 0) break;
+    }
+    return 0;
+}
+
+static int seg_get(tum_sim *s, const std::string &f, double *out, long long len)
+{
+    tum_ocp *c = s->c; const long long B = c->batch;
+    if (!s->seg) return fail("sim_get " + f + ": no segments attached (tum_sim_segments_attach)");
+    if (f == "seg_active") {
+        if (len != 1) return fail("sim_get seg_active: len != 1");
+        int n = 0;
+        if (seg_count_active(s, &n)) return 1;
+        out[0] = n;
+        return 0;
+    }
+    if (f == "seg_groups") {
+        if (len != 4LL * s->seg_groups) return fail("sim_get seg_groups: len != 4 * n_groups");
+        hipLaunchKernelGGL(segment_group_kernel, dim3(s->seg_groups), dim3(64), 0, c->stream, s->dseg_off, s->seg_groups, s->dseg_steps,
+                           s->dseg_state, s->dseg_lat, s->dseg_ssq, s->dseg_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(out, s->dseg_out, sizeof(double) * len, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (len != B) return fail("sim_get " + f + ": len != batch");
+    const int *isrc = f == "seg_steps" ? s->dseg_steps : f == "seg_state" ? s->dseg_state : f == "seg_qp_failures" ? s->dseg_qpf : nullptr;
+    if (isrc) {
+        std::vector<int> t(B);
+        HIPCHK(hipMemcpy(t.data(), isrc, sizeof(int) * B, hipMemcpyDeviceToHost));
+        for (long long i = 0; i < B; i++) out[i] = t[i];
+        return 0;
+    }
+    if (f == "seg_max_lat_dev") { HIPCHK(hipMemcpy(out, s->dseg_lat, sizeof(double) * B, hipMemcpyDeviceToHost)); return 0; }
+    if (f == "seg_max_a_comb") { HIPCHK(hipMemcpy(out, s->dseg_acomb, sizeof(double) * B, hipMemcpyDeviceToHost)); return 0; }
+    if (f == "seg_rms_vel_dev") {          // sqrt(sumsq_vel / steps): get_root_mean_square of objective_function.py:184 (0 before the first step)
+        std::vector<int> t(B);
+        HIPCHK(hipMemcpy(t.data(), s->dseg_steps, sizeof(int) * B, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out, s->dseg_ssq, sizeof(double) * B, hipMemcpyDeviceToHost));
+        for (long long i = 0; i < B; i++) out[i] = t[i] > 0 ? std::sqrt(out[i] / (double)t[i]) : 0.0;
+        return 0;
+    }
+    return fail("sim_get: unknown field '" + f + "'");
+}
+
 extern "C" int tum_sim_get(tum_sim *s, const char *field, double *out, long long len)
 {
     if (!s || !field || !out) return fail("null argument");
@@ -2455,6 +2604,7 @@ extern "C" int tum_sim_get(tum_sim *s, const char *field, double *out, long long
     if (flush_inputs(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     const double *src = nullptr; long long want = 0;
+    if (f.compare(0, 4, "seg_") == 0) return seg_get(s, f, out, len);
     if (f == "x_sim") { src = s->dxsim; want = B * 7; }
     else if (f == "x_mpc") { src = c->dx0; want = B * 8; }
     else if (f == "pose") { src = s->dpose; want = B * 2; }

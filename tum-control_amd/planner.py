@@ -22,12 +22,18 @@ def load_track(name):
         return d[name].copy()
 
 
+def closest_index(track, pose_xy):
+    """The planner's current_ref_idx: first nearest waypoint of every pose; pose_xy (..., 2) -> (...) integers."""
+    pose_xy = np.asarray(pose_xy, dtype=float)
+    d2 = (track[:, 0] - pose_xy[..., 0:1]) ** 2 + (track[:, 1] - pose_xy[..., 1:2]) ** 2
+    return np.argmin(d2, axis=-1)
+
+
 def planner_emulator(track, pose_xy, n_points, Tp, loop_circuit=True):
     """Returns (closest_index, ref) with ref an (n_points, 4) array [pos_x, pos_y, ref_yaw, ref_v]."""
     px, py, yaw, v = track[:, 0], track[:, 1], track[:, 2], track[:, 3]
     n = len(px)
-    d2 = (px - pose_xy[0]) ** 2 + (py - pose_xy[1]) ** 2
-    i0 = int(np.argmin(d2))
+    i0 = int(closest_index(track, pose_xy))
     idx = [i0]
     T = 0.0
     while T <= Tp:

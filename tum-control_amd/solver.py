@@ -75,7 +75,8 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_ocp_bounds_snapshot", "tum_ocp_bounds_restore", "tum_ocp_r2_backoff", "tum_ocp_r2_attach", "tum_ocp_constraints_get",
              "tum_ocp_snmpc_attach", "tum_ocp_snmpc_samples", "tum_ocp_snmpc_set_offsets",
              "tum_planner_emulate", "tum_sim_create", "tum_sim_free", "tum_sim_set_state", "tum_sim_plan", "tum_sim_advance",
-             "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances"]
+             "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
+             "tum_sim_segments_attach", "tum_sim_run_segments"]
 
 
 def load_library(path=None):
@@ -150,6 +151,9 @@ def load_library(path=None):
     L.tum_sim_get.argtypes = [vp, cs, dp, ctypes.c_longlong]
     if hasattr(L, "tum_sim_set_disturbances"):
         L.tum_sim_set_disturbances.argtypes = [vp, dp, dp, ci]
+    if hasattr(L, "tum_sim_segments_attach"):
+        L.tum_sim_segments_attach.argtypes = [vp, ip, ip, ci, cd, cd]
+        L.tum_sim_run_segments.argtypes = [vp, ci, ci]
     _libs[p] = L
     if p == LIB_PATH:
         _lib = L
@@ -806,3 +810,58 @@ class DeviceClosedLoop:
 
     def logs(self):
         return {k: self.get(k) for k in ("CiLX", "MPC_SimX", "simU", "simREF", "simSolverDebug")}
+
+    # ---- track segments: what a weight sweep runs the loop for (BO_WMPC/objective_function.py:57-200)
+    SEG_DONE, SEG_CRASH_LAT, SEG_CRASH_ACOMB = 1, 2, 4          # bits of a segment's state word (0: active)
+
+    def attach_segments(self, end_idx, max_lat_dev, max_a_comb, group_offsets=None):
+        """Score every instance on its own track segment from now on: end_idx (B,) planner index that ends it (< 0: never),
+        crash thresholds of the signed lateral deviation and of the combined acceleration (inf: no test), group_offsets
+        (n_groups + 1,) contiguous groups of instances for segment_groups() (None: one group per instance)."""
+        end = np.ascontiguousarray(np.broadcast_to(end_idx, (self.B,)), dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        off, ng = None, 0
+        if group_offsets is not None:
+            off = np.ascontiguousarray(group_offsets, dtype=np.int32).reshape(-1)
+            ng = len(off) - 1
+        self._chk(self._L.tum_sim_segments_attach(self._s, end.ctypes.data_as(ip), None if off is None else off.ctypes.data_as(ip), ng,
+                                                  float(max_lat_dev), float(max_a_comb)), "sim_segments_attach")
+        self.n_groups = ng if off is not None else self.B
+
+    def detach_segments(self):
+        self._chk(self._L.tum_sim_segments_attach(self._s, None, None, 0, 0.0, 0.0), "sim_segments_attach")
+        self.n_groups = 0
+
+    def run_segments(self, max_steps, check_every=0):
+        """run() in chunks of check_every steps (0: 100) until every segment is done or crashed, or max_steps have run"""
+        self._chk(self._L.tum_sim_run_segments(self._s, int(max_steps), int(check_every)), "sim_run_segments")
+
+    def _seg_get(self, field, n):
+        out = np.empty(n)
+        self._chk(self._L.tum_sim_get(self._s, field.encode(), _dp(out), out.size), "sim_get " + field)
+        return out
+
+    @property
+    def segments_active(self):
+        return int(self._seg_get("seg_active", 1)[0])
+
+    def segments(self):
+        """Per-instance scores: steps, state, max_lat_dev (max |lat_dev|), rms_vel_dev, max_a_comb, qp_failures, and the booleans
+        derived from the state word -- crashed (any crash bit; wins over done), done, timed_out (still active)."""
+        B = self.B
+        d = {k: self._seg_get("seg_" + k, B) for k in ("max_lat_dev", "rms_vel_dev", "max_a_comb")}
+        for k in ("steps", "state", "qp_failures"):
+            d[k] = self._seg_get("seg_" + k, B).astype(np.int64)
+        d.update(segment_flags(d["state"]))
+        return d
+
+    def segment_groups(self):
+        """(n_groups, 4): mean of -max|lat_dev|, mean of -rms(vel_dev), segments, segments not cleanly done (crashed or active)"""
+        return self._seg_get("seg_groups", 4 * self.n_groups).reshape(self.n_groups, 4)
+
+
+def segment_flags(state):
+    """crashed / done / timed_out of segment state words: crash wins over done, a segment still active has timed out"""
+    state = np.asarray(state)
+    crashed = (state & (DeviceClosedLoop.SEG_CRASH_LAT | DeviceClosedLoop.SEG_CRASH_ACOMB)) != 0
+    return dict(crashed=crashed, done=((state & DeviceClosedLoop.SEG_DONE) != 0) & ~crashed, timed_out=state == 0)
