@@ -442,6 +442,43 @@ int tum_sim_segments_attach(tum_sim *s, const int *end_idx, const int *group_off
  * still active; one reduction kernel per read, fixed summation order). */
 int tum_sim_run_segments(tum_sim *s, int max_steps, int check_every);
 
+/* ---- the weight-scheduling RL environment (Learning_To_Adapt/SafeRL_WMPC/RL_WMPC/environment.py:112-240, reward.py:15-33,
+ * observation.py:28-75) around the loop: every n_mpc_steps control steps an agent picks, per instance, one row
+ * [q_xy, q_yaw, q_vel, r_jerk, r_steer, L1, L2] of `table` (n_actions x 7, host; NMPC_class.py:269-317 update_cost_function_weights:
+ * the words written are those of the cost setter -- diag W at the stages 0..N-1, its first four entries at stage N, zl = zu = L1 and
+ * Zl = Zu = L2 of every slack). Once attached, every control step scores every instance whose environment step has not ended, between
+ * the solve and the plant step (Utils/Logging_Plotting.py:152-159: lat_dev signed, vel_dev), then latches truncated = lat_dev >
+ * max_lat_dev (environment.py:153-158,239-240) and terminated = full_lap ? planner index == n_track - 2 (an equality) :
+ * episode_steps == episode_length (environment.py:160-165). The step that sets a flag is counted, nothing after it is; the instance
+ * keeps driving unscored. episode_steps counts ENVIRONMENT steps (environment.py:115), so the last environment step of an episode ends
+ * after its first control step.
+ * sigmas: 2, lims: 4 = lims[0][lat, vel], lims[1][lat, vel] (reward.py: exp(-sum(clip((rms - lims[0]) / (lims[1] - lims[0]), 0, 1)^2 /
+ * (2 sigmas)))). Observation of 2 + 2 n_samples entries: [lat_dev, vel_dev], ref_v at idx_v, the 10-tap average of
+ * diff(unwrap(ref_yaw)) / Ts at idx_yawrate (np.linspace(0, len - 1, n_samples, dtype=int) of observation.py:58-59, computed by the
+ * caller; Ts is the loop's although the points are Tp / N apart), normalised with obs_lo / obs_hi (observation.py:16-24). obs_states 0:
+ * the first two entries are 0 before normalisation, as in the reference (Logging_Plotting.py:307-312 reads the row BEHIND the last one
+ * written); 1: those of the last scored control step. Needs 10 <= N <= 127.
+ * Refused: SNMPC, R2 and full-W capsules, SQP mode, rti_phase 1 / 2, the development kernel 'fused', a loop with segments attached (and
+ * segments on a loop with an environment). table == NULL detaches. Either way a captured chunk of the run function is dropped. While
+ * attached the state estimator counts its samples per instance (a reset empties one instance's buffers); disturbance playback and the
+ * logs stay indexed by the loop's global step. The state function (set_state) zeroes the environment's counters. */
+int tum_sim_env_attach(tum_sim *s, const double *table, int n_actions, int n_mpc_steps, double max_lat_dev, int episode_length, int full_lap,
+                       const double *sigmas, const double *lims, const double *obs_lo, const double *obs_hi,
+                       const int *idx_v, const int *idx_yawrate, int n_samples, int obs_states);
+/* environment.py:191-237 for the instances with mask[b] != 0 (mask == NULL: all): plant and controller state of waypoint start_idx[b]
+ * (yaw mod 2 pi, everything else 0), empty estimator, cold iterate (X_k = x0, U = 0, cold interior point method), episode counters 0.
+ * Nothing else of the batch changes. */
+int tum_sim_env_reset(tum_sim *s, const int *mask, const int *start_idx);
+/* environment.py:112-189 for the whole batch: one upload (actions, reset mask, start indices: batch ints each; the last two may be
+ * NULL), the resets, the actions, n_mpc_steps control steps, one download. out: batch x (6 + 2 + 2 n_samples) doubles -- reward,
+ * terminated, truncated, step_length, failed solves among the scored steps, planner error word, observation. An action outside the
+ * table, and stepping an instance whose episode has ended without marking it for reset, are errors; nothing runs then. reset_mask[b]:
+ * 0 nothing, 1 reset, 2 an instance whose episode has ended drives on as it is (scoring a loop nothing restarts: episode_steps keeps
+ * counting, so `terminated`, an equality, is not set again). */
+int tum_sim_env_step(tum_sim *s, const int *actions, const int *reset_mask, const int *start_idx, double *out);
+/* More fields of the get function, B values each, an error when no environment is attached: "env_episode_steps", "env_step_length",
+ * "env_flags" (1 terminated, 2 truncated), "env_qp_failures", "env_samples" (samples the estimator has seen), "env_ended". */
+
 /* development aid: one solve with in-kernel phase timers; out = batch x 12 shader-cycle counters
  * [linearise, condense, ipm-residuals, M assembly, Cholesky, rhs, tri-solves, row updates, (iteration tail), expand+cost] */
 int tum_ocp_profile_phases(tum_ocp *c, long long *out);

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import config as _config
 from .planner import closest_index, load_track, planner_emulator, yref_from_ref
-from .solver import BatchedOcpSolver, CoupledSnmpcSolver, DeviceClosedLoop, segment_flags
+from .solver import BatchedOcpSolver, CoupledSnmpcSolver, DeviceClosedLoop, env_observation_bounds, segment_flags
 
 WINDOWS = (1, 1, 4, 2, 2, 3, 4, 2)          # SimulationMode_main_class.py:86
 
@@ -485,3 +485,149 @@ def evaluate_segments(track_name, params, segment_groups, max_lat_dev, max_a_com
     cl.dev.run_segments(max_steps, check_every)
     objectives, feasible = _objectives_from_groups(cl.dev.segment_groups().reshape(P, len(sizes), 4))
     return objectives, feasible, cl.dev.segments()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The weight-scheduling RL environment (Learning_To_Adapt/SafeRL_WMPC/RL_WMPC/environment.py:112-240): every n_mpc_steps control
+# steps an agent installs one row of a parameter table per vehicle; the environment answers with a reward and an observation.
+# Host statements of what env_finish_kernel computes, and the environment itself.
+
+def rl_observation(ref_yaw, ref_v, Ts, n_samples, lat_dev, vel_dev):
+    """ObservationGenerator.get_observation (RL_WMPC/observation.py:28-75) of one local reference: [lat_dev, vel_dev], n_samples points
+    of ref_v and of the yaw rate -- diff(unwrap(ref_yaw)) / Ts smoothed by a 10-tap moving average ('valid') -- at
+    np.linspace(0, len - 1, n_samples, dtype=int) of each, normalised with the bounds of observation.py:16-24. Ts is the loop's
+    sampling time although the points of the window are Tp / N apart: the reference's choice (environment.py:180)."""
+    ref_v = np.asarray(ref_v, dtype=float)
+    yaw_rate = np.diff(np.unwrap(np.asarray(ref_yaw, dtype=float))) / Ts
+    yaw_rate = np.convolve(yaw_rate, np.ones(10) / 10, mode='valid')
+    iv = np.linspace(0, len(ref_v) - 1, n_samples, dtype=int)
+    ir = np.linspace(0, len(yaw_rate) - 1, n_samples, dtype=int)
+    obs = np.concatenate((np.array([lat_dev, vel_dev]), ref_v[iv], yaw_rate[ir]))
+    b = env_observation_bounds(n_samples)
+    return (obs - b[0]) / (b[1] - b[0])
+
+
+def rl_reward(lat_devs, vel_devs, sigmas, lims):
+    """RewardGenerator.get_reward (RL_WMPC/reward.py:15-33) of the scored control steps of one environment step:
+    exp(-sum(clip((m - lims[0]) / (lims[1] - lims[0]), 0, 1)^2 / (2 sigmas))), m = [rms(lat_devs), rms(vel_devs)]. lims[0] / lims[1]
+    broadcast over m as numpy does: (2, 2) rows lower / upper per metric; the FLAT list environment.py:79-82 builds from the shipped
+    rl_config.yaml, [0, 0.4, 0, 1], normalises both metrics with 0 .. 0.4."""
+    lat_devs, vel_devs = np.asarray(lat_devs, dtype=float), np.asarray(vel_devs, dtype=float)
+    sigmas, lims = np.array(sigmas), np.array(lims)
+    m = np.array([np.sqrt(np.mean(lat_devs ** 2)), np.sqrt(np.mean(vel_devs ** 2))])
+    m_nor = np.clip((m - lims[0]) / (lims[1] - lims[0]), 0., 1.)
+    return 1.0 * np.exp(-np.sum(np.power(m_nor, 2) / (2 * sigmas)))
+
+
+RL_SIGMAS = (0.1, 0.5)                       # _config/rl_config.yaml:33
+RL_LIMS = (0.0, 0.4, 0.0, 1.0)               # rew_lims_lat_dev + rew_lims_vel_dev as environment.py:79-82 concatenates them (flat: see rl_reward)
+
+
+def rl_env_steps_from_logs(logs, track, actions_per_step, n_mpc_steps, max_lat_dev=2.0, episode_length=128, sigmas=RL_SIGMAS,
+                           lims=RL_LIMS, n_samples=10, full_lap=False, obs_states="reference", N=38, Tp=3.04, Ts=0.02, first_step=0):
+    """The episode rules of RLEnvironment.step (environment.py:112-189) replayed on the five raw logs of a run that nothing reset: the
+    host statement of what the device environment returns. Environment step e (one row of actions_per_step, (E, B); only its length is
+    used -- the weights are in the logs already) covers the control steps first_step + e n_mpc_steps .. + n_mpc_steps - 1.
+    Per instance: episode_steps += 1 (once per ENVIRONMENT step), then per control step lat_dev / vel_dev of
+    segment_step_channels, truncated = lat_dev > max_lat_dev (signed), terminated = (planner index of the pose == len(track) - 2)
+    with full_lap, else (episode_steps == episode_length); the step that sets a flag is counted, nothing after it is. Reward over the
+    counted steps; observation from the planner's window at the last counted step, its first two entries 0 before normalisation with
+    obs_states 'reference' (Logger.get_observation_states reads the row behind the last one written) or the last counted step's
+    lat_dev / vel_dev with 'last_step'.
+    Returns a dict of (E, B[, 2 + 2 n_samples]) arrays: reward, observation, terminated, truncated, step_length, qp_failures."""
+    if obs_states not in ("reference", "last_step"):
+        raise ValueError("obs_states must be 'reference' or 'last_step'")
+    CiLX, REF, DBG = (np.asarray(logs[k]) for k in ("CiLX", "simREF", "simSolverDebug"))
+    E, B = len(actions_per_step), REF.shape[1]
+    if first_step + E * n_mpc_steps > REF.shape[0]:
+        raise ValueError("rl_env_steps_from_logs: the logs are shorter than the environment steps asked for")
+    out = dict(reward=np.zeros((E, B)), observation=np.zeros((E, B, 2 + 2 * n_samples)), terminated=np.zeros((E, B), dtype=bool),
+               truncated=np.zeros((E, B), dtype=bool), step_length=np.zeros((E, B), dtype=np.int64), qp_failures=np.zeros((E, B), dtype=np.int64))
+    episode_steps = np.zeros(B, dtype=np.int64)
+    for e in range(E):
+        episode_steps += 1
+        s0 = first_step + e * n_mpc_steps
+        for b in range(B):
+            lats, vels = [], []
+            terminated = truncated = False
+            for s in range(s0, s0 + n_mpc_steps):
+                _, lat = lon_lat_deviations(CiLX[s, b, 2], CiLX[s, b, 0], CiLX[s, b, 1], REF[s, b, 0], REF[s, b, 1])
+                lats.append(lat); vels.append(CiLX[s, b, 3] - REF[s, b, 3])
+                out["qp_failures"][e, b] += DBG[s, b, 4] != 0
+                truncated = bool(lat > max_lat_dev)
+                if full_lap:
+                    terminated = bool(closest_index(track, CiLX[s, b, :2]) == len(track) - 2)
+                else:
+                    terminated = bool(episode_steps[b] == episode_length)
+                if terminated or truncated:
+                    break
+            _, ref = planner_emulator(track, CiLX[s, b, :2], N + 1, Tp, True)
+            last = (lats[-1], vels[-1]) if obs_states == "last_step" else (0.0, 0.0)
+            out["reward"][e, b] = rl_reward(lats, vels, sigmas, lims)
+            out["observation"][e, b] = rl_observation(ref[:, 2], ref[:, 3], Ts, n_samples, *last)
+            out["terminated"][e, b], out["truncated"][e, b], out["step_length"][e, b] = terminated, truncated, len(lats)
+    return out
+
+
+class WeightScheduleEnv:
+    """n_envs copies of the reference's RLEnvironment (RL_WMPC/environment.py) on one track as ONE batched environment whose state stays
+    on the device: reset() -> (obs, info), step(actions) -> (obs, reward, terminated, truncated, info), arrays over the n_envs axis.
+    actions: the (A, 7) parameter table the integer actions index (rows as in update_cost_function_weights; the reference's
+    actions_file). info: terminal_observation (the observation of the step itself, also where obs was replaced by a reset's zeros),
+    step_length, qp_failures.
+    auto_reset (as a VecEnv): an instance whose episode ended is reset at the start of the next step() to a waypoint drawn from
+    restart_indices with numpy.random.RandomState(seed) (environment.py:195-198; one randint per reset instance, in instance order,
+    reset() draws n_envs first), and the observation step() returns for it is already the zeros of reset(). auto_reset=False never
+    resets: an ended instance drives on and is scored on -- for scoring a run; restart instances with reset(mask) where wanted.
+    One object per track (the reference's trajectories[i % n_trajs] becomes one object each). No gymnasium / stable_baselines3 needed."""
+
+    def __init__(self, track_name, n_envs, actions, n_mpc_steps=20, max_lat_dev=2.0, episode_length=128, rew_sigmas=RL_SIGMAS,
+                 rew_lims=RL_LIMS, obs_n_anticipation_points=10, full_lap=False, restart_indices=(0,), auto_reset=True, seed=0,
+                 obs_states="reference", **loop_kw):
+        self.table = np.ascontiguousarray(actions, dtype=float).reshape(-1, 7)
+        self.n_envs, self.n_actions, self.n_mpc_steps = int(n_envs), len(self.table), int(n_mpc_steps)
+        self.n_observations = 2 + 2 * int(obs_n_anticipation_points)
+        self.restart_indices = np.atleast_1d(np.asarray(restart_indices, dtype=np.int64))
+        self.auto_reset = bool(auto_reset)
+        self._rng = np.random.RandomState(seed)
+        for k in ("on_device", "controller", "batch", "params"):
+            if k in loop_kw:
+                raise ValueError(f"WeightScheduleEnv: '{k}' is the environment's to set")
+        # (idx_start among loop_kw: where the loops stand until the first reset() -- one waypoint or one per instance)
+        loop_kw.setdefault("idx_start", int(self.restart_indices[0]))
+        self.loop = ClosedLoopBatch(track_name, batch=self.n_envs, on_device=True, controller="nominal", **loop_kw)
+        self.dev = self.loop.dev
+        self.dev.attach_env(self.table, n_mpc_steps, max_lat_dev, episode_length, rew_sigmas, rew_lims, obs_n_anticipation_points,
+                            full_lap=full_lap, obs_states=obs_states)
+        self._ended = np.zeros(self.n_envs, dtype=bool)
+
+    def _draw(self, n):
+        return self.restart_indices[self._rng.randint(0, len(self.restart_indices), size=n)]
+
+    def reset(self, mask=None):
+        """environment.py:191-237 for every instance (or those of the boolean mask): start waypoints drawn from restart_indices;
+        the observation of a reset is all zeros (environment.py:230-233)."""
+        m = np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
+        start = np.zeros(self.n_envs, dtype=np.int64)
+        start[m] = self._draw(int(m.sum()))
+        self.dev.env_reset(start, m)
+        self._ended[m] = False
+        self.last_start = start
+        return np.zeros((self.n_envs, self.n_observations)), {}
+
+    def step(self, actions):
+        mask = np.zeros(self.n_envs, dtype=np.int32)
+        start = np.zeros(self.n_envs, dtype=np.int64)
+        if self.auto_reset:
+            mask[self._ended] = 1
+            start[self._ended] = self._draw(int(self._ended.sum()))
+        else:
+            mask[self._ended] = 2
+        r = self.dev.env_step(actions, mask, start)
+        self.last_start = start
+        self._ended = r["terminated"] | r["truncated"]
+        obs = r["observation"]
+        info = dict(terminal_observation=obs.copy(), step_length=r["step_length"], qp_failures=r["qp_failures"])
+        if self.auto_reset:
+            obs[self._ended] = 0.0
+        return obs, r["reward"], r["terminated"], r["truncated"], info

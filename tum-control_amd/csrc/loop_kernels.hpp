@@ -213,6 +213,10 @@ struct SimArgs {
     // the state DERIVATIVES, constant over a control step, and additive STATE ESTIMATION error, [step][b][7] each, dist_len steps
     const double *dist_w, *dist_e; int dist_len;
     double *lCiLX, *lSimX, *lU, *lREF, *lDBG;         // logs (nullable): (cap+1,B,7) (cap+1,B,8) (cap,B,2) (cap,B,4) (cap,B,5)
+    // samples the estimator of instance b has seen ([b], nullable: the global step counter, every instance started together). The RL
+    // environment restarts single instances (env_kernels.hpp: env_begin_kernel zeroes the word): read and incremented here. Disturbance
+    // playback and the logs stay indexed by the loop's GLOBAL step either way.
+    int *samples;
 };
 
 // Four lanes per instance (see plant_xdot): simMode 0 of sim_step. The plant takes the predicted acceleration of stage 1
@@ -321,7 +325,7 @@ __global__ void __launch_bounds__(64) plant_advance_kernel(const SimArgs sa)
             sa.pose[(size_t)b * 2] = x[0]; sa.pose[(size_t)b * 2 + 1] = x[1];
         }
         // state estimation: sample number k (1-based) goes to ring slot (k-1) & 3; this lane filters states role and role + 4
-        const int k = step + 1;
+        const int k = (sa.samples ? sa.samples[b] : step) + 1;
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const int i = role + 4 * j;
@@ -336,6 +340,7 @@ __global__ void __launch_bounds__(64) plant_advance_kernel(const SimArgs sa)
             for (int t = k - cnt + 1; t < k; t++) s = s + ((t == k - 1) ? v : hst[t & 3]);
             sa.x0[(size_t)b * NX + i] = s / (double)cnt;
         }
+        if (sa.samples && role == 0) sa.samples[b] = k;          // (behind the ring-buffer stores, whose addresses every lane of the quad derived from k)
         if (sa.lCiLX && step < sa.log_cap) {
             const size_t s = step;
             if (role == 0) {

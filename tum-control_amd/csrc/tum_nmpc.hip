@@ -20,6 +20,7 @@
 #endif
 #include "aux_kernels.hpp"
 #include "loop_kernels.hpp"
+#include "env_kernels.hpp"
 #include "sqp_kernels.hpp"
 #include "rti_kernels.hpp"
 
@@ -2206,7 +2207,35 @@ struct tum_sim {
     bool seg; int seg_groups; double seg_max_lat, seg_max_acomb;
     int *dseg_end, *dseg_off, *dseg_steps, *dseg_state, *dseg_qpf;
     double *dseg_lat, *dseg_ssq, *dseg_acomb, *dseg_ggv, *dseg_out;
+    // RL environment (tum_sim_env_attach): the settings as the kernels take them, the table / indices / bounds and the per-instance state
+    // on the device, pinned staging of the one upload and the one download of an environment step, and which episodes have ended (host)
+    bool env; int env_mpc_steps, env_rec; EnvArgs ea;
+    double *denv_table, *denv_bounds, *denv_acc, *denv_win, *denv_out, *henv_out;
+    int *denv_idx, *denv_in, *denv_ep, *denv_count, *denv_flags, *denv_qpf, *denv_samples, *henv_in;
+    unsigned char *env_ended;
 };
+static void env_release(tum_sim *s)
+{
+    (void)hipFree(s->denv_table); (void)hipFree(s->denv_bounds); (void)hipFree(s->denv_acc); (void)hipFree(s->denv_win); (void)hipFree(s->denv_out);
+    (void)hipFree(s->denv_idx); (void)hipFree(s->denv_in); (void)hipFree(s->denv_ep); (void)hipFree(s->denv_count); (void)hipFree(s->denv_flags);
+    (void)hipFree(s->denv_qpf); (void)hipFree(s->denv_samples);
+    if (s->henv_out) (void)hipHostFree(s->henv_out);
+    if (s->henv_in) (void)hipHostFree(s->henv_in);
+    free(s->env_ended);
+    s->denv_table = s->denv_bounds = s->denv_acc = s->denv_win = s->denv_out = s->henv_out = nullptr;
+    s->denv_idx = s->denv_in = s->denv_ep = s->denv_count = s->denv_flags = s->denv_qpf = s->denv_samples = s->henv_in = nullptr;
+    s->env_ended = nullptr; s->env = false;
+}
+// episode counters, step accumulators, flags and the estimator's sample numbers back to zero (fills on the NULL stream: the caller synchronises)
+static int env_zero(tum_sim *s)
+{
+    const size_t B = s->c->batch;
+    HIPCHK(hipMemset(s->denv_ep, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->denv_count, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->denv_flags, 0, sizeof(int) * B));
+    HIPCHK(hipMemset(s->denv_qpf, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->denv_samples, 0, sizeof(int) * B));
+    HIPCHK(hipMemset(s->denv_acc, 0, sizeof(double) * B * 4));
+    memset(s->env_ended, 0, B);
+    return 0;
+}
 static void seg_release(tum_sim *s)
 {
     (void)hipFree(s->dseg_end); (void)hipFree(s->dseg_off); (void)hipFree(s->dseg_steps); (void)hipFree(s->dseg_state); (void)hipFree(s->dseg_qpf);
@@ -2263,6 +2292,7 @@ extern "C" void tum_sim_free(tum_sim *s)
     (void)hipFree(s->lCiLX); (void)hipFree(s->lSimX); (void)hipFree(s->lU); (void)hipFree(s->lREF); (void)hipFree(s->lDBG);
     (void)hipFree(s->ddw); (void)hipFree(s->dde);
     seg_release(s);
+    env_release(s);
     delete s;
 }
 
@@ -2312,6 +2342,7 @@ extern "C" int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *
     HIPCHK(hipMemset(s->dhist, 0, sizeof(double) * B * 32));
     HIPCHK(hipMemset(s->dstep, 0, 2 * sizeof(int)));
     if (s->seg && seg_zero(s)) return 1;
+    if (s->env && env_zero(s)) return 1;
     HIPCHK(hipDeviceSynchronize());          // (the fills run on the NULL stream, the loop on the capsule's non-blocking one)
     s->step = 0;
     if (s->log_cap > 0) {
@@ -2354,6 +2385,7 @@ extern "C" int tum_sim_advance(tum_sim *s)
     sa.x_sim = s->dxsim; sa.x0 = c->dx0; sa.pose = s->dpose; sa.hist = s->dhist; sa.ref0 = s->dref0;
     sa.lCiLX = s->lCiLX; sa.lSimX = s->lSimX; sa.lU = s->lU; sa.lREF = s->lREF; sa.lDBG = s->lDBG;
     sa.dist_w = s->ddw; sa.dist_e = s->dde; sa.dist_len = s->dist_len;
+    sa.samples = s->env ? s->denv_samples : nullptr;
     hipLaunchKernelGGL(plant_advance_kernel, dim3((c->batch * PLANT_LANES + 63) / 64), dim3(64), 0, c->stream, sa);
     HIPCHK(hipGetLastError());
     s->step++;
@@ -2366,6 +2398,7 @@ extern "C" int tum_sim_advance(tum_sim *s)
 // kernel arguments never change.
 static const int GRAPH_STEPS = 25;
 static int sim_enqueue_step_body(tum_sim *s, bool events);
+static void env_bind(tum_sim *s);
 static int sim_enqueue_step(tum_sim *s, bool events)
 {
     // whatever goes wrong between the forked linearisation and the solve that consumes it (planner, join, a failed capture): the
@@ -2406,12 +2439,17 @@ static int sim_enqueue_step_body(tum_sim *s, bool events)
     } else if (tum_sim_plan(s)) return 1;
     if (launch(c, events)) return 1;
     if (s->seg && sim_enqueue_segment_score(s)) return 1;
+    if (s->env) {          // scores the control step whose solve is on the stream and whose plant step is not yet (tum_sim_env_attach)
+        env_bind(s);
+        hipLaunchKernelGGL(env_score_kernel, dim3(c->batch), dim3(64), 0, c->stream, s->ea);
+        HIPCHK(hipGetLastError());
+    }
     return tum_sim_advance(s);
 }
 
-extern "C" int tum_sim_run(tum_sim *s, int nsteps)
+// the control steps of tum_sim_run on the capsule's stream, without the wait behind them
+static int sim_run_enqueue(tum_sim *s, int nsteps)
 {
-    if (!s || nsteps < 0) return fail("bad argument");
     tum_ocp *c = s->c;
     if (c->nlp_type) return fail("sim_run: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
     if (c->rti_phase) return fail("sim_run: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
@@ -2456,6 +2494,15 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
     }
     for (; done < nsteps; done++)
         if (sim_enqueue_step(s, true)) return 1;
+    return 0;
+}
+
+extern "C" int tum_sim_run(tum_sim *s, int nsteps)
+{
+    if (!s || nsteps < 0) return fail("bad argument");
+    tum_ocp *c = s->c;
+    if (sim_run_enqueue(s, nsteps)) return 1;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
     HIPCHK(hipStreamSynchronize(c->stream));
     int err = 0;
     HIPCHK(hipMemcpy(&err, s->derr, sizeof(int), hipMemcpyDeviceToHost));
@@ -2491,6 +2538,7 @@ extern "C" int tum_sim_segments_attach(tum_sim *s, const int *end_idx, const int
 {
     if (!s) return fail("null argument");
     tum_ocp *c = s->c; const int B = c->batch;
+    if (end_idx && s->env) return fail("segments_attach: this loop is an RL environment (tum_sim_env_attach): an instance is scored by one set of rules; detach the environment first");
     if (end_idx) {
         if (max_lat_dev != max_lat_dev || max_a_comb != max_a_comb) return fail("segments_attach: a threshold is NaN (an infinite one disables its crash test)");
         if (group_offsets) {
@@ -2554,6 +2602,177 @@ extern "C" int tum_sim_run_segments(tum_sim *s, int max_steps, int check_every)
     return 0;
 }
 
+
+// ---------------------------------------------------------------------------------------------- K11: RL environment
+// what the environment cannot run on, at attach time and again at every step (a capsule can change behind an attached environment)
+static int env_refuse(const tum_sim *s, const char *who)
+{
+    const tum_ocp *c = s->c;
+    const std::string w(who);
+    if (c->sn) return fail(w + ": the RL environment runs the nominal OCP; this is a coupled SNMPC capsule");
+    if (c->r2) return fail(w + ": the RL environment runs the nominal OCP; this capsule has the R2 back-off attached (its reset restores bounds the environment does not know)");
+    if (c->dWf) return fail(w + ": the RL environment installs a diagonal W (update_cost_function_weights); this capsule keeps a full W");
+    if (c->nlp_type) return fail(w + ": the RL environment runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
+    if (c->rti_phase) return fail(w + ": the RL environment runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
+    if (c->kmode == KMode::FUSED || (c->ka.flags & KF_DEBUG)) return fail(w + ": the RL environment runs on the pipeline, not on the development kernel 'fused'");
+    if (s->seg) return fail(w + ": this loop has track segments attached (tum_sim_segments_attach): an instance is scored by one set of rules; detach them first");
+    return 0;
+}
+
+extern "C" int tum_sim_env_attach(tum_sim *s, const double *table, int n_actions, int n_mpc_steps, double max_lat_dev, int episode_length, int full_lap,
+                                  const double *sigmas, const double *lims, const double *obs_lo, const double *obs_hi,
+                                  const int *idx_v, const int *idx_yawrate, int n_samples, int obs_states)
+{
+    if (!s) return fail("null argument");
+    tum_ocp *c = s->c; const size_t B = c->batch; const int N = c->N;
+    if (table) {
+        if (!sigmas || !lims || !obs_lo || !obs_hi || !idx_v || !idx_yawrate) return fail("null argument");
+        if (env_refuse(s, "env_attach")) return 1;
+        if (n_actions < 1 || n_mpc_steps < 1 || episode_length < 1 || n_samples < 1) return fail("env_attach: n_actions, n_mpc_steps, episode_length and n_samples must be >= 1");
+        if (N < ENV_MA || N + 1 > ENV_MAXPTS) return fail("env_attach: the observation's 10-tap moving average of the yaw rate needs 10 <= N <= 127");
+        if (max_lat_dev != max_lat_dev) return fail("env_attach: max_lat_dev is NaN (an infinite one disables the crash test)");
+        if (obs_states != 0 && obs_states != 1) return fail("env_attach: obs_states must be 0 (reference) or 1 (last_step)");
+        for (int i = 0; i < 2; i++) {
+            if (!(sigmas[i] > 0.0)) return fail("env_attach: sigmas must be positive");
+            if (!(lims[2 + i] != lims[i])) return fail("env_attach: lims[1] must differ from lims[0]");
+        }
+        for (int i = 0; i < n_samples; i++) {
+            if (idx_v[i] < 0 || idx_v[i] > N) return fail("env_attach: a velocity sample index is outside 0..N");
+            if (idx_yawrate[i] < 0 || idx_yawrate[i] > N - ENV_MA) return fail("env_attach: a yaw rate sample index is outside 0..N-10");
+        }
+        for (int i = 0; i < 2 + 2 * n_samples; i++)
+            if (!(obs_hi[i] != obs_lo[i])) return fail("env_attach: an observation bound has no width");
+    }
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }          // (a captured chunk holds the extra launch and the sample counters, or lacks them)
+    env_release(s);
+    if (!table) return 0;
+    const int no = 2 + 2 * n_samples, rec = ENV_REC + no;
+    std::vector<double> bounds(2 * (size_t)no);
+    for (int i = 0; i < no; i++) { bounds[i] = obs_lo[i]; bounds[no + i] = obs_hi[i]; }
+    std::vector<int> idx(2 * (size_t)n_samples), samples(B, s->step);
+    for (int i = 0; i < n_samples; i++) { idx[i] = idx_v[i]; idx[n_samples + i] = idx_yawrate[i]; }
+    bool ok = true;
+    ok &= dalloc(&s->denv_table, (size_t)n_actions * 7) == hipSuccess && dalloc(&s->denv_bounds, bounds.size()) == hipSuccess;
+    ok &= dalloc(&s->denv_acc, B * 4) == hipSuccess && dalloc(&s->denv_win, B * 2 * (N + 1)) == hipSuccess && dalloc(&s->denv_out, B * rec) == hipSuccess;
+    ok &= dalloc(&s->denv_idx, idx.size()) == hipSuccess && dalloc(&s->denv_in, B * 3) == hipSuccess && dalloc(&s->denv_ep, B) == hipSuccess;
+    ok &= dalloc(&s->denv_count, B) == hipSuccess && dalloc(&s->denv_flags, B) == hipSuccess && dalloc(&s->denv_qpf, B) == hipSuccess && dalloc(&s->denv_samples, B) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&s->henv_out, sizeof(double) * B * rec, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc((void **)&s->henv_in, sizeof(int) * B * 3, hipHostMallocDefault) == hipSuccess;
+    ok = ok && (s->env_ended = (unsigned char *)calloc(B, 1)) != nullptr;
+    ok = ok && hipMemcpy(s->denv_table, table, sizeof(double) * 7 * n_actions, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(s->denv_bounds, bounds.data(), sizeof(double) * bounds.size(), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(s->denv_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice) == hipSuccess;
+    // the estimator of every instance has seen as many samples as the loop has run control steps: attaching changes nothing the loop computes
+    ok = ok && hipMemcpy(s->denv_samples, samples.data(), sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { env_release(s); (void)hipGetLastError(); return fail("env_attach: allocation failed"); }
+    EnvArgs &a = s->ea;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.batch = c->batch; a.n_track = s->n_track; a.n_actions = n_actions; a.n_samples = n_samples; a.episode_length = episode_length;
+    a.full_lap = full_lap ? 1 : 0; a.obs_last_step = obs_states; a.log_cap = s->log_cap;
+    a.max_lat_dev = max_lat_dev; a.Ts = s->Ts;
+    for (int i = 0; i < 2; i++) a.sig[i] = sigmas[i];
+    for (int i = 0; i < 4; i++) a.lim[i] = lims[i];
+    a.track = s->dtrack; a.table = s->denv_table; a.in = s->denv_in; a.obs_idx = s->denv_idx; a.obs_bounds = s->denv_bounds;
+    a.x_sim = s->dxsim; a.pose = s->dpose; a.hist = s->dhist; a.ref0 = s->dref0; a.closest = s->dclosest; a.step_counter = s->dstep; a.err = s->derr;
+    a.lCiLX = s->lCiLX; a.lSimX = s->lSimX;
+    a.ep_steps = s->denv_ep; a.count = s->denv_count; a.flags = s->denv_flags; a.qpf = s->denv_qpf; a.samples = s->denv_samples;
+    a.acc = s->denv_acc; a.win = s->denv_win; a.out = s->denv_out;
+    s->env = true; s->env_mpc_steps = n_mpc_steps; s->env_rec = rec;
+    return 0;
+}
+
+// the capsule's arrays as they are NOW (tum_ocp_bind_device moves x0 / yref; a captured chunk is dropped with the epoch then)
+static void env_bind(tum_sim *s)
+{
+    tum_ocp *c = s->c; EnvArgs &a = s->ea;
+    a.X = c->dX; a.U = c->dU; a.x0 = c->dx0; a.W = c->dW; a.pen = c->dpen; a.qp_lam = c->dqplam; a.yref = c->dyref; a.status = c->dstatus;
+}
+
+// uploads actions | reset mask | start indices (any may be null: none) and runs the begin kernel; the caller holds the device guard
+static int env_begin(tum_sim *s, const int *actions, const int *reset_mask, const int *start_idx, const char *who)
+{
+    tum_ocp *c = s->c; const int B = c->batch;
+    const std::string w(who);
+    bool any_reset = false;
+    for (int b = 0; b < B; b++) {
+        const bool r = reset_mask && reset_mask[b] == 1, go_on = reset_mask && reset_mask[b] == 2;
+        if (reset_mask && !r && !go_on && reset_mask[b] != 0) return fail(w + ": a reset mask holds 0 (nothing), 1 (reset) or 2 (an ended episode drives on)");
+        if (r && (!start_idx || start_idx[b] < 0 || start_idx[b] >= s->n_track)) return fail(w + ": start index of instance " + std::to_string(b) + " is outside the track");
+        if (actions && (actions[b] < 0 || actions[b] >= s->ea.n_actions))
+            return fail(w + ": action " + std::to_string(actions[b]) + " of instance " + std::to_string(b) + " is outside the table of " + std::to_string(s->ea.n_actions) + " rows");
+        if (actions && s->env_ended[b] && !r && !go_on) return fail(w + ": the episode of instance " + std::to_string(b) + " has ended and it is not marked for reset");
+        any_reset |= r;
+    }
+    if (flush_inputs(c)) return 1;          // (older setters of x0 / yref in the pinned shadow go first: the begin kernel writes behind them)
+    for (int b = 0; b < B; b++) {
+        const bool r = reset_mask && reset_mask[b] == 1;
+        if (reset_mask && reset_mask[b] == 2) s->env_ended[b] = 0;
+        s->henv_in[b] = actions ? actions[b] : 0; s->henv_in[B + b] = r ? 1 : 0; s->henv_in[2 * B + b] = r ? start_idx[b] : 0;
+        if (r) s->env_ended[b] = 0;
+    }
+    HIPCHK(hipMemcpyAsync(s->denv_in, s->henv_in, sizeof(int) * 3 * B, hipMemcpyHostToDevice, c->stream));
+    // the begin kernel writes W, the penalties and -- of the instances it resets -- the iterate, x0 and the pose the planner reads. Never
+    // CH_RESTART: a partly reset batch is not stage-uniform
+    invalidate(c, (actions ? (CH_W | CH_BOUNDS) : 0u) | (any_reset ? (CH_ITERATE | CH_X0 | CH_REF) : 0u));
+    env_bind(s);
+    hipLaunchKernelGGL(env_begin_kernel, dim3(B), dim3(64), 0, c->stream, s->ea, actions ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int tum_sim_env_reset(tum_sim *s, const int *mask, const int *start_idx)
+{
+    if (!s || !start_idx) return fail("null argument");
+    if (!s->env) return fail("env_reset: no environment attached (tum_sim_env_attach)");
+    if (env_refuse(s, "env_reset")) return 1;
+    tum_ocp *c = s->c;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    std::vector<int> all;
+    if (!mask) { all.assign(c->batch, 1); mask = all.data(); }
+    if (env_begin(s, nullptr, mask, start_idx, "env_reset")) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int tum_sim_env_step(tum_sim *s, const int *actions, const int *reset_mask, const int *start_idx, double *out)
+{
+    if (!s || !actions || !out) return fail("null argument");
+    if (!s->env) return fail("env_step: no environment attached (tum_sim_env_attach)");
+    if (env_refuse(s, "env_step")) return 1;
+    tum_ocp *c = s->c; const size_t B = c->batch;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (env_begin(s, actions, reset_mask, start_idx, "env_step")) return 1;
+    if (sim_run_enqueue(s, s->env_mpc_steps)) return 1;
+    env_bind(s);
+    hipLaunchKernelGGL(env_finish_kernel, dim3(c->batch), dim3(64), 0, c->stream, s->ea);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s->henv_out, s->denv_out, sizeof(double) * B * s->env_rec, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (s->henv_out[5] != 0.0) return fail("env_step: planner segment longer than PLAN_MAXM points");
+    memcpy(out, s->henv_out, sizeof(double) * B * s->env_rec);
+    for (size_t b = 0; b < B; b++)
+        if (out[b * s->env_rec + 1] != 0.0 || out[b * s->env_rec + 2] != 0.0) s->env_ended[b] = 1;
+    return lin_uniform_check(c);
+}
+
+static int env_get(tum_sim *s, const std::string &f, double *out, long long len)
+{
+    const long long B = s->c->batch;
+    if (!s->env) return fail("sim_get " + f + ": no environment attached (tum_sim_env_attach)");
+    if (len != B) return fail("sim_get " + f + ": len != batch");
+    if (f == "env_ended") { for (long long i = 0; i < B; i++) out[i] = s->env_ended[i]; return 0; }
+    const int *src = f == "env_episode_steps" ? s->denv_ep : f == "env_step_length" ? s->denv_count : f == "env_flags" ? s->denv_flags :
+                     f == "env_qp_failures" ? s->denv_qpf : f == "env_samples" ? s->denv_samples : nullptr;
+    if (!src) return fail("sim_get: unknown field '" + f + "'");
+    std::vector<int> t(B);
+    HIPCHK(hipMemcpy(t.data(), src, sizeof(int) * B, hipMemcpyDeviceToHost));
+    for (long long i = 0; i < B; i++) out[i] = t[i];
+    return 0;
+}
+
 static int seg_get(tum_sim *s, const std::string &f, double *out, long long len)
 {
     tum_ocp *c = s->c; const long long B = c->batch;
@@ -2605,6 +2824,7 @@ extern "C" int tum_sim_get(tum_sim *s, const char *field, double *out, long long
     HIPCHK(hipStreamSynchronize(c->stream));
     const double *src = nullptr; long long want = 0;
     if (f.compare(0, 4, "seg_") == 0) return seg_get(s, f, out, len);
+    if (f.compare(0, 4, "env_") == 0) return env_get(s, f, out, len);
     if (f == "x_sim") { src = s->dxsim; want = B * 7; }
     else if (f == "x_mpc") { src = c->dx0; want = B * 8; }
     else if (f == "pose") { src = s->dpose; want = B * 2; }

@@ -76,7 +76,7 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_ocp_snmpc_attach", "tum_ocp_snmpc_samples", "tum_ocp_snmpc_set_offsets",
              "tum_planner_emulate", "tum_sim_create", "tum_sim_free", "tum_sim_set_state", "tum_sim_plan", "tum_sim_advance",
              "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
-             "tum_sim_segments_attach", "tum_sim_run_segments"]
+             "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step"]
 
 
 def load_library(path=None):
@@ -154,6 +154,10 @@ def load_library(path=None):
     if hasattr(L, "tum_sim_segments_attach"):
         L.tum_sim_segments_attach.argtypes = [vp, ip, ip, ci, cd, cd]
         L.tum_sim_run_segments.argtypes = [vp, ci, ci]
+    if hasattr(L, "tum_sim_env_attach"):
+        L.tum_sim_env_attach.argtypes = [vp, dp, ci, ci, cd, ci, ci, dp, dp, dp, dp, ip, ip, ci, ci]
+        L.tum_sim_env_reset.argtypes = [vp, ip, ip]
+        L.tum_sim_env_step.argtypes = [vp, ip, ip, ip, dp]
     _libs[p] = L
     if p == LIB_PATH:
         _lib = L
@@ -858,6 +862,86 @@ class DeviceClosedLoop:
     def segment_groups(self):
         """(n_groups, 4): mean of -max|lat_dev|, mean of -rms(vel_dev), segments, segments not cleanly done (crashed or active)"""
         return self._seg_get("seg_groups", 4 * self.n_groups).reshape(self.n_groups, 4)
+
+    # ---- the weight-scheduling RL environment (RL_WMPC/environment.py:112-240)
+    ENV_HEAD = 6          # reward, terminated, truncated, step_length, qp_failures, planner error word; then the observation
+    _OBS_STATES = {"reference": 0, "last_step": 1}
+
+    def attach_env(self, table, n_mpc_steps, max_lat_dev, episode_length, sigmas, lims, n_samples=10, full_lap=False,
+                   obs_states="reference", obs_bounds=None):
+        """Turn the loop into the reference's RL environment: `table` (A, 7) rows [q_xy, q_yaw, q_vel, r_jerk, r_steer, L1, L2] an
+        agent picks from every n_mpc_steps control steps; sigmas (2,) and lims (lims[0] lower, lims[1] upper, broadcast over
+        [lat_dev, vel_dev] as reward.py does) of the reward; n_samples anticipation points of the observation; obs_states
+        "reference" (first two observation entries 0 before normalisation, as the reference computes them) or "last_step";
+        obs_bounds (2, 2 + 2 n_samples) lower / upper (None: observation.py:16-24)."""
+        if obs_states not in self._OBS_STATES:
+            raise Exception("attach_env: obs_states must be 'reference' or 'last_step'")
+        N, n = self.solver.N, int(n_samples)
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 7:
+            raise Exception("attach_env: table must be (n_actions, 7)")
+        if N < 10 or n < 1:
+            raise Exception("attach_env: the observation's 10-tap moving average of the yaw rate needs N >= 10 (and n_samples >= 1)")
+        lims = np.asarray(lims, dtype=np.float64)
+        lo_hi = np.ascontiguousarray(np.concatenate([np.broadcast_to(lims[0], (2,)), np.broadcast_to(lims[1], (2,))]))
+        sig = np.ascontiguousarray(np.broadcast_to(np.asarray(sigmas, dtype=np.float64), (2,)))
+        if obs_bounds is None:
+            obs_bounds = env_observation_bounds(n)
+        ob = np.ascontiguousarray(obs_bounds, dtype=np.float64).reshape(2, 2 + 2 * n)
+        # observation.py:58-59: the sample indices into ref_v (N + 1 points) and into the averaged yaw rate (N - 9 points)
+        iv = np.ascontiguousarray(np.linspace(0, N, n, dtype=int), dtype=np.int32)
+        ir = np.ascontiguousarray(np.linspace(0, N - 10, n, dtype=int), dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        self._chk(self._L.tum_sim_env_attach(self._s, _dp(table), table.shape[0], int(n_mpc_steps), float(max_lat_dev), int(episode_length),
+                                             int(bool(full_lap)), _dp(sig), _dp(lo_hi), _dp(ob[0]), _dp(ob[1]), iv.ctypes.data_as(ip),
+                                             ir.ctypes.data_as(ip), n, self._OBS_STATES[obs_states]), "sim_env_attach")
+        self.env_n_obs = 2 + 2 * n
+
+    def detach_env(self):
+        self._chk(self._L.tum_sim_env_attach(self._s, None, 0, 0, 0.0, 0, 0, None, None, None, None, None, None, 0, 0), "sim_env_attach")
+        self.env_n_obs = 0
+
+    def _ints(self, a):
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(a), (self.B,)))
+        if not (np.issubdtype(a.dtype, np.integer) or a.dtype == bool):
+            raise Exception("env: actions, masks and start indices are integers")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def env_reset(self, start_idx, mask=None):
+        """environment.py:191-237 for the instances of `mask` (None: all): plant and controller at waypoint start_idx[b], empty
+        estimator, cold iterate, episode counters 0. The rest of the batch is untouched."""
+        ip = ctypes.POINTER(ctypes.c_int)
+        st = self._ints(start_idx)
+        m = None if mask is None else self._ints(mask)
+        self._chk(self._L.tum_sim_env_reset(self._s, None if m is None else m.ctypes.data_as(ip), st.ctypes.data_as(ip)), "sim_env_reset")
+
+    def env_step(self, actions, reset_mask=None, start_idx=None):
+        """One environment step of every instance (environment.py:112-189): reset_mask[b] 1 resets instance b to start_idx[b] first,
+        2 lets an instance whose episode has ended drive on without a reset (episode_steps keeps counting), 0 neither -- an error
+        if its episode has ended. Returns a dict of batched arrays: reward, terminated, truncated, step_length, qp_failures,
+        observation (B, 2 + 2 n_samples)."""
+        ip = ctypes.POINTER(ctypes.c_int)
+        act = self._ints(actions)
+        m = None if reset_mask is None else self._ints(reset_mask)
+        st = None if start_idx is None else self._ints(start_idx)
+        out = np.empty((self.B, self.ENV_HEAD + getattr(self, "env_n_obs", 0)))
+        self._chk(self._L.tum_sim_env_step(self._s, act.ctypes.data_as(ip), None if m is None else m.ctypes.data_as(ip),
+                                           None if st is None else st.ctypes.data_as(ip), _dp(out)), "sim_env_step")
+        return dict(reward=out[:, 0].copy(), terminated=out[:, 1] != 0, truncated=out[:, 2] != 0, step_length=out[:, 3].astype(np.int64),
+                    qp_failures=out[:, 4].astype(np.int64), observation=out[:, self.ENV_HEAD:].copy())
+
+    def env_get(self, field):
+        """per-instance integers of the environment: episode_steps, step_length, flags, qp_failures, samples, ended"""
+        out = np.empty(self.B)
+        self._chk(self._L.tum_sim_get(self._s, ("env_" + field).encode(), _dp(out), out.size), "sim_get env_" + field)
+        return out.astype(np.int64)
+
+
+def env_observation_bounds(n_samples):
+    """(2, 2 + 2 n) lower / upper normalisation bounds of the RL observation (RL_WMPC/observation.py:16-24): lateral deviation,
+    velocity deviation, n future velocities, n future yaw rates"""
+    n = int(n_samples)
+    return np.concatenate((np.array([[-3., 3.], [-5, 5]]), np.tile([0., 39.], (n, 1)), np.tile([-3.2, 3.2], (n, 1)))).transpose()
 
 
 def segment_flags(state):
