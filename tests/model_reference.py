@@ -1,0 +1,491 @@
+"""
+The vehicle model of csrc/nmpc_device.hpp once more, exactly: forward evaluation only, in mpmath at 60 digits, and the inputs
+at which the tests compare it with the oracle (tests/test_model_reference.py) and with the device code
+(tests/test_gpu_model_reference.py).
+
+What is restated, from the formulas the header cites:
+  f(x, u)              the single-track / Pacejka right-hand side, pred_model_dynamic_stm_pacejka.py:118-175
+  Phi(x, u; dt, nsub)  one shooting interval, classic RK4 with nsub steps of dt / nsub
+  h(x)                 the gg circle (a / ax)^2 + (vl r / ay)^2, NMPC_STM_acados_settings.py:70-74, 108-119
+  wrap(yaw)            fmod(yaw, 2 pi) with the binary64 constant 2 pi, plus 2 pi where negative, NMPC_STM_acados_settings.py:41-42
+x = (px, py, psi, vl, vt, r, delta, a), u = (jerk, steering rate). The parameters are those of oracle.edgar_model() and the gg
+table of config, every one taken as the exact binary64 number it is; so are 3.6, 100, 0.001, 0.98, 0.5 and dt.
+
+There is NO hand-derived derivative in this file. J = df / d(vl, vt, r, delta, a), A = dPhi / dx, B = dPhi / du and grad h are
+central differences in the same arithmetic with a step of 1e-20 of the variable's scale (truncation ~1e-40, cancellation leaves
+40 digits): exact far below binary64. A branch (vl > 0.001, the clip of Gf / Gr at +-0.98, a < 0, the table segment) is decided
+once, at the unperturbed point, on the exact quantities, and the perturbed evaluations replay that decision (`Tape`): CasADi's
+"derivative of the taken branch", also where an input sits exactly on a kink.
+
+Not covered here (they have restatements of their own): the sensitivity-free RK4 of sqp_kernels.hpp, the plant of
+loop_kernels.hpp and the SNMPC sample propagation.
+"""
+import functools
+import math
+
+import mpmath as mp
+import numpy as np
+
+from oracle import oracle as _orc
+
+DPS = 60
+H_DPS = 700                 # h is rational: digits are cheap, and a = 1e-300 next to a step of 1e-20 needs them
+DT = 0.08
+NSUBS = (3, 1)
+HARMLESS = np.array([0.0, 0.0, 0.0, 20.0, 0.0, 0.0, 0.0, 0.0])
+VL_THR = 0.001
+CLIP = 0.98
+KINK_MARGIN = 1e-9          # a computed quantity this close (relative) to its kink may round to the other side in binary64
+TWO_PI = 2.0 * math.pi
+_PNAMES = ("lf", "lr", "m", "Iz", "ro", "S", "Cd", "Bf", "Cf", "Df", "Ef", "Br", "Cr", "Dr", "Er", "g", "fr0", "fr1", "fr4", "acc_min")
+
+
+def ggv_table():
+    from tum_control_amd import config
+    g = config.default_config()["ggv"]
+    return [float(v) for v in g["v"]], [float(v) for v in g["ax"]], [float(v) for v in g["ay"]]
+
+
+def params():
+    """the parameters as exact numbers at the working precision"""
+    m = _orc.edgar_model()
+    P = {k: mp.mpf(float(getattr(m, k))) for k in _PNAMES}
+    v, ax, ay = ggv_table()
+    P["ggv_v"], P["ggv_ax"], P["ggv_ay"] = [mp.mpf(t) for t in v], [mp.mpf(t) for t in ax], [mp.mpf(t) for t in ay]
+    P["Fz_f"] = P["m"] * P["lr"] * P["g"] / (P["lf"] + P["lr"])
+    P["Fz_r"] = P["m"] * P["lf"] * P["g"] / (P["lf"] + P["lr"])
+    P["Fmax_f"] = mp.sqrt(P["Fz_f"] ** 2 + (P["Cf"] * P["Fz_f"]) ** 2)
+    P["Fmax_r"] = mp.sqrt(P["Fz_r"] ** 2 + (P["Cr"] * P["Fz_r"]) ** 2)
+    return P
+
+
+class Tape:
+    """the branch decisions of one evaluation, in order; a second evaluation given `replay` takes the same ones"""
+
+    def __init__(self, replay=None):
+        self.rec, self.replay, self.i = [], replay, 0
+        self.computed = []          # (name, quantity, kink) of every decision on a computed quantity
+        self.info = []              # one dict per model evaluation: what the labels are checked against
+
+    def take(self, decision):
+        if self.replay is not None:
+            decision = self.replay.rec[self.i]
+            self.i += 1
+        self.rec.append(decision)
+        return decision
+
+
+def _mpv(v):
+    return [mp.mpf(float(t)) if not isinstance(t, mp.mpf) else t for t in v]
+
+
+def f_rhs(P, x, u, tape, input_is_exact=True):
+    """xdot (8 mpf). input_is_exact: vl is an input of the caller (the kink vl > 0.001 is then decided on an input)"""
+    px, py, psi, vl, vt, r, de, a = x
+    v = mp.sqrt(vl * vl + vt * vt) * mp.mpf(3.6)
+    w = v / 100
+    fr = P["fr0"] + P["fr1"] * w + P["fr4"] * w ** 4
+    Fx_f = -fr * P["Fz_f"]
+    Fx_r = P["m"] * a - fr * P["Fz_r"]
+    Faero = mp.mpf(0.5) * P["ro"] * P["S"] * P["Cd"] * vl * vl
+    thr = mp.mpf(VL_THR)
+    moving = tape.take(bool(vl > thr))
+    if not input_is_exact:
+        tape.computed.append(("vl", vl, thr))
+    if moving:
+        al_f = de - mp.atan((vt + P["lf"] * r) / vl)
+        al_r = mp.atan((P["lr"] * r - vt) / vl)
+    else:
+        al_f = al_r = mp.mpf(0)
+    bf, br = P["Bf"] * al_f, P["Br"] * al_r
+    Fyf_lat = P["Df"] * mp.sin(P["Cf"] * mp.atan(bf - P["Ef"] * (bf - mp.atan(bf))))
+    Fyr_lat = P["Dr"] * mp.sin(P["Cr"] * mp.atan(br - P["Er"] * (br - mp.atan(br))))
+    c = mp.mpf(CLIP)
+    G = []
+    for nm, g in (("Gf", Fx_f / P["Fmax_f"]), ("Gr", Fx_r / P["Fmax_r"])):
+        side = tape.take(1 if g > c else (-1 if g < -c else 0))
+        tape.computed.append((nm, abs(g), c))
+        G.append(side * c if side else g)
+    Fy_f = Fyf_lat * mp.sqrt(1 - G[0] * G[0])       # cos(asin(G))
+    Fy_r = Fyr_lat * mp.sqrt(1 - G[1] * G[1])
+    if tape.replay is None:
+        tape.info.append(dict(moving=moving, clip_f=tape.rec[-2], clip_r=tape.rec[-1], x1f=float(bf), x1r=float(br),
+                              Gf=float(Fx_f / P["Fmax_f"]), Gr=float(Fx_r / P["Fmax_r"])))
+    sd, cd, sp, cp = mp.sin(de), mp.cos(de), mp.sin(psi), mp.cos(psi)
+    front = Fy_f * cd + Fx_f * sd
+    return [vl * cp - vt * sp, vl * sp + vt * cp, r,
+            (Fx_r - Faero - Fy_f * sd + Fx_f * cd) / P["m"] + vt * r,
+            (Fy_r + front) / P["m"] - vl * r,
+            (P["lf"] * front - P["lr"] * Fy_r) / P["Iz"],
+            u[1], u[0]]
+
+
+def phi(P, x, u, dt, nsub, tape):
+    """x after one shooting interval: RK4, nsub steps"""
+    h = mp.mpf(dt) / nsub
+    x = list(x)
+    for sub in range(nsub):
+        k1 = f_rhs(P, x, u, tape, input_is_exact=(sub == 0))
+        k2 = f_rhs(P, [a + h / 2 * b for a, b in zip(x, k1)], u, tape, False)
+        k3 = f_rhs(P, [a + h / 2 * b for a, b in zip(x, k2)], u, tape, False)
+        k4 = f_rhs(P, [a + h * b for a, b in zip(x, k3)], u, tape, False)
+        x = [a + h / 6 * (b + 2 * c + 2 * d + e) for a, b, c, d, e in zip(x, k1, k2, k3, k4)]
+    return x
+
+
+def interp(xs, ys, x, tape):
+    n = len(xs)
+    i = 0
+    while i < n - 2 and x >= xs[i + 1]:
+        i += 1
+    i = tape.take(i)
+    sl = (ys[i + 1] - ys[i]) / (xs[i + 1] - xs[i])
+    return ys[i] + sl * (x - xs[i]), sl, i
+
+
+def h_fun(P, x, tape):
+    vl, r, a = x[3], x[5], x[7]
+    ax, _, seg = interp(P["ggv_v"], P["ggv_ax"], vl, tape)
+    ay, _, _ = interp(P["ggv_v"], P["ggv_ay"], vl, tape)
+    brake = tape.take(bool(a < 0))
+    if brake:
+        ax = -P["acc_min"]
+    if tape.replay is None:
+        tape.info.append(dict(brake=brake, seg=seg))
+    return (a / ax) ** 2 + (vl * r / ay) ** 2
+
+
+def wrap(yaw):
+    """float64 in, float64 out: fmod is exact in binary64 (math.fmod), the sum with 2 pi rounds once, as the expression does"""
+    y = math.fmod(yaw, TWO_PI)
+    return y + TWO_PI if y < 0.0 else y
+
+
+def wrap_exact(yaw):
+    """the same in mpmath: (value before the final rounding)"""
+    with mp.workdps(DPS):
+        t, y = mp.mpf(TWO_PI), mp.mpf(float(yaw))
+        q = mp.floor(abs(y) / t)
+        rem = (abs(y) - q * t) * (1 if y >= 0 else -1)
+        return rem + t if rem < 0 else rem
+
+
+# ---------------------------------------------------------------------------------------------- derivatives: differences only
+def _step(v, rel):
+    s = abs(v)
+    s = min(s, mp.mpf(1)) if s >= mp.mpf("1e-4") else mp.mpf(1)
+    return s * rel
+
+
+def _central(fun, z, idx, tape0, rel):
+    """columns d fun / d z[i] for i in idx, by central differences replaying the branches of tape0"""
+    cols = []
+    for i in idx:
+        e = _step(z[i], rel)
+        zp, zm = list(z), list(z)
+        zp[i] = z[i] + e
+        zm[i] = z[i] - e
+        fp, fm = fun(zp, Tape(tape0)), fun(zm, Tape(tape0))
+        cols.append([(a - b) / (2 * e) for a, b in zip(fp, fm)])
+    return cols            # [column][row]
+
+
+def _f64(a):
+    return np.array([[float(v) for v in row] for row in a]) if a and isinstance(a[0], (list, tuple)) else np.array([float(v) for v in a])
+
+
+def eval_f(x, u, dps=DPS, rel="1e-20", raw=False):
+    """f (8,), J (3, 5) = d(vl', vt', r') / d(vl, vt, r, delta, a), and the tape of the evaluation"""
+    with mp.workdps(dps):
+        P, z = params(), _mpv(list(x) + list(u))
+        t0 = Tape()
+        f = f_rhs(P, z[:8], z[8:], t0)
+        cols = _central(lambda zz, t: f_rhs(P, zz[:8], zz[8:], t)[3:6], z, range(3, 8), t0, mp.mpf(rel))
+        J = [[cols[c][i] for c in range(5)] for i in range(3)]
+        if raw:
+            return f, J, t0
+        return _f64(f), _f64(J), t0
+
+
+def eval_phi(x, u, dt=DT, nsub=3, dps=DPS, rel="1e-20", raw=False, derivatives=True):
+    """Phi (8,), A (8, 8), B (8, 2), tape"""
+    with mp.workdps(dps):
+        P, z = params(), _mpv(list(x) + list(u))
+        t0 = Tape()
+        xn = phi(P, z[:8], z[8:], dt, nsub, t0)
+        if not derivatives:
+            return (xn if raw else _f64(xn)), None, None, t0
+        cols = _central(lambda zz, t: phi(P, zz[:8], zz[8:], dt, nsub, t), z, range(10), t0, mp.mpf(rel))
+        A = [[cols[c][i] for c in range(8)] for i in range(8)]
+        B = [[cols[8 + c][i] for c in range(2)] for i in range(8)]
+        if raw:
+            return xn, A, B, t0
+        return _f64(xn), _f64(A), _f64(B), t0
+
+
+def eval_h(x, dps=H_DPS, rel="1e-20", raw=False):
+    """h, grad h (8,) (entries vl, r, a; the others are structurally 0), tape"""
+    with mp.workdps(dps):
+        P, z = params(), _mpv(list(x))
+        t0 = Tape()
+        h = h_fun(P, z, t0)
+        cols = _central(lambda zz, t: [h_fun(P, zz, t)], z, (3, 5, 7), t0, mp.mpf(rel))
+        g = [mp.mpf(0)] * 8
+        for c, i in enumerate((3, 5, 7)):
+            g[i] = cols[c][0]
+        if raw:
+            return h, g, t0
+        return float(h), _f64(g), t0
+
+
+def kink_margin(tape):
+    """smallest relative distance of a computed quantity from the kink it was compared with"""
+    return min([float(abs(q - k) / k) for _, q, k in tape.computed] or [1.0])
+
+
+# ---------------------------------------------------------------------------------------------- the model points
+def _nominal(rng):
+    x = np.array([rng.normal(0, 50), rng.normal(0, 50), rng.uniform(-7, 7), rng.uniform(3, 38),
+                  rng.normal(0, 0.3), rng.normal(0, 0.1), rng.normal(0, 0.05), rng.uniform(-3, 2.5)])
+    return x, rng.normal(0, 1, 2)
+
+
+def _slip_class(v):
+    v = abs(v)
+    return "small" if v <= math.tan(math.pi / 8) else ("mid" if v <= math.tan(3 * math.pi / 8) else "big")
+
+
+def _x1(x):
+    """Bf alpha_f, Br alpha_r in binary64 (only to sort candidates into classes; atan is smooth at its seams)"""
+    E = _orc.EDGAR
+    vl, vt, r, de = x[3], x[4], x[5], x[6]
+    return E["Bf"] * (de - math.atan((vt + E["lf"] * r) / vl)), E["Br"] * math.atan((E["lr"] * r - vt) / vl)
+
+
+def _a_for_gr(g, vl, vt=0.0):
+    """a that puts Gr at g (binary64 arithmetic; the generator verifies the margin on the exact model)"""
+    E = _orc.EDGAR
+    Fz_r = E["m"] * E["lf"] * E["g"] / (E["lf"] + E["lr"])
+    w = math.hypot(vl, vt) * 3.6 / 100
+    fr = E["fr0"] + E["fr1"] * w + E["fr4"] * w ** 4
+    return (g * Fz_r * math.sqrt(1 + E["Cr"] ** 2) + fr * Fz_r) / E["m"]
+
+
+GF_NOTE = ("Gf = -fr Fz_f / Fmax_f is negative at every speed: it cannot clip high; it clips low once fr > 0.98 sqrt(1 + Cf^2), "
+           "beyond 235 m/s with these parameters")
+
+
+@functools.lru_cache(maxsize=None)
+def model_points(seed=20240):
+    """(X (P, 8), U (P, 2), labels): the smallest set that reaches every branch of the model. Deterministic."""
+    rng = np.random.default_rng(seed)
+    X, U, L = [], [], []
+
+    def add(label, x, u):
+        X.append(np.array(x, dtype=np.float64)); U.append(np.array(u, dtype=np.float64)); L.append(label)
+
+    for _ in range(40):
+        add("nominal", *_nominal(rng))
+    # low speed, vt and r nonzero but small against vl where the slip angles are live (the model is not meant for |vt| >> vl); vt
+    # dominates lf r and lr r, so that neither slip numerator vt + lf r, lr r - vt is a difference of nearly equal terms (entries of
+    # 1e-7 would then carry the rounding of terms a thousand times their size: ill-conditioned without a large bound to show it)
+    for vl, lab in ((0.0005, "vl_below_thr"), (0.001, "vl_at_thr"), (np.nextafter(0.001, 1.0), "vl_above_thr"), (0.01, "vl_low_0.01"),
+                    (0.5, "vl_low_0.5"), (3.0, "vl_low_3")):
+        for sgn in (1.0, -1.0):
+            x, u = _nominal(rng)
+            x[3] = vl; x[4] = sgn * 0.2 * vl * rng.uniform(0.5, 1.0); x[5] = -sgn * 0.02 * vl * rng.uniform(0.5, 1.0); x[7] = rng.uniform(-1, 1)
+            add(lab, x, u)
+    # large slip: every pair of ranges of fast_atan's argument B alpha, front and rear
+    for cf in ("small", "mid", "big"):
+        for cr in ("small", "mid", "big"):
+            if cf == cr == "small":
+                continue
+            n = 0
+            while n < 5:
+                x, u = _nominal(rng)
+                x[3] = rng.uniform(3, 30); x[4] = rng.uniform(-1, 1) * x[3]; x[5] = rng.uniform(-2, 2); x[6] = rng.uniform(-0.6, 0.6)
+                a, b = _x1(x)
+                if _slip_class(a) == cf and _slip_class(b) == cr:
+                    add(f"slip_f{cf}_r{cr}", x, u); n += 1
+    # the clip of Gr through a, of Gf (low side only, GF_NOTE) through the speed; no jerk, so that a stays on its side over the interval
+    for lab, g in (("gr_clip_high", 1.05), ("gr_inside_high", 0.975), ("gr_clip_low", -1.05), ("gr_inside_low", -0.975)):
+        for _ in range(4):
+            x, u = _nominal(rng)
+            x[7] = _a_for_gr(g * rng.uniform(0.999, 1.001), x[3], x[4]); u[0] = 0.0
+            add(lab, x, u)
+    for lab, vl in (("gf_clip_low", 240.0), ("gf_inside_low", 235.0)):
+        for _ in range(3):
+            x, u = _nominal(rng)
+            x[3] = vl * rng.uniform(0.999, 1.001); x[7] = rng.uniform(-1, 1)
+            add(lab, x, u)
+    for a, lab in ((-6.0, "a_-6"), (-1e-300, "a_-tiny"), (-0.0, "a_-0"), (0.0, "a_+0"), (1e-300, "a_+tiny"), (4.0, "a_4")):
+        for _ in range(2):
+            x, u = _nominal(rng)
+            x[7] = a
+            add(lab, x, u)
+    v = ggv_table()[0]
+    for i, kv in enumerate(v):
+        for lab, vl in ((f"knot{i}", kv), (f"knot{i}_below", np.nextafter(kv, -np.inf)), (f"knot{i}_above", np.nextafter(kv, np.inf))):
+            x, u = _nominal(rng)
+            x[3] = vl            # (knot 0: vl = 0 and one double either side with vt != 0 -- the model is finite there; vl = vt = 0 is
+            if vl < 1.0:         #  the edge of the domain, tests/test_gpu_model_reference.py part (c))
+                x[4] *= 0.01; x[5] *= 0.01
+            add(lab, x, u)
+    for lab, vl in (("below_first_knot", 2.0), ("above_last_knot", 41.0)):
+        x, u = _nominal(rng)
+        x[3] = vl
+        add(lab, x, u)
+    for yaw, lab in ((0.0, "yaw_0"), (1e-17, "yaw_+1e-17"), (-1e-17, "yaw_-1e-17"), (TWO_PI, "yaw_2pi"), (np.nextafter(TWO_PI, 0.0), "yaw_2pi_below"),
+                     (np.nextafter(TWO_PI, 7.0), "yaw_2pi_above"), (-TWO_PI, "yaw_-2pi"), (37.7, "yaw_37.7"), (1e4, "yaw_1e4")):
+        x, u = _nominal(rng)
+        x[2] = yaw
+        add(lab, x, u)
+    X, U = np.array(X), np.array(U)
+    # a computed quantity within KINK_MARGIN of its kink: move the point (never drop it)
+    moved = 0
+    for p in range(len(L)):
+        for attempt in range(8):
+            m = min(kink_margin(eval_phi(X[p], U[p], DT, ns, derivatives=False)[3]) for ns in NSUBS)
+            m = min(m, kink_margin(eval_phi(X[p], 0 * U[p], DT, 3, derivatives=False)[3]))
+            if m > KINK_MARGIN:
+                break
+            X[p, 7] += 1e-3 * (1 + abs(X[p, 7])); X[p, 3] *= 1 + 1e-6; moved += 1
+        else:
+            raise AssertionError(f"point {p} ({L[p]}) stays on a kink")
+    X.setflags(write=False); U.setflags(write=False)
+    return X, U, tuple(L)
+
+
+def label_holds(label, x, u):
+    """does the exact model take, at (x, u), the branch the label names? (first evaluation of the interval / of h)"""
+    tf = eval_phi(x, u, DT, 3, derivatives=False)[3].info[0]
+    th = eval_h(x)[2].info[0]
+    v = ggv_table()[0]
+    if label == "nominal":
+        return tf["moving"] and tf["clip_f"] == 0 and tf["clip_r"] == 0
+    if label in ("vl_below_thr", "vl_at_thr"):
+        return not tf["moving"]
+    if label.startswith("vl_"):
+        return tf["moving"]
+    if label.startswith("slip_"):
+        cf, cr = label.split("_")[1][1:], label.split("_")[2][1:]
+        return tf["moving"] and _slip_class(tf["x1f"]) == cf and _slip_class(tf["x1r"]) == cr
+    if label.startswith("gr_"):
+        return tf["clip_r"] == {"gr_clip_high": 1, "gr_clip_low": -1}.get(label, 0) and abs(abs(tf["Gr"]) - CLIP) < 0.1
+    if label.startswith("gf_"):
+        return tf["clip_f"] == {"gf_clip_low": -1}.get(label, 0) and abs(abs(tf["Gf"]) - CLIP) < 0.1
+    if label.startswith("a_"):
+        return th["brake"] == (label in ("a_-6", "a_-tiny")) and (x[7] == 0.0) == (label in ("a_-0", "a_+0")) and \
+            (not label == "a_-0" or math.copysign(1.0, x[7]) < 0)
+    if label.startswith("knot"):
+        i = int(label[4:].split("_")[0])
+        want = i - 1 if label.endswith("_below") else i
+        return th["seg"] == min(max(want, 0), len(v) - 2) and (x[3] == v[i]) == ("_" not in label)
+    if label == "below_first_knot":
+        return th["seg"] == 0 and x[3] < v[1]
+    if label == "above_last_knot":
+        return th["seg"] == len(v) - 2 and x[3] > v[-1]
+    if label.startswith("yaw_"):
+        return True
+    raise KeyError(label)
+
+
+REQUIRED_LABELS = (
+    ["nominal", "vl_below_thr", "vl_at_thr", "vl_above_thr", "vl_low_0.01", "vl_low_0.5", "vl_low_3"]
+    + [f"slip_f{a}_r{b}" for a in ("small", "mid", "big") for b in ("small", "mid", "big") if (a, b) != ("small", "small")]
+    + ["gr_clip_high", "gr_inside_high", "gr_clip_low", "gr_inside_low", "gf_clip_low", "gf_inside_low"]
+    + ["a_-6", "a_-tiny", "a_-0", "a_+0", "a_+tiny", "a_4"]
+    + [f"knot{i}{s}" for i in range(10) for s in ("", "_below", "_above")] + ["below_first_knot", "above_last_knot"]
+    + ["yaw_0", "yaw_+1e-17", "yaw_-1e-17", "yaw_2pi", "yaw_2pi_below", "yaw_2pi_above", "yaw_-2pi", "yaw_37.7", "yaw_1e4"])
+
+
+def reference_arrays(idx=None):
+    """the model-level reference of the points idx (default: all), rounded to binary64: what tests/golden/model_reference.npz holds"""
+    X, U, L = model_points()
+    idx = range(len(L)) if idx is None else idx
+    out = dict(f=[], J=[], h=[], gh=[])
+    for ns in NSUBS:
+        for tag in ("", "_u0"):
+            for k in ("Phi", "A", "B"):
+                out[f"{k}{ns}{tag}"] = []
+    for p in idx:
+        f, J, _ = eval_f(X[p], U[p])
+        h, gh, _ = eval_h(X[p])
+        out["f"].append(f); out["J"].append(J); out["h"].append(h); out["gh"].append(gh)
+        for ns in NSUBS:
+            for tag, u in (("", U[p]), ("_u0", 0 * U[p])):
+                xn, A, B, _ = eval_phi(X[p], u, DT, ns)
+                out[f"Phi{ns}{tag}"].append(xn); out[f"A{ns}{tag}"].append(A); out[f"B{ns}{tag}"].append(B)
+    return {k: np.array(v) for k, v in out.items()}
+
+
+# ---------------------------------------------------------------------------------------------- the primitive points
+ATAN_SEAMS = (4.14213562373095034458e-01, 2.41421356237309492343e+00)        # tan(pi / 8), tan(3 pi / 8) as the header spells them
+YAWS = (0.0, 1e-17, -1e-17, TWO_PI, float(np.nextafter(TWO_PI, 0.0)), float(np.nextafter(TWO_PI, 7.0)), -TWO_PI, 37.7, 1e4)
+
+
+def _around(c, k):
+    """the 2 k + 1 doubles around c"""
+    out = [c]
+    lo = hi = np.float64(c)
+    for _ in range(k):
+        lo = np.nextafter(lo, -np.inf); hi = np.nextafter(hi, np.inf)
+        out += [lo, hi]
+    return np.array(out, dtype=np.float64)
+
+
+def _loguniform(rng, n, lo=-300.0, hi=300.0):
+    return 10.0 ** rng.uniform(lo, hi, n)
+
+
+@functools.lru_cache(maxsize=None)
+def primitive_points(name, seed=7):
+    """inputs of one primitive (float64, read-only); for interp_lin: (table index, x) rows"""
+    rng = np.random.default_rng(seed)
+    if name == "fast_sincos":
+        ks = np.unique(np.concatenate([rng.integers(-60000, 60001, 1990), [-60000, -3, -2, -1, 0, 1, 2, 3, 30000, 60000]]))
+        with mp.workdps(40):
+            near = np.concatenate([_around(float(int(k) * mp.pi / 2), 4) for k in ks])
+        x = np.concatenate([rng.uniform(-10, 10, 2000), rng.uniform(-1e-3, 1e-3, 1000), rng.uniform(-1e5, 1e5, 2000), near, [0.0, -0.0]])
+    elif name == "fast_atan":
+        seams = np.concatenate([_around(c, 20) for c in (0.0,) + ATAN_SEAMS])
+        lg = _loguniform(rng, 8000)
+        x = np.concatenate([rng.uniform(-10, 10, 8000), lg * np.where(rng.random(8000) < 0.5, -1.0, 1.0), seams, -seams])
+    elif name == "fast_sqrt_pos":
+        X = model_points()[0]
+        G = np.linspace(-CLIP, CLIP, 4001)
+        x = np.concatenate([_loguniform(rng, 12000), 1.0 - G * G, X[:, 3] * X[:, 3] + X[:, 4] * X[:, 4]])
+    elif name == "frcp":
+        lg = _loguniform(rng, 20000)
+        x = lg * np.where(rng.random(20000) < 0.5, -1.0, 1.0)
+    elif name == "interp_lin":
+        v = ggv_table()[0]
+        xs = [-1.0, float(np.nextafter(v[0], -1.0)), 41.0, 100.0]
+        for kv in v:
+            xs += [kv, float(np.nextafter(kv, -np.inf)), float(np.nextafter(kv, np.inf))]
+        x = np.array([(t, xv) for t in (0.0, 1.0) for xv in xs])
+    elif name == "wrap_yaw":
+        x = np.concatenate([YAWS, rng.uniform(-1e5, 1e5, 2000)])
+    else:
+        raise KeyError(name)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    x.setflags(write=False)
+    return x
+
+
+def ulp_of(v):
+    """one unit in the last place of the binary64 format at the magnitude of the exact value v (mpf or float)"""
+    a = abs(v)
+    if a == 0:
+        return 2.0 ** -1074
+    e = a.man.bit_length() + a.exp - 1 if isinstance(a, mp.mpf) else math.frexp(a)[1] - 1
+    return 2.0 ** max(e - 52, -1074)
+
+
+def interp_f64(xs, ys, x):
+    """interp_lin's two lines in binary64 (numpy scalars: no contraction)"""
+    n, i = len(xs), 0
+    while i < n - 2 and x >= xs[i + 1]:
+        i += 1
+    sl = (np.float64(ys[i + 1]) - np.float64(ys[i])) / (np.float64(xs[i + 1]) - np.float64(xs[i]))
+    return float(np.float64(ys[i]) + sl * (np.float64(x) - np.float64(xs[i]))), float(sl)

@@ -232,8 +232,9 @@ __device__ __forceinline__ double wave_max(double v)
     TUM_DPP_SCAN(op_max, 0.0)
     return rl(v, 63);
 }
-// 1/x without the IEEE division sequence: v_rcp_f64 (4.4e-8 relative, measured) + ONE Newton step -> 2e-15
-// relative (measured over 40 decades, scripts/probes/probe_trisolve2.cpp); 3 VALU instead of ~27. The IPM only
+// 1/x without the IEEE division sequence: v_rcp_f64 (seed, 4.47e-8 relative to the exact reciprocal) + ONE Newton step -> at most
+// seed^2 + 2^-52 = 2.2e-15 relative to the exact reciprocal; measured 1.99e-15 over 1e-300 .. 1e300, both signs
+// (tests/test_gpu_model_reference.py, profiles/model_reference_bounds.txt); 3 VALU instead of ~27. The IPM only
 // uses it inside Newton-type iterations, which are self-correcting at that level.
 __device__ __forceinline__ double frcp(double x)
 {
@@ -267,18 +268,25 @@ __device__ __forceinline__ void wsync()
 
 // sin and cos together for moderate arguments (|x| < ~1e5: tyre-model angles, steering angle, yaw): two-constant
 // Cody-Waite reduction by pi/2 with FMAs, then the classic minimax kernels on [-pi/4, pi/4] (coefficients of the
-// fdlibm k_sin / k_cos kernels, < 1 ulp there). About a third of the instructions of the general-range library routine,
+// fdlibm k_sin / k_cos kernels). About a third of the instructions of the general-range library routine,
 // which matters because the linearisation evaluates it 48 times per lane.
+// Accuracy against the EXACT value (tests/test_gpu_model_reference.py): |x| <= pi/4 (n = 0): sin 0.54, cos 1.08 ulp of the result
+// (bound 2); beyond: |error| <= 3 ulp of the result + |n| 1.5e-33 ABSOLUTE, 1.5e-33 = |pi/2 - hi - lo| of the two constants. Next to
+// a multiple of pi/2 the second term is all there is: at |n| = 6e4 it is 1e-28 absolute, which is up to 160 ulp of a result of
+// 1e-12 .. 1e-20 -- harmless in absolute terms, but not "< 1 ulp". sin is odd and cos even in x to the bit, the sign of a zero included.
 __device__ __forceinline__ void fast_sincos(double x, double *sn, double *cs)
 {
-    const double n = rint(x * 6.36619772367581382433e-01);              // x * 2/pi
+    // (sin(-0.0) = -0.0 needs two things a plain reduction loses, each by adding a zero of the other sign: n = +0.0 for x = -0.0 -- the
+    //  product is an fma onto +0.0, the same bits for every other x -- so that r = fma(-0.0, hi, -0.0) = -0.0, and the sign of r on s
+    //  below, which s has anyway whenever r is not a zero)
+    const double n = rint(fma(x, 6.36619772367581382433e-01, 0.0));     // x * 2/pi
     double r = fma(-n, 1.57079632679489655800e+00, x);
     r = fma(-n, 6.12323399573676603587e-17, r);
     const int q = (int)n & 3;
     const double z = r * r;
     const double ps = fma(z, fma(z, fma(z, fma(z, fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08),
                        2.75573137070700676789e-06), -1.98412698298579493134e-04), 8.33333333332248946124e-03), -1.66666666666666324348e-01);
-    const double s = fma(r * z, ps, r);
+    const double s = copysign(fma(r * z, ps, r), r);
     const double pc = fma(z, fma(z, fma(z, fma(z, fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09),
                        -2.75573143513906633035e-07), 2.48015872894767294178e-05), -1.38888888888741095749e-03), 4.16666666666666019037e-02);
     const double c = fma(z * z, pc, fma(-0.5, z, 1.0));
@@ -288,8 +296,11 @@ __device__ __forceinline__ void fast_sincos(double x, double *sn, double *cs)
 }
 
 // atan for any finite argument: three ranges (|x| <= tan(pi/8): x itself; <= tan(3pi/8): (|x|-1)/(|x|+1) + pi/4; beyond:
-// -1/|x| + pi/2), reduced argument |t| <= 0.4143 where the fdlibm atan polynomial holds (< 1 ulp); the quotient is a
+// -1/|x| + pi/2), reduced argument |t| <= 0.4143 where the fdlibm atan polynomial holds; the quotient is a
 // reciprocal with one residual correction. Half the instructions of the library routine (85), 72 calls per lane.
+// Accuracy against the EXACT value, in ulp of the result (tests/test_gpu_model_reference.py): first range 0.55 (bound 1.5: the
+// polynomial 1, the inner rounding 1/2), the other two 1.62 (bound 2.5: the subtraction from hi rounds at ulp(hi) <= 2 ulp of the
+// result, largest just above the first seam). Odd in x to the bit, atan(+-0) = +-0.
 __device__ __forceinline__ double fast_atan(double x)
 {
     const double ax = fabs(x);
@@ -309,8 +320,10 @@ __device__ __forceinline__ double fast_atan(double x)
     const double r = hi - ((t * (s1 + s2) - lo) - t);
     return copysign(r, x);
 }
-// sqrt of a strictly positive normal number: v_rsq_f64 seed and two coupled Goldschmidt / Newton corrections (< 1 ulp
-// measured); a quarter of the instructions of the IEEE sequence. Not for 0, denormals or infinities.
+// sqrt of a strictly positive normal number: v_rsq_f64 seed (5.0e-8 relative to the exact value) and two coupled Goldschmidt /
+// Newton corrections: 0.50 ulp of the exact root measured over 1e-300 .. 1e300 (contract: <= 1 ulp; tests/test_gpu_model_reference.py);
+// a quarter of the instructions of the IEEE sequence. Not for 0, denormals or infinities: at vl = vt = 0 the model returns NaN
+// and the instance fails with status 4 (same test file, "standstill").
 __device__ __forceinline__ double fast_sqrt_pos(double x)
 {
     const double r = __builtin_amdgcn_rsq(x);
