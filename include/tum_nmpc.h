@@ -479,6 +479,34 @@ int tum_sim_env_step(tum_sim *s, const int *actions, const int *reset_mask, cons
 /* More fields of the get function, B values each, an error when no environment is attached: "env_episode_steps", "env_step_length",
  * "env_flags" (1 terminated, 2 truncated), "env_qp_failures", "env_samples" (samples the estimator has seen), "env_ended". */
 
+/* --- K12: the agent of the environment on the device (enable_WMPC of the reference's controller classes, RL_WMPC/evaluation.py:65-105
+ * run_policy: model.predict(obs, deterministic=True) of a stable_baselines3 MlpPolicy with tanh activations). Inference only.
+ * The policy net is evaluated in FP64 on the float32 weights, the observation rounded to float32 first as stable_baselines3 does:
+ * h = tanh(W h + b) per hidden layer, a linear action layer, the action the first index of the largest logit, the probabilities the
+ * softmax of the logits (helpers.py:100-105).
+ * widths[n_layers + 1]: inputs, hidden widths..., actions (n_layers matrices: 2..5, that is 1 to 4 hidden layers; 1..128 inputs,
+ * hidden layers 1..256 wide, 1..64 actions); W[l] row-major (out, in) as torch stores it; W == NULL detaches.
+ * On a loop with an attached environment the observation must have widths[0] entries and the table widths[n_layers] rows. On a
+ * loop without one the policy serves tum_sim_policy_eval alone (a rollout is refused). Attaching, re-attaching or detaching the
+ * environment detaches the policy. */
+int tum_sim_policy_attach(tum_sim *s, int n_layers, const int *widths, const float *const *W, const float *const *b);
+/* the policy alone on n host observations (n >= 1, independent of the loop's batch; n x widths[0] doubles): logits and probs
+ * n x actions doubles, actions n ints; any of the outputs may be NULL */
+int tum_sim_policy_eval(tum_sim *s, const double *obs, int n, double *logits, double *probs, int *actions);
+/* n_env_steps environment steps with the policy choosing every action, enqueued without a host wait in between:
+ * first_obs (B x n_obs, NULL = zeros, what a reset returns) is what the policy sees first.
+ * on_end 0: an ended instance is frozen out: it drives on as with reset mask 2 of tum_sim_env_step, live = 0 from the next step on,
+ *           and its later rows are not results. An instance whose episode had ended before the call starts with live = 0.
+ * on_end 1: it is reset at the start of step e + 1 to start_table[e + 1][b] and the policy sees zeros for it; an instance whose
+ *           episode had ended before the call is reset to start_table[0][b] at step 0. start_table: n_env_steps x B ints, every one
+ *           checked against the track before anything is launched.
+ * check_every > 0: the counter of live instances is read back every check_every steps and the rollout stops when it is 0.
+ * out: n_env_steps x B records as tum_sim_env_step writes them; actions_out, live_out: n_env_steps x B ints; steps_run: how many
+ * steps ran (the rows behind them are not written). Everything tum_sim_env_step refuses is refused, and a rollout without a policy.
+ * "env_ended" afterwards: the flags of the last step that ran. tum_sim_env_step works unchanged after a rollout. */
+int tum_sim_env_rollout(tum_sim *s, int n_env_steps, const double *first_obs, int on_end, const int *start_table,
+                        int check_every, double *out, int *actions_out, int *live_out, int *steps_run);
+
 /* development aid: one solve with in-kernel phase timers; out = batch x 12 shader-cycle counters
  * [linearise, condense, ipm-residuals, M assembly, Cholesky, rhs, tri-solves, row updates, (iteration tail), expand+cost] */
 int tum_ocp_profile_phases(tum_ocp *c, long long *out);

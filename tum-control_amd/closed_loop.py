@@ -600,6 +600,8 @@ class WeightScheduleEnv:
         self.dev.attach_env(self.table, n_mpc_steps, max_lat_dev, episode_length, rew_sigmas, rew_lims, obs_n_anticipation_points,
                             full_lap=full_lap, obs_states=obs_states)
         self._ended = np.zeros(self.n_envs, dtype=bool)
+        self._next_obs = np.zeros((self.n_envs, self.n_observations))          # what an agent sees next (rollout)
+        self._policy = None
 
     def _draw(self, n):
         return self.restart_indices[self._rng.randint(0, len(self.restart_indices), size=n)]
@@ -613,6 +615,7 @@ class WeightScheduleEnv:
         self.dev.env_reset(start, m)
         self._ended[m] = False
         self.last_start = start
+        self._next_obs[m] = 0.0
         return np.zeros((self.n_envs, self.n_observations)), {}
 
     def step(self, actions):
@@ -630,4 +633,145 @@ class WeightScheduleEnv:
         info = dict(terminal_observation=obs.copy(), step_length=r["step_length"], qp_failures=r["qp_failures"])
         if self.auto_reset:
             obs[self._ended] = 0.0
+        self._next_obs = obs.copy()
         return obs, r["reward"], r["terminated"], r["truncated"], info
+
+    def rollout(self, policy, n_steps, stop_when_done=False):
+        """n_steps environment steps with `policy` (a WeightPolicy) choosing every action ON THE DEVICE: policy_kernel, the environment's
+        kernels and the control steps are enqueued back to back, the host waits once at the end. What the policy sees first is what
+        the last reset() / step() / rollout() returned (zeros after a reset). Equal, bit for bit, to step() driven with
+        policy.predict(obs) on the host.
+        auto_reset: an instance whose episode ends is reset at the next step and the policy sees zeros for it. The start waypoints are
+        drawn BEFORE the rollout, one per step and instance -- self._draw(n_steps * n_envs), row e for the resets at the start of step
+        e -- so the generator is consumed differently from step(), which draws one number per reset that happens: after a rollout the
+        two no longer draw the same sequence.
+        auto_reset=False: an ended instance is frozen out -- it drives on, live is False from the next step on and its rows are masked;
+        stop_when_done ends the rollout once no instance is live (looked at after every step).
+        Returns a dict of (E, B[, n_obs]) arrays over the E steps that ran: live (bool) and, as numpy masked arrays whose mask is
+        ~live, action, reward, observation (of the step itself, as info['terminal_observation'] of step()), terminated, truncated,
+        step_length, qp_failures."""
+        E, B = int(n_steps), self.n_envs
+        if self._policy is not policy:
+            self.dev.attach_policy(policy)
+            self._policy = policy
+        table = self._draw(E * B).reshape(E, B) if self.auto_reset else None
+        r = self.dev.env_rollout(E, first_obs=self._next_obs, on_end=1 if self.auto_reset else 0, start_table=table,
+                                 check_every=1 if stop_when_done else 0)
+        live = r["live"]
+        if len(live):
+            self._ended = r["terminated"][-1] | r["truncated"][-1]
+            self._next_obs = r["observation"][-1].copy()
+            if self.auto_reset:
+                self._next_obs[self._ended] = 0.0
+                self.last_start = table[len(live) - 1]
+        out = dict(live=live)
+        for k, v in r.items():
+            if k != "live":
+                out[k] = np.ma.masked_array(v, mask=np.broadcast_to((~live).reshape(live.shape + (1,) * (v.ndim - 2)), v.shape))
+        return out
+
+
+class WeightPolicy:
+    """The trained agent of the reference as DATA: the policy net of a stable_baselines3 MlpPolicy -- Linear / Tanh hidden layers
+    (mlp_extractor.policy_net, rl_training.py:116-121) and the linear action layer (action_net) -- and its deterministic decision,
+    model.predict(obs, deterministic=True): the first index of the largest logit. This is the HOST statement, in float64 numpy on
+    the float32 weights, the observation rounded to float32 first as stable_baselines3 does; policy_kernel computes the same on the
+    device (DeviceClosedLoop.attach_policy). Inference only: no value head, no sampling, no training.
+    weights: float32 (out, in) matrices as torch stores them, biases: float32 (out,) vectors; the last pair is the action layer."""
+
+    def __init__(self, weights, biases):
+        self.weights = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+        self.biases = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
+        if len(self.weights) < 2 or len(self.weights) != len(self.biases):
+            raise ValueError("WeightPolicy: at least one hidden layer and the action layer, one bias per weight matrix")
+        for i, (w, b) in enumerate(zip(self.weights, self.biases)):
+            if w.ndim != 2 or b.shape != (w.shape[0],) or (i and w.shape[1] != self.weights[i - 1].shape[0]):
+                raise ValueError(f"WeightPolicy: layer {i} does not fit: weight {w.shape}, bias {b.shape}")
+        self.n_observations, self.n_actions = self.weights[0].shape[1], self.weights[-1].shape[0]
+
+    @classmethod
+    def from_npz(cls, path):
+        """the fixture format: W0, W1, ... and b0, b1, ... (tests/golden/wmpc_policy.npz)"""
+        d = np.load(path)
+        n = 0
+        while f"W{n}" in d.files:
+            n += 1
+        missing = [f"b{i}" for i in range(n) if f"b{i}" not in d.files]
+        if n == 0 or missing:
+            raise ValueError(f"WeightPolicy.from_npz: {path} holds no W0, W1, ... / lacks {missing}")
+        return cls([d[f"W{i}"] for i in range(n)], [d[f"b{i}"] for i in range(n)])
+
+    @classmethod
+    def from_sb3_zip(cls, path):
+        """a stable_baselines3 archive (model.save: best_model.zip): its policy.pth is a plain state dict, read with zipfile and
+        torch.load(weights_only=True) -- stable_baselines3 is not needed. Takes mlp_extractor.policy_net.<i>.weight / .bias and
+        action_net.weight / .bias; a shared trunk (mlp_extractor.shared_net) is refused, and so are missing keys."""
+        import io
+        import re
+        import zipfile
+
+        import torch
+        with zipfile.ZipFile(path) as z:
+            if "policy.pth" not in z.namelist():
+                raise ValueError(f"WeightPolicy.from_sb3_zip: {path} holds no policy.pth")
+            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
+        if any(k.startswith("mlp_extractor.shared_net") for k in sd):
+            raise ValueError("WeightPolicy.from_sb3_zip: the policy has a shared trunk (mlp_extractor.shared_net): not supported")
+        idx = sorted(int(m.group(1)) for m in (re.fullmatch(r"mlp_extractor\.policy_net\.(\d+)\.weight", k) for k in sd) if m)
+        names = [f"mlp_extractor.policy_net.{i}" for i in idx] + ["action_net"]
+        missing = [f"{n}.{p}" for n in names for p in ("weight", "bias") if f"{n}.{p}" not in sd]
+        if not idx or missing:
+            raise ValueError(f"WeightPolicy.from_sb3_zip: missing keys {missing or ['mlp_extractor.policy_net.*.weight']}")
+        return cls([sd[n + ".weight"].numpy() for n in names], [sd[n + ".bias"].numpy() for n in names])
+
+    def logits(self, obs):
+        """(n, n_actions) float64 (or (n_actions,) for one observation)"""
+        x = np.asarray(obs, dtype=np.float64)
+        h = np.atleast_2d(x).astype(np.float32).astype(np.float64)          # obs_as_tensor: float32 before the first layer
+        if h.shape[1] != self.n_observations:
+            raise ValueError(f"WeightPolicy: observations have {self.n_observations} entries")
+        for i, (w, b) in enumerate(zip(self.weights, self.biases)):
+            h = h @ w.astype(np.float64).T + b.astype(np.float64)
+            if i + 1 < len(self.weights):
+                h = np.tanh(h)
+        return h[0] if x.ndim == 1 else h
+
+    def probabilities(self, obs):
+        """get_action_probabilities (helpers.py:100-105): the softmax of the logits"""
+        z = self.logits(obs)
+        e = np.exp(z - z.max(axis=-1, keepdims=True))
+        return e / e.sum(axis=-1, keepdims=True)
+
+    def predict(self, obs):
+        """model.predict(obs, deterministic=True): the first index of the largest logit"""
+        return np.argmax(self.logits(obs), axis=-1)
+
+
+def run_policy(track_name, policy, table, starts, max_steps=400, n_mpc_steps=20, check_every=1, n_obs_stack=1, **env_kw):
+    """RL_WMPC/evaluation.py:65-105 run_policy for MANY start waypoints at once: one vehicle per entry of `starts` on `track_name`,
+    full_lap=True and no restarts -- an episode ends at the last-but-one waypoint of the track or when the vehicle leaves it -- with
+    `policy` (a WeightPolicy) picking rows of `table` (A, 7) every n_mpc_steps control steps, on the device, until every instance has
+    ended or max_steps environment steps have run. env_kw: further arguments of WeightScheduleEnv (N, Tp, max_lat_dev, log_capacity ...;
+    by default the five logs of all control steps are kept).
+    Returns a dict: actions (E, B) and probabilities (E, B, A) -- get_action_probabilities of what the policy saw at each decision,
+    through the device policy -- masked where the instance had ended; live (E, B); n_decisions (B,); rollout: everything
+    WeightScheduleEnv.rollout returned; logs: the loop's logs (None with log_capacity=0); env: the environment."""
+    if int(n_obs_stack) != 1:
+        raise ValueError("run_policy: n_obs_stack > 1 (VecFrameStack) is not supported; every shipped config has 1")
+    starts = np.atleast_1d(np.asarray(starts))
+    if starts.ndim != 1 or not np.issubdtype(starts.dtype, np.integer):
+        raise ValueError("run_policy: starts is a list of waypoint indices")
+    for k in ("full_lap", "auto_reset", "restart_indices", "idx_start"):
+        if k in env_kw:
+            raise ValueError(f"run_policy: '{k}' is run_policy's to set")
+    B = len(starts)
+    env_kw.setdefault("log_capacity", int(max_steps) * int(n_mpc_steps))
+    env = WeightScheduleEnv(track_name, B, table, n_mpc_steps=n_mpc_steps, full_lap=True, auto_reset=False, idx_start=starts.astype(np.int64), **env_kw)
+    r = env.rollout(policy, int(max_steps), stop_when_done=check_every > 0)
+    live = r["live"]
+    E = len(live)
+    seen = np.concatenate([np.zeros((1, B, env.n_observations)), r["observation"].data[:-1]])          # environment.py:230-233: reset() returns zeros
+    probs = env.dev.policy_eval(seen.reshape(E * B, -1))["probabilities"].reshape(E, B, -1)
+    probs = np.ma.masked_array(probs, mask=np.broadcast_to(~live[:, :, None], probs.shape))
+    return dict(actions=r["action"], probabilities=probs, live=live, n_decisions=live.sum(axis=0), rollout=r,
+                logs=env.dev.logs() if env.dev.log_capacity > 0 else None, env=env)

@@ -21,6 +21,7 @@
 #include "aux_kernels.hpp"
 #include "loop_kernels.hpp"
 #include "env_kernels.hpp"
+#include "policy_kernels.hpp"
 #include "sqp_kernels.hpp"
 #include "rti_kernels.hpp"
 
@@ -2213,9 +2214,23 @@ struct tum_sim {
     double *denv_table, *denv_bounds, *denv_acc, *denv_win, *denv_out, *henv_out;
     int *denv_idx, *denv_in, *denv_ep, *denv_count, *denv_flags, *denv_qpf, *denv_samples, *henv_in;
     unsigned char *env_ended;
+    // the agent (tum_sim_policy_attach): the policy net in the order policy_kernel reads it, its input inside a rollout, the live flags and
+    // their counter; the device-side log of a rollout (tum_sim_env_rollout), grown on demand
+    bool pol; PolicyArgs pa;
+    double *dpol_W[POL_MAXMAT], *dpol_b[POL_MAXMAT], *dpol_obs;
+    int *dpol_live, *dpol_nlive;
+    double *droll_log; int *droll_ints; size_t roll_cap;
 };
+static void policy_release(tum_sim *s)
+{
+    for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(s->dpol_W[l]); (void)hipFree(s->dpol_b[l]); s->dpol_W[l] = s->dpol_b[l] = nullptr; }
+    (void)hipFree(s->dpol_obs); (void)hipFree(s->dpol_live); (void)hipFree(s->dpol_nlive); (void)hipFree(s->droll_log); (void)hipFree(s->droll_ints);
+    s->dpol_obs = s->droll_log = nullptr; s->dpol_live = s->dpol_nlive = s->droll_ints = nullptr;
+    s->roll_cap = 0; s->pol = false;
+}
 static void env_release(tum_sim *s)
 {
+    policy_release(s);          // (the policy reads the environment's observation and writes its actions: it goes with it)
     (void)hipFree(s->denv_table); (void)hipFree(s->denv_bounds); (void)hipFree(s->denv_acc); (void)hipFree(s->denv_win); (void)hipFree(s->denv_out);
     (void)hipFree(s->denv_idx); (void)hipFree(s->denv_in); (void)hipFree(s->denv_ep); (void)hipFree(s->denv_count); (void)hipFree(s->denv_flags);
     (void)hipFree(s->denv_qpf); (void)hipFree(s->denv_samples);
@@ -2757,6 +2772,190 @@ extern "C" int tum_sim_env_step(tum_sim *s, const int *actions, const int *reset
         if (out[b * s->env_rec + 1] != 0.0 || out[b * s->env_rec + 2] != 0.0) s->env_ended[b] = 1;
     return lin_uniform_check(c);
 }
+
+// ---------------------------------------------------------------------------------------------- K12: the agent, whole episodes
+// The policy net of the reference's agent (a stable_baselines3 MlpPolicy with tanh activations; inference only: model.predict(obs,
+// deterministic=True) and helpers.py:100-105 get_action_probabilities) in the layout policy_kernel reads. widths[n_layers + 1]: inputs,
+// hidden widths..., actions; W[l] row-major (out, in) as torch stores it. W == NULL detaches. On a loop with an environment the widths
+// must fit it; on one without, the policy serves tum_sim_policy_eval alone (attaching an environment detaches it). Nothing a captured
+// chunk of control steps holds changes: the policy runs outside sim_run_enqueue.
+extern "C" int tum_sim_policy_attach(tum_sim *s, int n_layers, const int *widths, const float *const *W, const float *const *b)
+{
+    if (!s) return fail("null argument");
+    tum_ocp *c = s->c;
+    if (W) {
+        if (!widths || !b) return fail("null argument");
+        if (n_layers < 2 || n_layers > POL_MAXMAT) return fail("policy_attach: 1 to 4 hidden layers (n_layers 2..5 with the action layer)");
+        for (int l = 0; l < n_layers; l++) if (!W[l] || !b[l]) return fail("null argument");
+        if (widths[0] < 1 || widths[0] > POL_MAXIN) return fail("policy_attach: 1 to 128 inputs");
+        for (int l = 1; l < n_layers; l++)
+            if (widths[l] < 1 || widths[l] > POL_MAXWIDTH) return fail("policy_attach: hidden layers are 1 to 256 wide");
+        if (widths[n_layers] < 1 || widths[n_layers] > POL_MAXACT) return fail("policy_attach: 1 to 64 actions");
+        // without an environment the policy serves tum_sim_policy_eval alone; with one it reads its observation and picks rows of its table
+        if (s->env && widths[0] != s->env_rec - ENV_REC)
+            return fail("policy_attach: the policy takes " + std::to_string(widths[0]) + " inputs, the environment's observation has " + std::to_string(s->env_rec - ENV_REC) + " entries");
+        if (s->env && widths[n_layers] != s->ea.n_actions)
+            return fail("policy_attach: the policy has " + std::to_string(widths[n_layers]) + " actions, the environment's table has " + std::to_string(s->ea.n_actions) + " rows");
+    }
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    policy_release(s);
+    if (!W) return 0;
+    PolicyArgs &a = s->pa;
+    memset(&a, 0, sizeof(a));
+    a.n_mat = n_layers; a.n_in = widths[0]; a.n_act = widths[n_layers];
+    const size_t B = c->batch;
+    bool ok = true;
+    for (int l = 0; l < n_layers && ok; l++) {
+        const int in = widths[l], out = widths[l + 1], kp = (in + 3) & ~3, mp = (out + 15) & ~15;
+        a.kp[l] = kp; a.mp[l] = mp; a.rows = std::max(a.rows, std::max(kp, mp));
+        // float -> double is exact; the A operand of product (t, q) is 64 consecutive doubles: lane holds W[16 t + (lane & 15)][4 q + (lane >> 4)]
+        std::vector<double> Wp((size_t)mp * kp, 0.0), bp(mp, 0.0);
+        for (int t = 0; t < mp / 16; t++)
+            for (int q = 0; q < kp / 4; q++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int r = 16 * t + (lane & 15), k = 4 * q + (lane >> 4);
+                    if (r < out && k < in) Wp[((size_t)t * (kp / 4) + q) * 64 + lane] = (double)W[l][(size_t)r * in + k];
+                }
+        for (int r = 0; r < out; r++) bp[r] = (double)b[l][r];
+        ok = ok && dalloc(&s->dpol_W[l], Wp.size()) == hipSuccess && dalloc(&s->dpol_b[l], bp.size()) == hipSuccess;
+        ok = ok && hipMemcpy(s->dpol_W[l], Wp.data(), sizeof(double) * Wp.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(s->dpol_b[l], bp.data(), sizeof(double) * bp.size(), hipMemcpyHostToDevice) == hipSuccess;
+        a.W[l] = s->dpol_W[l]; a.b[l] = s->dpol_b[l];
+    }
+    ok = ok && dalloc(&s->dpol_obs, B * a.n_in) == hipSuccess && dalloc(&s->dpol_live, B) == hipSuccess && dalloc(&s->dpol_nlive, (size_t)1) == hipSuccess;
+    ok = ok && hipFuncSetAttribute((const void *)policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { policy_release(s); (void)hipGetLastError(); return fail("policy_attach: allocation failed"); }
+    s->pol = true;
+    return 0;
+}
+
+// one launch of the policy on the capsule's stream: n instances, observations [n][stride] on the device
+static int policy_launch(tum_sim *s, const double *dobs, int stride, int n, double *dlogits, double *dprobs, int *dactions)
+{
+    PolicyArgs a = s->pa;
+    a.n = n; a.obs = dobs; a.obs_stride = stride; a.logits = dlogits; a.probs = dprobs; a.actions = dactions;
+    hipLaunchKernelGGL(policy_kernel, dim3((n + POL_TILE - 1) / POL_TILE), dim3(64 * POL_WAVES), sizeof(double) * 2 * a.rows * POL_TILE, s->c->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the policy alone on n host observations (n x widths[0]), independent of the loop's batch: logits and probabilities n x actions, actions n
+extern "C" int tum_sim_policy_eval(tum_sim *s, const double *obs, int n, double *logits, double *probs, int *actions)
+{
+    if (!s || !obs) return fail("null argument");
+    if (!s->pol) return fail("policy_eval: no policy attached (tum_sim_policy_attach)");
+    if (n < 1) return fail("policy_eval: n < 1");
+    tum_ocp *c = s->c;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    const size_t ni = (size_t)n * s->pa.n_in, na = (size_t)n * s->pa.n_act;
+    DevTmp to, tl, tp, ta;
+    HIPCHK(to.alloc(sizeof(double) * ni)); HIPCHK(tl.alloc(sizeof(double) * na)); HIPCHK(tp.alloc(sizeof(double) * na)); HIPCHK(ta.alloc(sizeof(int) * n));
+    HIPCHK(hipMemcpy(to.as<double>(), obs, sizeof(double) * ni, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    if (policy_launch(s, to.as<double>(), s->pa.n_in, n, logits ? tl.as<double>() : nullptr, probs ? tp.as<double>() : nullptr, actions ? ta.as<int>() : nullptr)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (logits) HIPCHK(hipMemcpy(logits, tl.as<double>(), sizeof(double) * na, hipMemcpyDeviceToHost));
+    if (probs) HIPCHK(hipMemcpy(probs, tp.as<double>(), sizeof(double) * na, hipMemcpyDeviceToHost));
+    if (actions) HIPCHK(hipMemcpy(actions, ta.as<int>(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// n_env_steps x (policy, begin, n_mpc_steps control steps, finish, next) on the capsule's stream without a host wait in between; one
+// download behind the last step (and the 4-byte counter of live instances every check_every steps where asked for).
+//   first_obs (B x n_obs, NULL: zeros -- what a reset returns) is what the policy sees first.
+//   on_end 0: an instance whose episode ends is frozen out: it drives on as with reset mask 2 of tum_sim_env_step, live = 0 from the
+//             next step on and its later rows are not results. An instance whose episode had ended BEFORE the call starts with live = 0.
+//   on_end 1: it is reset at the start of step e + 1 to start_table[e + 1][b] and the policy sees zeros for it; an instance whose
+//             episode had ended before the call is reset to start_table[0][b] at step 0. start_table: n_env_steps x B.
+// The host does not know which instances the begin kernel resets: every step invalidates as if any had been. env_ended[] afterwards:
+// the flags of the last step that ran, which is what tum_sim_env_step leaves when an ended instance drives on.
+extern "C" int tum_sim_env_rollout(tum_sim *s, int n_env_steps, const double *first_obs, int on_end, const int *start_table,
+                                   int check_every, double *out, int *actions_out, int *live_out, int *steps_run)
+{
+    if (!s || !out || !actions_out || !live_out || !steps_run) return fail("null argument");
+    if (!s->env) return fail("env_rollout: no environment attached (tum_sim_env_attach)");
+    if (env_refuse(s, "env_rollout")) return 1;
+    if (!s->pol) return fail("env_rollout: no policy attached (tum_sim_policy_attach)");
+    if (n_env_steps < 1) return fail("env_rollout: n_env_steps < 1");
+    if (on_end != 0 && on_end != 1) return fail("env_rollout: on_end is 0 (an ended instance is frozen out) or 1 (it is reset)");
+    if (on_end == 1 && !start_table) return fail("env_rollout: on_end 1 resets ended instances and needs a start table (n_env_steps x batch)");
+    tum_ocp *c = s->c; const size_t B = c->batch, E = n_env_steps, rec = s->env_rec; const int no = s->pa.n_in;
+    if (start_table)
+        for (size_t i = 0; i < E * B; i++)
+            if (start_table[i] < 0 || start_table[i] >= s->n_track)
+                return fail("env_rollout: start index of instance " + std::to_string(i % B) + " at step " + std::to_string(i / B) + " is outside the track");
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (flush_inputs(c)) return 1;          // (older setters of x0 / yref in the pinned shadow go first: the begin kernel writes behind them)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (E > s->roll_cap) {
+        (void)hipFree(s->droll_log); (void)hipFree(s->droll_ints); s->droll_log = nullptr; s->droll_ints = nullptr; s->roll_cap = 0;
+        if (dalloc(&s->droll_log, E * B * rec) != hipSuccess || dalloc(&s->droll_ints, 3 * E * B) != hipSuccess) { (void)hipGetLastError(); return fail("env_rollout: allocation failed"); }
+        s->roll_cap = E;
+    }
+    int *dact = s->droll_ints, *dlive = dact + E * B, *dtab = dlive + E * B;
+    // step 0: what the host knows -- the episodes that have ended, the first observation
+    std::vector<double> obs0(B * no, 0.0);
+    std::vector<int> live0(B, 1);
+    int n_live = 0;
+    for (size_t b = 0; b < B; b++) {
+        const bool r = on_end == 1 && s->env_ended[b];
+        s->henv_in[b] = 0; s->henv_in[B + b] = r ? 1 : 0; s->henv_in[2 * B + b] = r ? start_table[b] : 0;
+        if (first_obs && !r) memcpy(&obs0[b * no], first_obs + b * no, sizeof(double) * no);
+        if (on_end == 0 && s->env_ended[b]) live0[b] = 0;
+        n_live += live0[b];
+    }
+    HIPCHK(hipMemcpy(s->denv_in, s->henv_in, sizeof(int) * 3 * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->dpol_obs, obs0.data(), sizeof(double) * B * no, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->dpol_live, live0.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->dpol_nlive, &n_live, sizeof(int), hipMemcpyHostToDevice));
+    if (start_table) HIPCHK(hipMemcpy(dtab, start_table, sizeof(int) * E * B, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    RolloutArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.batch = (int)B; ra.rec = (int)rec; ra.head = ENV_REC; ra.n_obs = no; ra.n_env_steps = n_env_steps; ra.on_end = on_end;
+    ra.out = s->denv_out; ra.in = s->denv_in; ra.start_table = start_table ? dtab : nullptr; ra.pol_obs = s->dpol_obs;
+    ra.live = s->dpol_live; ra.n_live = s->dpol_nlive; ra.log = s->droll_log; ra.act_log = dact; ra.live_log = dlive;
+    int ran = 0;
+    *steps_run = 0;
+    if (!(check_every > 0 && n_live == 0))
+        for (int e = 0; e < n_env_steps; e++) {
+            if (policy_launch(s, s->dpol_obs, no, (int)B, nullptr, nullptr, s->denv_in)) return 1;
+            // the begin kernel writes W and the penalties, and -- of the instances the DEVICE marked -- the iterate, x0 and the pose. Never
+            // CH_RESTART: a partly reset batch is not stage-uniform
+            invalidate(c, CH_W | CH_BOUNDS | CH_ITERATE | CH_X0 | CH_REF);
+            env_bind(s);
+            hipLaunchKernelGGL(env_begin_kernel, dim3(B), dim3(64), 0, c->stream, s->ea, 1);
+            HIPCHK(hipGetLastError());
+            if (sim_run_enqueue(s, s->env_mpc_steps)) return 1;
+            env_bind(s);
+            hipLaunchKernelGGL(env_finish_kernel, dim3(B), dim3(64), 0, c->stream, s->ea);
+            HIPCHK(hipGetLastError());
+            ra.e = e;
+            hipLaunchKernelGGL(rollout_next_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, ra);
+            HIPCHK(hipGetLastError());
+            ran = e + 1;
+            if (check_every > 0 && ran % check_every == 0 && ran < n_env_steps) {
+                int nl = 0;
+                HIPCHK(hipStreamSynchronize(c->stream));
+                HIPCHK(hipMemcpy(&nl, s->dpol_nlive, sizeof(int), hipMemcpyDeviceToHost));
+                if (nl == 0) break;
+            }
+        }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *steps_run = ran;
+    if (ran == 0) return 0;
+    HIPCHK(hipMemcpy(out, s->droll_log, sizeof(double) * ran * B * rec, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(actions_out, dact, sizeof(int) * ran * B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(live_out, dlive, sizeof(int) * ran * B, hipMemcpyDeviceToHost));
+    const double *last = out + (size_t)(ran - 1) * B * rec;
+    for (size_t b = 0; b < B; b++) s->env_ended[b] = (last[b * rec + 1] != 0.0 || last[b * rec + 2] != 0.0) ? 1 : 0;
+    for (int e = 0; e < ran; e++)
+        if (out[(size_t)e * B * rec + 5] != 0.0) return fail("env_rollout: planner segment longer than PLAN_MAXM points");
+    return lin_uniform_check(c);
+}
+
 
 static int env_get(tum_sim *s, const std::string &f, double *out, long long len)
 {

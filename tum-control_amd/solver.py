@@ -76,7 +76,8 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_ocp_snmpc_attach", "tum_ocp_snmpc_samples", "tum_ocp_snmpc_set_offsets",
              "tum_planner_emulate", "tum_sim_create", "tum_sim_free", "tum_sim_set_state", "tum_sim_plan", "tum_sim_advance",
              "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
-             "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step"]
+             "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step",
+             "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout"]
 
 
 def load_library(path=None):
@@ -158,6 +159,10 @@ def load_library(path=None):
         L.tum_sim_env_attach.argtypes = [vp, dp, ci, ci, cd, ci, ci, dp, dp, dp, dp, ip, ip, ci, ci]
         L.tum_sim_env_reset.argtypes = [vp, ip, ip]
         L.tum_sim_env_step.argtypes = [vp, ip, ip, ip, dp]
+    if hasattr(L, "tum_sim_policy_attach"):
+        L.tum_sim_policy_attach.argtypes = [vp, ci, ip, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+        L.tum_sim_policy_eval.argtypes = [vp, dp, ci, dp, dp, ip]
+        L.tum_sim_env_rollout.argtypes = [vp, ci, dp, ci, ip, ci, dp, ip, ip, ip]
     _libs[p] = L
     if p == LIB_PATH:
         _lib = L
@@ -896,10 +901,12 @@ class DeviceClosedLoop:
                                              int(bool(full_lap)), _dp(sig), _dp(lo_hi), _dp(ob[0]), _dp(ob[1]), iv.ctypes.data_as(ip),
                                              ir.ctypes.data_as(ip), n, self._OBS_STATES[obs_states]), "sim_env_attach")
         self.env_n_obs = 2 + 2 * n
+        self.policy_widths = None          # (attaching an environment detaches the policy of the one before)
 
     def detach_env(self):
         self._chk(self._L.tum_sim_env_attach(self._s, None, 0, 0, 0.0, 0, 0, None, None, None, None, None, None, 0, 0), "sim_env_attach")
         self.env_n_obs = 0
+        self.policy_widths = None
 
     def _ints(self, a):
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(a), (self.B,)))
@@ -935,6 +942,79 @@ class DeviceClosedLoop:
         out = np.empty(self.B)
         self._chk(self._L.tum_sim_get(self._s, ("env_" + field).encode(), _dp(out), out.size), "sim_get env_" + field)
         return out.astype(np.int64)
+
+    # ---- the agent of the environment (enable_WMPC of the controller classes, RL_WMPC/evaluation.py:65-105)
+    def attach_policy(self, policy):
+        """The policy net that picks the environment's actions on the device: `policy` has .weights / .biases, lists of float32 arrays
+        (out, in) / (out,) -- closed_loop.WeightPolicy. 1 to 4 hidden layers up to 256 wide, tanh, up to 128 inputs and 64 actions; its
+        input width is the environment's observation, its action count the rows of the environment's table."""
+        Ws = [np.ascontiguousarray(w) for w in policy.weights]
+        bs = [np.ascontiguousarray(b) for b in policy.biases]
+        if len(Ws) != len(bs) or len(Ws) < 1:
+            raise Exception("attach_policy: one bias per weight matrix")
+        for w, b in zip(Ws, bs):
+            if w.dtype != np.float32 or b.dtype != np.float32 or w.ndim != 2 or b.shape != (w.shape[0],):
+                raise Exception("attach_policy: weights are float32 (out, in) matrices, biases float32 (out,) vectors")
+        for w0, w1 in zip(Ws, Ws[1:]):
+            if w1.shape[1] != w0.shape[0]:
+                raise Exception("attach_policy: the layers do not chain")
+        widths = np.array([Ws[0].shape[1]] + [w.shape[0] for w in Ws], dtype=np.int32)
+        pw = (ctypes.c_void_p * len(Ws))(*[w.ctypes.data for w in Ws])
+        pb = (ctypes.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
+        self._chk(self._L.tum_sim_policy_attach(self._s, len(Ws), widths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), pw, pb), "sim_policy_attach")
+        self.policy_widths = tuple(int(w) for w in widths)
+
+    def detach_policy(self):
+        self._chk(self._L.tum_sim_policy_attach(self._s, 0, None, None, None), "sim_policy_attach")
+        self.policy_widths = None
+
+    def policy_eval(self, obs):
+        """the attached policy alone on (n, n_obs) observations, independent of the loop's batch: dict of logits (n, A), probabilities
+        (n, A) -- the softmax of the logits -- and actions (n,), the first index of the largest logit"""
+        w = getattr(self, "policy_widths", None)
+        if not w:
+            raise Exception("policy_eval: no policy attached (attach_policy)")
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != w[0] or obs.shape[0] < 1:
+            raise Exception(f"policy_eval: observations are (n, {w[0]}), n >= 1")
+        n = obs.shape[0]
+        logits, probs, act = np.empty((n, w[-1])), np.empty((n, w[-1])), np.empty(n, dtype=np.int32)
+        self._chk(self._L.tum_sim_policy_eval(self._s, _dp(obs), n, _dp(logits), _dp(probs), act.ctypes.data_as(ctypes.POINTER(ctypes.c_int))),
+                  "sim_policy_eval")
+        return dict(logits=logits, probabilities=probs, actions=act.astype(np.int64))
+
+    def env_rollout(self, n_env_steps, first_obs=None, on_end=0, start_table=None, check_every=0):
+        """n_env_steps environment steps with the attached policy choosing every action, without a host wait in between. first_obs
+        (B, n_obs) what the policy sees first (None: zeros, what a reset returns). on_end 0: an ended instance is frozen out (live 0
+        from the next step on; its later rows are not results); on_end 1: it is reset at the start of step e + 1 to
+        start_table[e + 1][b] -- (n_env_steps, B) -- and the policy sees zeros for it. check_every > 0: the rollout stops when no
+        instance is live, looked at every check_every steps. Returns a dict of (E, B[, ...]) arrays over the E steps that ran: the
+        fields of env_step, action and live."""
+        ip = ctypes.POINTER(ctypes.c_int)
+        E, B, no = int(n_env_steps), self.B, getattr(self, "env_n_obs", 0)
+        if E < 1:
+            raise Exception("env_rollout: n_env_steps < 1")
+        fo = None
+        if first_obs is not None:
+            fo = np.ascontiguousarray(first_obs, dtype=np.float64)
+            if fo.shape != (B, no):
+                raise Exception(f"env_rollout: first_obs is ({B}, {no})")
+        tab = None
+        if start_table is not None:
+            tab = np.asarray(start_table)
+            if tab.shape != (E, B) or not np.issubdtype(tab.dtype, np.integer):
+                raise Exception(f"env_rollout: start_table is an integer array ({E}, {B})")
+            tab = np.ascontiguousarray(tab, dtype=np.int32)
+        out = np.zeros((E, B, self.ENV_HEAD + no))
+        act, live, ran = np.zeros((E, B), dtype=np.int32), np.zeros((E, B), dtype=np.int32), ctypes.c_int(0)
+        self._chk(self._L.tum_sim_env_rollout(self._s, E, None if fo is None else _dp(fo), int(on_end), None if tab is None else tab.ctypes.data_as(ip),
+                                              int(check_every), _dp(out), act.ctypes.data_as(ip), live.ctypes.data_as(ip), ctypes.byref(ran)),
+                  "sim_env_rollout")
+        n = ran.value
+        out = out[:n]
+        return dict(action=act[:n].astype(np.int64), live=live[:n] != 0, reward=out[:, :, 0].copy(), terminated=out[:, :, 1] != 0,
+                    truncated=out[:, :, 2] != 0, step_length=out[:, :, 3].astype(np.int64), qp_failures=out[:, :, 4].astype(np.int64),
+                    observation=out[:, :, self.ENV_HEAD:].copy())
 
 
 def env_observation_bounds(n_samples):
