@@ -480,7 +480,7 @@ int tum_sim_env_step(tum_sim *s, const int *actions, const int *reset_mask, cons
  * "env_flags" (1 terminated, 2 truncated), "env_qp_failures", "env_samples" (samples the estimator has seen), "env_ended". */
 
 /* --- K12: the agent of the environment on the device (enable_WMPC of the reference's controller classes, RL_WMPC/evaluation.py:65-105
- * run_policy: model.predict(obs, deterministic=True) of a stable_baselines3 MlpPolicy with tanh activations). Inference only.
+ * run_policy: model.predict(obs, deterministic=True) of a stable_baselines3 MlpPolicy with tanh activations). Inference; sampling and the value net are K13 below.
  * The policy net is evaluated in FP64 on the float32 weights, the observation rounded to float32 first as stable_baselines3 does:
  * h = tanh(W h + b) per hidden layer, a linear action layer, the action the first index of the largest logit, the probabilities the
  * softmax of the logits (helpers.py:100-105).
@@ -506,6 +506,40 @@ int tum_sim_policy_eval(tum_sim *s, const double *obs, int n, double *logits, do
  * "env_ended" afterwards: the flags of the last step that ran. tum_sim_env_step works unchanged after a rollout. */
 int tum_sim_env_rollout(tum_sim *s, int n_env_steps, const double *first_obs, int on_end, const int *start_table,
                         int check_every, double *out, int *actions_out, int *live_out, int *steps_run);
+
+/* --- K13: collecting PPO training rollouts on the device (stable_baselines3 collect_rollouts + compute_returns_and_advantage as
+ * rl_training.py's model.learn drives them). The PPO update is not here.
+ * The value net of the agent beside the attached policy (mlp_extractor.value_net.<i>, value_net): widths[n_layers + 1] = inputs,
+ * hidden widths..., 1, with widths[0] the attached policy's inputs; 1 to 4 hidden layers up to 256 wide, its own depth and widths.
+ * W == NULL detaches. Refused without a policy; detaching or re-attaching the policy or the environment detaches it. */
+int tum_sim_policy_attach_value(tum_sim *s, int n_layers, const int *widths, const float *const *W, const float *const *b);
+/* The two nets and ONE draw per observation on n host observations (n x widths[0] doubles). The draw of observation i is the uniform
+ * u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (first_instance + i, t & 0xffffffff, t >> 32, 0); with e_j = exp(z_j - max z) and prefix sums c_j in index order, S = c_{A-1}, the
+ * action is the smallest j with u S < c_j (A - 1 if none) and log_probs = (z_a - max z) - log S. This is the project's own sampling
+ * rule: the distribution of stable_baselines3, not the draws of torch.multinomial. Any output may be NULL; values needs the value net. */
+int tum_sim_policy_eval_ac(tum_sim *s, const double *obs, int n, unsigned long long seed, unsigned long long t, unsigned first_instance,
+                           int *actions, double *values, double *log_probs, double *uniforms);
+/* Generalised advantage estimation alone on host arrays (rewards, values, episode_starts: E x B; last_values, last_dones: B), FP64:
+ *   nnt = 1 - (t == E-1 ? last_dones : episode_starts[t+1]);  nv = t == E-1 ? last_values : values[t+1]
+ *   delta = (rewards[t] + (gamma nv) nnt) - values[t];  last = delta + ((gamma lambda) nnt) last;  adv[t] = last;  ret[t] = adv[t] + values[t] */
+int tum_sim_gae(tum_sim *s, int E, int B, const double *rewards, const double *values, const double *episode_starts,
+                const double *last_values, const double *last_dones, double gamma, double lambda, double *adv, double *ret);
+/* tum_sim_env_rollout with on_end 1, SAMPLED actions (decision counter t0 + e at step e, counter word 0 the instance's index) and the
+ * record of a RolloutBuffer, GAE included; everything is enqueued, one wait and one download at the end.
+ * first_obs (B x n_obs, NULL = zeros) and first_episode_starts (B, NULL = ones): what the policy sees first and whether that begins an
+ * episode. start_table: n_env_steps x B, as for the rollout.
+ * rewards = rewards_raw + gamma V(the step's own observation) where truncated && !terminated (stable_baselines3's TimeLimit.truncated;
+ * in the reference's naming that is the crash, not the episode length).
+ * out: TUM_COLLECT_FIELDS fields of n_env_steps x B doubles each, in the order of the enum below, then the observations the policy
+ * saw (n_env_steps x B x n_obs), then last_values (B) -- the value of what the policy would see next, zeros for an instance that just
+ * ended -- last_dones (B) and what the policy would see next (B x n_obs: the first_obs of a following call). Refuses what the rollout
+ * refuses, and a missing value net. */
+enum { TUM_COLLECT_ACTION, TUM_COLLECT_VALUE, TUM_COLLECT_LOG_PROB, TUM_COLLECT_REWARD, TUM_COLLECT_REWARD_RAW, TUM_COLLECT_EPISODE_START,
+       TUM_COLLECT_ADVANTAGE, TUM_COLLECT_RETURN, TUM_COLLECT_TERMINATED, TUM_COLLECT_TRUNCATED, TUM_COLLECT_STEP_LENGTH,
+       TUM_COLLECT_QP_FAILURES, TUM_COLLECT_PLANNER_ERROR, TUM_COLLECT_FIELDS };
+int tum_sim_env_collect(tum_sim *s, int n_env_steps, const double *first_obs, const double *first_episode_starts, const int *start_table,
+                        unsigned long long seed, unsigned long long t0, double gamma, double gae_lambda, double *out);
 
 /* development aid: one solve with in-kernel phase timers; out = batch x 12 shader-cycle counters
  * [linearise, condense, ipm-residuals, M assembly, Cholesky, rhs, tri-solves, row updates, (iteration tail), expand+cost] */

@@ -602,6 +602,10 @@ class WeightScheduleEnv:
         self._ended = np.zeros(self.n_envs, dtype=bool)
         self._next_obs = np.zeros((self.n_envs, self.n_observations))          # what an agent sees next (rollout)
         self._policy = None
+        # collect(): the seed of the draws, the decision counter (one per environment step, whoever drives it) and whether what the
+        # agent sees next begins an episode (_last_episode_starts of stable_baselines3)
+        self._seed, self._t = int(seed), 0
+        self._episode_starts = np.ones(self.n_envs)
 
     def _draw(self, n):
         return self.restart_indices[self._rng.randint(0, len(self.restart_indices), size=n)]
@@ -616,6 +620,7 @@ class WeightScheduleEnv:
         self._ended[m] = False
         self.last_start = start
         self._next_obs[m] = 0.0
+        self._episode_starts[m] = 1.0
         return np.zeros((self.n_envs, self.n_observations)), {}
 
     def step(self, actions):
@@ -634,6 +639,8 @@ class WeightScheduleEnv:
         if self.auto_reset:
             obs[self._ended] = 0.0
         self._next_obs = obs.copy()
+        self._episode_starts = self._ended.astype(float)
+        self._t += 1
         return obs, r["reward"], r["terminated"], r["truncated"], info
 
     def rollout(self, policy, n_steps, stop_when_done=False):
@@ -660,6 +667,8 @@ class WeightScheduleEnv:
         live = r["live"]
         if len(live):
             self._ended = r["terminated"][-1] | r["truncated"][-1]
+            self._episode_starts = self._ended.astype(float)
+            self._t += len(live)
             self._next_obs = r["observation"][-1].copy()
             if self.auto_reset:
                 self._next_obs[self._ended] = 0.0
@@ -670,16 +679,104 @@ class WeightScheduleEnv:
                 out[k] = np.ma.masked_array(v, mask=np.broadcast_to((~live).reshape(live.shape + (1,) * (v.ndim - 2)), v.shape))
         return out
 
+    def collect(self, policy, n_steps, gamma, gae_lambda, seed=None):
+        """What stable_baselines3's collect_rollouts and compute_returns_and_advantage leave in a RolloutBuffer, for n_steps environment
+        steps ON THE DEVICE with one wait at the end: `policy` (a WeightPolicy WITH a value net) samples every action -- one Philox
+        draw per instance and step, WeightPolicy.sample -- policy_ac_kernel, the environment, collect_next_kernel and gae_kernel are
+        enqueued back to back. Equal, bit for bit, to the host-driven loop: dev.policy_eval_ac on the observation just returned,
+        step(), the value of the terminal observations, gae().
+        seed: of the draws (None: the environment's); the decision counter is the environment's: it advances by one per environment
+        step (step() and rollout() included), so consecutive calls continue one stream, and one episode bookkeeping: episode_starts of
+        the first row is what the last reset() / step() / rollout() / collect() left. The policy is attached anew at every call:
+        changed weights between two calls are what a training loop has. Needs auto_reset=True; the start waypoints are drawn before
+        the call as rollout() draws them.
+        Returns a dict of (E, B[, n_obs]) arrays: observations (what the policy saw), actions, log_probs, values, rewards (with
+        gamma V(terminal observation) added where truncated and not terminated: the CRASH, environment.py:152-165), rewards_raw,
+        episode_starts, advantages, returns, terminated, truncated, step_length, qp_failures; and last_values, last_dones (B,).
+        Everything is float64 (stable_baselines3 keeps float32 buffers)."""
+        E, B = int(n_steps), self.n_envs
+        if not self.auto_reset:
+            raise ValueError("WeightScheduleEnv.collect: needs auto_reset=True (an ended instance is reset, as in a VecEnv)")
+        if getattr(policy, "value_weights", None) is None:
+            raise ValueError("WeightScheduleEnv.collect: the policy carries no value net")
+        if E < 1:
+            raise ValueError("WeightScheduleEnv.collect: n_steps < 1")
+        self.dev.attach_policy(policy)
+        self._policy = policy
+        table = self._draw(E * B).reshape(E, B)
+        r = self.dev.env_collect(E, table, self._seed if seed is None else int(seed), self._t, gamma, gae_lambda,
+                                 first_obs=self._next_obs, first_episode_starts=self._episode_starts)
+        self._t += E
+        self._ended = r["terminated"][-1] | r["truncated"][-1]
+        self._episode_starts = self._ended.astype(float)
+        self._next_obs = r.pop("next_observation")
+        self.last_start = table[-1]
+        return r
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The random numbers of collect(): the project's own rule (INTEGRATION.md) -- torch.multinomial's stream cannot be reproduced.
+
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon et al., Random123): counter (..., 4) and key (..., 2) of 32-bit words -> (..., 4) uint32"""
+    c = np.array(np.broadcast_arrays(*[np.asarray(counter, dtype=np.uint64)[..., i] for i in range(4)]), dtype=np.uint64)
+    k = [np.asarray(key, dtype=np.uint64)[..., i] for i in range(2)]
+    m32 = np.uint64(0xffffffff)
+    for _ in range(10):
+        p0, p1 = np.uint64(PHILOX_M[0]) * c[0], np.uint64(PHILOX_M[1]) * c[2]
+        c = np.array([(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & m32], dtype=np.uint64)
+        k = [(k[0] + np.uint64(PHILOX_W[0])) & m32, (k[1] + np.uint64(PHILOX_W[1])) & m32]
+    return np.moveaxis(c, 0, -1).astype(np.uint32)
+
+
+def uniform_from_words(x0, x1):
+    """u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 in [0, 1): integer work and an exact conversion"""
+    m = (np.asarray(x0, dtype=np.uint64) >> np.uint64(5)) * np.uint64(1 << 26) + (np.asarray(x1, dtype=np.uint64) >> np.uint64(6))
+    return m.astype(np.float64) * 2.0 ** -53
+
+
+def policy_uniforms(seed, t, n, first_instance=0):
+    """(n,) uniforms of the instances first_instance .. first_instance + n - 1 at decision t: key (seed & 0xffffffff, seed >> 32),
+    counter (b, t & 0xffffffff, t >> 32, 0). A draw depends on (seed, b, t) alone."""
+    seed, t = int(seed) & (2 ** 64 - 1), int(t) & (2 ** 64 - 1)
+    ctr = np.zeros((int(n), 4), dtype=np.uint64)
+    ctr[:, 0] = (int(first_instance) + np.arange(int(n), dtype=np.uint64)) & np.uint64(0xffffffff)
+    ctr[:, 1], ctr[:, 2] = t & 0xffffffff, t >> 32
+    x = philox4x32(ctr, np.array([seed & 0xffffffff, seed >> 32], dtype=np.uint64))
+    return uniform_from_words(x[:, 0], x[:, 1])
+
+
+def gae(rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda):
+    """RolloutBuffer.compute_returns_and_advantage on (E, B) float64 arrays, in the association gae_kernel uses: (advantages, returns)"""
+    rewards, values, episode_starts = (np.asarray(a, dtype=np.float64) for a in (rewards, values, episode_starts))
+    E = rewards.shape[0]
+    adv = np.zeros_like(rewards)
+    last = np.zeros(rewards.shape[1:])
+    for t in range(E - 1, -1, -1):
+        nnt = 1.0 - (np.asarray(last_dones, dtype=np.float64) if t == E - 1 else episode_starts[t + 1])
+        nv = np.asarray(last_values, dtype=np.float64) if t == E - 1 else values[t + 1]
+        delta = (rewards[t] + (gamma * nv) * nnt) - values[t]
+        last = delta + ((gamma * gae_lambda) * nnt) * last
+        adv[t] = last
+    return adv, adv + values
+
 
 class WeightPolicy:
     """The trained agent of the reference as DATA: the policy net of a stable_baselines3 MlpPolicy -- Linear / Tanh hidden layers
     (mlp_extractor.policy_net, rl_training.py:116-121) and the linear action layer (action_net) -- and its deterministic decision,
     model.predict(obs, deterministic=True): the first index of the largest logit. This is the HOST statement, in float64 numpy on
     the float32 weights, the observation rounded to float32 first as stable_baselines3 does; policy_kernel computes the same on the
-    device (DeviceClosedLoop.attach_policy). Inference only: no value head, no sampling, no training.
-    weights: float32 (out, in) matrices as torch stores them, biases: float32 (out,) vectors; the last pair is the action layer."""
+    device (DeviceClosedLoop.attach_policy). No training.
+    weights: float32 (out, in) matrices as torch stores them, biases: float32 (out,) vectors; the last pair is the action layer.
+    value_weights / value_biases (optional): the value net of the same archive (mlp_extractor.value_net, value_net) with its own
+    hidden layers, the same inputs and a last matrix of one row. With it the object also states what collecting training data needs:
+    values, log_prob and sample -- the sampling rule of policy_ac_kernel. Without it the object is the inference-only one."""
 
-    def __init__(self, weights, biases):
+    def __init__(self, weights, biases, value_weights=None, value_biases=None):
         self.weights = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
         self.biases = [np.ascontiguousarray(b, dtype=np.float32) for b in biases]
         if len(self.weights) < 2 or len(self.weights) != len(self.biases):
@@ -688,10 +785,27 @@ class WeightPolicy:
             if w.ndim != 2 or b.shape != (w.shape[0],) or (i and w.shape[1] != self.weights[i - 1].shape[0]):
                 raise ValueError(f"WeightPolicy: layer {i} does not fit: weight {w.shape}, bias {b.shape}")
         self.n_observations, self.n_actions = self.weights[0].shape[1], self.weights[-1].shape[0]
+        self.value_weights = self.value_biases = None
+        if (value_weights is None) != (value_biases is None):
+            raise ValueError("WeightPolicy: a value net is value_weights AND value_biases")
+        if value_weights is not None:
+            vw = [np.ascontiguousarray(w, dtype=np.float32) for w in value_weights]
+            vb = [np.ascontiguousarray(b, dtype=np.float32) for b in value_biases]
+            if len(vw) < 2 or len(vw) != len(vb):
+                raise ValueError("WeightPolicy: the value net has at least one hidden layer and the value layer, one bias per weight matrix")
+            for i, (w, b) in enumerate(zip(vw, vb)):
+                if w.ndim != 2 or b.shape != (w.shape[0],) or (i and w.shape[1] != vw[i - 1].shape[0]):
+                    raise ValueError(f"WeightPolicy: value layer {i} does not fit: weight {w.shape}, bias {b.shape}")
+            if vw[0].shape[1] != self.n_observations:
+                raise ValueError(f"WeightPolicy: the value net takes {vw[0].shape[1]} inputs, the policy net {self.n_observations}")
+            if vw[-1].shape[0] != 1:
+                raise ValueError("WeightPolicy: the last matrix of the value net has one row")
+            self.value_weights, self.value_biases = vw, vb
 
     @classmethod
-    def from_npz(cls, path):
-        """the fixture format: W0, W1, ... and b0, b1, ... (tests/golden/wmpc_policy.npz)"""
+    def from_npz(cls, path, value_path=None):
+        """the fixture format: W0, W1, ... and b0, b1, ... (tests/golden/wmpc_policy.npz); the value net V0, V1, ... and c0, c1, ...
+        where `path` -- or value_path, a second file (tests/golden/wmpc_value.npz) -- holds them"""
         d = np.load(path)
         n = 0
         while f"W{n}" in d.files:
@@ -699,13 +813,22 @@ class WeightPolicy:
         missing = [f"b{i}" for i in range(n) if f"b{i}" not in d.files]
         if n == 0 or missing:
             raise ValueError(f"WeightPolicy.from_npz: {path} holds no W0, W1, ... / lacks {missing}")
-        return cls([d[f"W{i}"] for i in range(n)], [d[f"b{i}"] for i in range(n)])
+        v = d if value_path is None else np.load(value_path)
+        m = 0
+        while f"V{m}" in v.files:
+            m += 1
+        missing = [f"c{i}" for i in range(m) if f"c{i}" not in v.files]
+        if missing or (value_path is not None and m == 0):
+            raise ValueError(f"WeightPolicy.from_npz: {value_path or path} holds no V0, V1, ... / lacks {missing}")
+        value = ([v[f"V{i}"] for i in range(m)], [v[f"c{i}"] for i in range(m)]) if m else (None, None)
+        return cls([d[f"W{i}"] for i in range(n)], [d[f"b{i}"] for i in range(n)], *value)
 
     @classmethod
     def from_sb3_zip(cls, path):
         """a stable_baselines3 archive (model.save: best_model.zip): its policy.pth is a plain state dict, read with zipfile and
         torch.load(weights_only=True) -- stable_baselines3 is not needed. Takes mlp_extractor.policy_net.<i>.weight / .bias and
-        action_net.weight / .bias; a shared trunk (mlp_extractor.shared_net) is refused, and so are missing keys."""
+        action_net.weight / .bias, and -- when the archive has them -- mlp_extractor.value_net.<i> and value_net as the value net; a
+        shared trunk (mlp_extractor.shared_net) is refused, and so are missing keys."""
         import io
         import re
         import zipfile
@@ -722,19 +845,56 @@ class WeightPolicy:
         missing = [f"{n}.{p}" for n in names for p in ("weight", "bias") if f"{n}.{p}" not in sd]
         if not idx or missing:
             raise ValueError(f"WeightPolicy.from_sb3_zip: missing keys {missing or ['mlp_extractor.policy_net.*.weight']}")
-        return cls([sd[n + ".weight"].numpy() for n in names], [sd[n + ".bias"].numpy() for n in names])
+        vidx = sorted(int(m.group(1)) for m in (re.fullmatch(r"mlp_extractor\.value_net\.(\d+)\.weight", k) for k in sd) if m)
+        value = (None, None)
+        if vidx or "value_net.weight" in sd:
+            vnames = [f"mlp_extractor.value_net.{i}" for i in vidx] + ["value_net"]
+            missing = [f"{n}.{p}" for n in vnames for p in ("weight", "bias") if f"{n}.{p}" not in sd]
+            if not vidx or missing:
+                raise ValueError(f"WeightPolicy.from_sb3_zip: missing keys {missing or ['mlp_extractor.value_net.*.weight']}")
+            value = ([sd[n + ".weight"].numpy() for n in vnames], [sd[n + ".bias"].numpy() for n in vnames])
+        return cls([sd[n + ".weight"].numpy() for n in names], [sd[n + ".bias"].numpy() for n in names], *value)
 
-    def logits(self, obs):
-        """(n, n_actions) float64 (or (n_actions,) for one observation)"""
+    def _forward(self, obs, weights, biases):
         x = np.asarray(obs, dtype=np.float64)
         h = np.atleast_2d(x).astype(np.float32).astype(np.float64)          # obs_as_tensor: float32 before the first layer
         if h.shape[1] != self.n_observations:
             raise ValueError(f"WeightPolicy: observations have {self.n_observations} entries")
-        for i, (w, b) in enumerate(zip(self.weights, self.biases)):
+        for i, (w, b) in enumerate(zip(weights, biases)):
             h = h @ w.astype(np.float64).T + b.astype(np.float64)
-            if i + 1 < len(self.weights):
+            if i + 1 < len(weights):
                 h = np.tanh(h)
         return h[0] if x.ndim == 1 else h
+
+    def logits(self, obs):
+        """(n, n_actions) float64 (or (n_actions,) for one observation)"""
+        return self._forward(obs, self.weights, self.biases)
+
+    def values(self, obs):
+        """(n,) float64 (a scalar for one observation): the value net"""
+        if self.value_weights is None:
+            raise ValueError("WeightPolicy.values: no value net")
+        return self._forward(obs, self.value_weights, self.value_biases)[..., 0]
+
+    def _prefix_sums(self, obs):
+        """z - max z and the prefix sums, in index order, of exp(z - max z): (n, A) each"""
+        z = np.atleast_2d(self.logits(obs))
+        d = z - z.max(axis=-1, keepdims=True)
+        return d, np.cumsum(np.exp(d), axis=-1)
+
+    def log_prob(self, obs, actions):
+        """(n,) log-probability of the given actions: (z_a - max z) - log S, S the sum of exp(z - max z) in index order"""
+        d, c = self._prefix_sums(obs)
+        a = np.broadcast_to(np.asarray(actions, dtype=np.int64), (len(d),))
+        return d[np.arange(len(d)), a] - np.log(c[:, -1])
+
+    def sample(self, obs, seed, t, first_instance=0):
+        """(n,) sampled actions, row i with the uniform u of (seed, first_instance + i, t) (policy_uniforms): the smallest j with
+        u S < c_j, c the prefix sums of exp(z - max z) in index order and S the last of them; n_actions - 1 if there is none"""
+        d, c = self._prefix_sums(obs)
+        u = policy_uniforms(seed, t, len(d), first_instance)
+        below = (u * c[:, -1])[:, None] < c
+        return np.where(below.any(axis=1), np.argmax(below, axis=1), self.n_actions - 1)
 
     def probabilities(self, obs):
         """get_action_probabilities (helpers.py:100-105): the softmax of the logits"""

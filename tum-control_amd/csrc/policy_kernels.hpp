@@ -6,7 +6,9 @@
 //                        stable_baselines3 does. One WORKGROUP of POL_WAVES wavefronts owns a tile of 16 instances: D[output][instance]
 //                        accumulates on v_mfma_f64_16x16x4_f64 over K in steps of 4, A a 16 x 4 block of W, B the activations
 //                        h[k][instance] from LDS; the activations ping-pong between two LDS buffers; the 16-output tiles of a layer are
-//                        spread over the wavefronts, a barrier between layers. Every weight read serves 16 instances.
+//                        spread over the wavefronts, a barrier between layers. Every weight read serves 16 instances. The load of
+//                        the observation and the layer loop are device functions (policy_load_obs, policy_layers) that
+//                        policy_ac_kernel of collect_kernels.hpp runs as well: one order of sums for both.
 //   rollout_next_kernel  one lane per instance, behind env_finish_kernel inside a rollout: the record into the rollout's log, the next
 //                        step's reset mask / start index and the policy's next input, the live flag and the counter of live instances.
 #pragma once
@@ -65,22 +67,23 @@ __device__ __forceinline__ void policy_decide(const PolicyArgs &a, const double 
     }
 }
 
-__global__ void __launch_bounds__(64 * POL_WAVES) policy_kernel(const PolicyArgs a)
+// The observation of a tile into one LDS buffer, rounded to float32 (stable_baselines3: obs_as_tensor -> float32 before the first
+// Linear); zero rows up to kp[0], zero columns behind the last instance of a partial tile. The caller puts the barrier behind it.
+__device__ __forceinline__ void policy_load_obs(const PolicyArgs &a, double *dst, int i0, int tid)
 {
-    extern __shared__ __attribute__((aligned(16))) double pol_lds[];          // [2][rows][16]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i0 = blockIdx.x * POL_TILE;
-    const int col = lane & 15, quad = lane >> 4;
-    double *buf[2] = {pol_lds, pol_lds + (size_t)a.rows * POL_TILE};
-    // the observation, rounded to float32 (stable_baselines3: obs_as_tensor -> float32 before the first Linear); zero rows up to kp[0],
-    // zero columns behind the last instance of a partial tile
     for (int i = tid; i < a.kp[0] * POL_TILE; i += 64 * POL_WAVES) {
         const int inst = i / a.kp[0], k = i - inst * a.kp[0];
         double v = 0.0;
         if (i0 + inst < a.n && k < a.n_in) v = (double)(float)a.obs[(size_t)(i0 + inst) * a.obs_stride + k];
-        buf[0][k * POL_TILE + inst] = v;
+        dst[k * POL_TILE + inst] = v;
     }
-    __syncthreads();
+}
+
+// The layers of one net on the tile whose input is in buf[0]: the result of matrix l is in buf[(l + 1) & 1], a barrier behind every
+// layer. policy_kernel and policy_ac_kernel both run this loop and nothing else on the matrices: one order of sums.
+__device__ __forceinline__ void policy_layers(const PolicyArgs &a, double *const *buf, int lane, int wave)
+{
+    const int col = lane & 15, quad = lane >> 4;
     for (int l = 0; l < a.n_mat; l++) {
         const double *src = buf[l & 1];
         double *dst = buf[(l + 1) & 1];
@@ -105,6 +108,17 @@ __global__ void __launch_bounds__(64 * POL_WAVES) policy_kernel(const PolicyArgs
         }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(64 * POL_WAVES) policy_kernel(const PolicyArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double pol_lds[];          // [2][rows][16]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i0 = blockIdx.x * POL_TILE;
+    double *buf[2] = {pol_lds, pol_lds + (size_t)a.rows * POL_TILE};
+    policy_load_obs(a, buf[0], i0, tid);
+    __syncthreads();
+    policy_layers(a, buf, lane, wave);
     if (tid < POL_TILE && i0 + tid < a.n) policy_decide(a, buf[a.n_mat & 1] + tid, i0 + tid);
 }
 

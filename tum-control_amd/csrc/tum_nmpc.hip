@@ -22,6 +22,7 @@
 #include "loop_kernels.hpp"
 #include "env_kernels.hpp"
 #include "policy_kernels.hpp"
+#include "collect_kernels.hpp"
 #include "sqp_kernels.hpp"
 #include "rti_kernels.hpp"
 
@@ -2220,9 +2221,22 @@ struct tum_sim {
     double *dpol_W[POL_MAXMAT], *dpol_b[POL_MAXMAT], *dpol_obs;
     int *dpol_live, *dpol_nlive;
     double *droll_log; int *droll_ints; size_t roll_cap;
+    // the value net beside it (tum_sim_policy_attach_value), the value of a step's own observation and the episode-start flags of a
+    // collection's first step, and the device-side buffer of a collection with its start table (tum_sim_env_collect), grown on demand
+    PolicyArgs va;
+    double *dval_W[POL_MAXMAT], *dval_b[POL_MAXMAT], *dval_term, *dval_starts;
+    double *dcol; int *dcol_tab; size_t col_cap;
 };
+static void value_release(tum_sim *s)
+{
+    for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(s->dval_W[l]); (void)hipFree(s->dval_b[l]); s->dval_W[l] = s->dval_b[l] = nullptr; }
+    (void)hipFree(s->dval_term); (void)hipFree(s->dval_starts); (void)hipFree(s->dcol); (void)hipFree(s->dcol_tab);
+    s->dval_term = s->dval_starts = s->dcol = nullptr; s->dcol_tab = nullptr;
+    s->col_cap = 0; s->va.n_mat = 0;
+}
 static void policy_release(tum_sim *s)
 {
+    value_release(s);          // (the value net takes the policy's inputs: it goes with it)
     for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(s->dpol_W[l]); (void)hipFree(s->dpol_b[l]); s->dpol_W[l] = s->dpol_b[l] = nullptr; }
     (void)hipFree(s->dpol_obs); (void)hipFree(s->dpol_live); (void)hipFree(s->dpol_nlive); (void)hipFree(s->droll_log); (void)hipFree(s->droll_ints);
     s->dpol_obs = s->droll_log = nullptr; s->dpol_live = s->dpol_nlive = s->droll_ints = nullptr;
@@ -2779,6 +2793,32 @@ extern "C" int tum_sim_env_step(tum_sim *s, const int *actions, const int *reset
 // hidden widths..., actions; W[l] row-major (out, in) as torch stores it. W == NULL detaches. On a loop with an environment the widths
 // must fit it; on one without, the policy serves tum_sim_policy_eval alone (attaching an environment detaches it). Nothing a captured
 // chunk of control steps holds changes: the policy runs outside sim_run_enqueue.
+// a net in the layout policy_layers reads, on the device; false where an allocation or a copy failed (the caller releases)
+static bool net_upload(PolicyArgs &a, int n_layers, const int *widths, const float *const *W, const float *const *b, double **dW, double **db)
+{
+    memset(&a, 0, sizeof(a));
+    a.n_mat = n_layers; a.n_in = widths[0]; a.n_act = widths[n_layers];
+    bool ok = true;
+    for (int l = 0; l < n_layers && ok; l++) {
+        const int in = widths[l], out = widths[l + 1], kp = (in + 3) & ~3, mp = (out + 15) & ~15;
+        a.kp[l] = kp; a.mp[l] = mp; a.rows = std::max(a.rows, std::max(kp, mp));
+        // float -> double is exact; the A operand of product (t, q) is 64 consecutive doubles: lane holds W[16 t + (lane & 15)][4 q + (lane >> 4)]
+        std::vector<double> Wp((size_t)mp * kp, 0.0), bp(mp, 0.0);
+        for (int t = 0; t < mp / 16; t++)
+            for (int q = 0; q < kp / 4; q++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int r = 16 * t + (lane & 15), k = 4 * q + (lane >> 4);
+                    if (r < out && k < in) Wp[((size_t)t * (kp / 4) + q) * 64 + lane] = (double)W[l][(size_t)r * in + k];
+                }
+        for (int r = 0; r < out; r++) bp[r] = (double)b[l][r];
+        ok = ok && dalloc(&dW[l], Wp.size()) == hipSuccess && dalloc(&db[l], bp.size()) == hipSuccess;
+        ok = ok && hipMemcpy(dW[l], Wp.data(), sizeof(double) * Wp.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(db[l], bp.data(), sizeof(double) * bp.size(), hipMemcpyHostToDevice) == hipSuccess;
+        a.W[l] = dW[l]; a.b[l] = db[l];
+    }
+    return ok;
+}
+
 extern "C" int tum_sim_policy_attach(tum_sim *s, int n_layers, const int *widths, const float *const *W, const float *const *b)
 {
     if (!s) return fail("null argument");
@@ -2802,29 +2842,11 @@ extern "C" int tum_sim_policy_attach(tum_sim *s, int n_layers, const int *widths
     policy_release(s);
     if (!W) return 0;
     PolicyArgs &a = s->pa;
-    memset(&a, 0, sizeof(a));
-    a.n_mat = n_layers; a.n_in = widths[0]; a.n_act = widths[n_layers];
     const size_t B = c->batch;
-    bool ok = true;
-    for (int l = 0; l < n_layers && ok; l++) {
-        const int in = widths[l], out = widths[l + 1], kp = (in + 3) & ~3, mp = (out + 15) & ~15;
-        a.kp[l] = kp; a.mp[l] = mp; a.rows = std::max(a.rows, std::max(kp, mp));
-        // float -> double is exact; the A operand of product (t, q) is 64 consecutive doubles: lane holds W[16 t + (lane & 15)][4 q + (lane >> 4)]
-        std::vector<double> Wp((size_t)mp * kp, 0.0), bp(mp, 0.0);
-        for (int t = 0; t < mp / 16; t++)
-            for (int q = 0; q < kp / 4; q++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int r = 16 * t + (lane & 15), k = 4 * q + (lane >> 4);
-                    if (r < out && k < in) Wp[((size_t)t * (kp / 4) + q) * 64 + lane] = (double)W[l][(size_t)r * in + k];
-                }
-        for (int r = 0; r < out; r++) bp[r] = (double)b[l][r];
-        ok = ok && dalloc(&s->dpol_W[l], Wp.size()) == hipSuccess && dalloc(&s->dpol_b[l], bp.size()) == hipSuccess;
-        ok = ok && hipMemcpy(s->dpol_W[l], Wp.data(), sizeof(double) * Wp.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(s->dpol_b[l], bp.data(), sizeof(double) * bp.size(), hipMemcpyHostToDevice) == hipSuccess;
-        a.W[l] = s->dpol_W[l]; a.b[l] = s->dpol_b[l];
-    }
+    bool ok = net_upload(a, n_layers, widths, W, b, s->dpol_W, s->dpol_b);
     ok = ok && dalloc(&s->dpol_obs, B * a.n_in) == hipSuccess && dalloc(&s->dpol_live, B) == hipSuccess && dalloc(&s->dpol_nlive, (size_t)1) == hipSuccess;
     ok = ok && hipFuncSetAttribute((const void *)policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
+    ok = ok && hipFuncSetAttribute((const void *)policy_ac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
     ok = ok && hipDeviceSynchronize() == hipSuccess;
     if (!ok) { policy_release(s); (void)hipGetLastError(); return fail("policy_attach: allocation failed"); }
     s->pol = true;
@@ -2953,6 +2975,199 @@ extern "C" int tum_sim_env_rollout(tum_sim *s, int n_env_steps, const double *fi
     for (size_t b = 0; b < B; b++) s->env_ended[b] = (last[b * rec + 1] != 0.0 || last[b * rec + 2] != 0.0) ? 1 : 0;
     for (int e = 0; e < ran; e++)
         if (out[(size_t)e * B * rec + 5] != 0.0) return fail("env_rollout: planner segment longer than PLAN_MAXM points");
+    return lin_uniform_check(c);
+}
+
+
+// ---------------------------------------------------------------------------------------------- K13: collecting PPO training rollouts
+// The value net of the agent (mlp_extractor.value_net.<i>, value_net of a stable_baselines3 MlpPolicy) beside the attached policy:
+// widths[n_layers + 1] = inputs, hidden widths..., 1; the inputs are the policy's. W == NULL detaches. Detaching or re-attaching the
+// policy or the environment detaches it.
+extern "C" int tum_sim_policy_attach_value(tum_sim *s, int n_layers, const int *widths, const float *const *W, const float *const *b)
+{
+    if (!s) return fail("null argument");
+    tum_ocp *c = s->c;
+    if (W) {
+        if (!widths || !b) return fail("null argument");
+        if (!s->pol) return fail("policy_attach_value: no policy attached (tum_sim_policy_attach): the value net takes the policy's inputs");
+        if (n_layers < 2 || n_layers > POL_MAXMAT) return fail("policy_attach_value: 1 to 4 hidden layers (n_layers 2..5 with the value layer)");
+        for (int l = 0; l < n_layers; l++) if (!W[l] || !b[l]) return fail("null argument");
+        if (widths[0] != s->pa.n_in)
+            return fail("policy_attach_value: the value net takes " + std::to_string(widths[0]) + " inputs, the policy " + std::to_string(s->pa.n_in));
+        for (int l = 1; l < n_layers; l++)
+            if (widths[l] < 1 || widths[l] > POL_MAXWIDTH) return fail("policy_attach_value: hidden layers are 1 to 256 wide");
+        if (widths[n_layers] != 1) return fail("policy_attach_value: the last matrix of a value net has one row");
+    }
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    value_release(s);
+    if (!W) return 0;
+    const size_t B = c->batch;
+    bool ok = net_upload(s->va, n_layers, widths, W, b, s->dval_W, s->dval_b);
+    ok = ok && dalloc(&s->dval_term, B) == hipSuccess && dalloc(&s->dval_starts, B) == hipSuccess;
+    ok = ok && hipFuncSetAttribute((const void *)policy_ac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { value_release(s); (void)hipGetLastError(); return fail("policy_attach_value: allocation failed"); }
+    return 0;
+}
+
+// one launch of the actor-critic evaluation on the capsule's stream: n instances, observations [n][stride] on the device. do_pi 0: the
+// value net alone. with_value 0: the policy net alone (dvalues must be null then)
+static int ac_launch(tum_sim *s, const double *dobs, int stride, int n, int do_pi, bool with_value, unsigned long long seed, unsigned long long t,
+                     unsigned first, int *dactions, double *dvalues, double *dlogp, double *du)
+{
+    AcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pi = s->pa;
+    if (with_value) a.vf = s->va;
+    a.pi.n = a.vf.n = n; a.pi.obs = a.vf.obs = dobs; a.pi.obs_stride = a.vf.obs_stride = stride;
+    a.pi.logits = a.pi.probs = nullptr; a.pi.actions = dactions;
+    a.rows = std::max(do_pi ? s->pa.rows : 0, with_value ? s->va.rows : 0);
+    a.do_pi = do_pi; a.seed = seed; a.t = t; a.first = first;
+    a.values = dvalues; a.log_probs = dlogp; a.uniforms = du;
+    hipLaunchKernelGGL(policy_ac_kernel, dim3((n + POL_TILE - 1) / POL_TILE), dim3(64 * POL_WAVES), sizeof(double) * 2 * a.rows * POL_TILE, s->c->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the two nets and one draw on n host observations (n x widths[0]), independent of the loop's batch; instance i draws with counter word
+// first_instance + i at decision t. Any output may be NULL; values needs the value net, the others do not.
+extern "C" int tum_sim_policy_eval_ac(tum_sim *s, const double *obs, int n, unsigned long long seed, unsigned long long t, unsigned first_instance,
+                                      int *actions, double *values, double *log_probs, double *uniforms)
+{
+    if (!s || !obs) return fail("null argument");
+    if (!s->pol) return fail("policy_eval_ac: no policy attached (tum_sim_policy_attach)");
+    if (values && s->va.n_mat == 0) return fail("policy_eval_ac: values asked for and no value net attached (tum_sim_policy_attach_value)");
+    if (n < 1) return fail("policy_eval_ac: n < 1");
+    tum_ocp *c = s->c;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    const size_t ni = (size_t)n * s->pa.n_in;
+    DevTmp to, td, ta;
+    HIPCHK(to.alloc(sizeof(double) * ni)); HIPCHK(td.alloc(sizeof(double) * 3 * n)); HIPCHK(ta.alloc(sizeof(int) * n));
+    double *dv = td.as<double>(), *dl = dv + n, *du = dl + n;
+    HIPCHK(hipMemcpy(to.as<double>(), obs, sizeof(double) * ni, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    const int do_pi = (actions || log_probs || uniforms) ? 1 : 0;
+    if (!do_pi && !values) return 0;
+    if (ac_launch(s, to.as<double>(), s->pa.n_in, n, do_pi, values != nullptr, seed, t, first_instance, actions ? ta.as<int>() : nullptr,
+                  values ? dv : nullptr, log_probs ? dl : nullptr, uniforms ? du : nullptr)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (actions) HIPCHK(hipMemcpy(actions, ta.as<int>(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (values) HIPCHK(hipMemcpy(values, dv, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (log_probs) HIPCHK(hipMemcpy(log_probs, dl, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (uniforms) HIPCHK(hipMemcpy(uniforms, du, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// generalised advantage estimation alone, on host arrays: rewards, values, episode_starts E x B, last_values and last_dones B -> adv, ret E x B
+extern "C" int tum_sim_gae(tum_sim *s, int E, int B, const double *rewards, const double *values, const double *episode_starts,
+                           const double *last_values, const double *last_dones, double gamma, double lambda, double *adv, double *ret)
+{
+    if (!s || !rewards || !values || !episode_starts || !last_values || !last_dones || !adv || !ret) return fail("null argument");
+    if (E < 1 || B < 1) return fail("gae: E and B must be >= 1");
+    tum_ocp *c = s->c;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    const size_t EB = (size_t)E * B;
+    DevTmp tb;
+    HIPCHK(tb.alloc(sizeof(double) * (5 * EB + 2 * B)));
+    double *d = tb.as<double>();
+    HIPCHK(hipMemcpy(d, rewards, sizeof(double) * EB, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + EB, values, sizeof(double) * EB, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + 2 * EB, episode_starts, sizeof(double) * EB, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + 5 * EB, last_values, sizeof(double) * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + 5 * EB + B, last_dones, sizeof(double) * B, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    GaeArgs g;
+    g.E = E; g.B = B; g.gamma = gamma; g.lambda = lambda;
+    g.rewards = d; g.values = d + EB; g.episode_starts = d + 2 * EB; g.last_values = d + 5 * EB; g.last_dones = d + 5 * EB + B;
+    g.adv = d + 3 * EB; g.ret = d + 4 * EB;
+    hipLaunchKernelGGL(gae_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, g);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(adv, g.adv, sizeof(double) * EB, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ret, g.ret, sizeof(double) * EB, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// tum_sim_env_rollout with on_end 1, SAMPLED actions and the record of a stable_baselines3 RolloutBuffer: per step the actor-critic
+// evaluation (decision counter t0 + e), begin, n_mpc_steps control steps, finish, the value net on the step's own observation, the record;
+// behind the last step the value net on what the policy would see next (last_values) and gae_kernel. One wait, one download.
+//   first_obs (B x n_obs, NULL: zeros), first_episode_starts (B, NULL: ones): what the policy sees first, and whether that begins an episode
+//   out: TUM_COLLECT_FIELDS fields of E x B doubles each (TUM_COLLECT_* in tum_nmpc.h), the observations E x B x n_obs, last_values B,
+//        last_dones B, and what the policy would see next B x n_obs (the first_obs of a following call)
+extern "C" int tum_sim_env_collect(tum_sim *s, int n_env_steps, const double *first_obs, const double *first_episode_starts, const int *start_table,
+                                   unsigned long long seed, unsigned long long t0, double gamma, double gae_lambda, double *out)
+{
+    if (!s || !out) return fail("null argument");
+    if (!s->env) return fail("env_collect: no environment attached (tum_sim_env_attach)");
+    if (env_refuse(s, "env_collect")) return 1;
+    if (!s->pol) return fail("env_collect: no policy attached (tum_sim_policy_attach)");
+    if (s->va.n_mat == 0) return fail("env_collect: no value net attached (tum_sim_policy_attach_value)");
+    if (n_env_steps < 1) return fail("env_collect: n_env_steps < 1");
+    if (!start_table) return fail("env_collect: ended instances are reset and need a start table (n_env_steps x batch)");
+    tum_ocp *c = s->c; const size_t B = c->batch, E = n_env_steps, EB = E * B, rec = s->env_rec; const int no = s->pa.n_in;
+    for (size_t i = 0; i < EB; i++)
+        if (start_table[i] < 0 || start_table[i] >= s->n_track)
+            return fail("env_collect: start index of instance " + std::to_string(i % B) + " at step " + std::to_string(i / B) + " is outside the track");
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (flush_inputs(c)) return 1;          // (older setters of x0 / yref in the pinned shadow go first: the begin kernel writes behind them)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t total = EB * (COL_FIELDS + no) + 2 * B + B * no;
+    if (E > s->col_cap) {
+        (void)hipFree(s->dcol); (void)hipFree(s->dcol_tab); s->dcol = nullptr; s->dcol_tab = nullptr; s->col_cap = 0;
+        if (dalloc(&s->dcol, total) != hipSuccess || dalloc(&s->dcol_tab, EB) != hipSuccess) { (void)hipGetLastError(); return fail("env_collect: allocation failed"); }
+        s->col_cap = E;
+    }
+    // step 0: what the host knows -- the episodes that have ended, the first observation and its episode-start flags
+    std::vector<double> obs0(B * no, 0.0), st0(B, 1.0);
+    for (size_t b = 0; b < B; b++) {
+        const bool r = s->env_ended[b];
+        s->henv_in[b] = 0; s->henv_in[B + b] = r ? 1 : 0; s->henv_in[2 * B + b] = r ? start_table[b] : 0;
+        if (first_obs && !r) memcpy(&obs0[b * no], first_obs + b * no, sizeof(double) * no);
+        if (first_episode_starts) st0[b] = first_episode_starts[b] != 0.0 ? 1.0 : 0.0;
+    }
+    HIPCHK(hipMemcpy(s->denv_in, s->henv_in, sizeof(int) * 3 * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->dpol_obs, obs0.data(), sizeof(double) * B * no, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->dval_starts, st0.data(), sizeof(double) * B, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->dcol_tab, start_table, sizeof(int) * EB, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    double *buf = s->dcol;
+    CollectArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.batch = (int)B; ca.rec = (int)rec; ca.head = ENV_REC; ca.n_obs = no; ca.n_env_steps = n_env_steps; ca.gamma = gamma;
+    ca.out = s->denv_out; ca.in = s->denv_in; ca.start_table = s->dcol_tab; ca.pol_obs = s->dpol_obs; ca.term_val = s->dval_term;
+    ca.first_starts = s->dval_starts; ca.buf = buf;
+    for (int e = 0; e < n_env_steps; e++) {
+        if (ac_launch(s, s->dpol_obs, no, (int)B, 1, true, seed, t0 + (unsigned long long)e, 0u, s->denv_in,
+                      buf + COL_VALUE * EB + e * B, buf + COL_LOGP * EB + e * B, nullptr)) return 1;
+        // as in tum_sim_env_rollout: the host does not know which instances the begin kernel resets
+        invalidate(c, CH_W | CH_BOUNDS | CH_ITERATE | CH_X0 | CH_REF);
+        env_bind(s);
+        hipLaunchKernelGGL(env_begin_kernel, dim3(B), dim3(64), 0, c->stream, s->ea, 1);
+        HIPCHK(hipGetLastError());
+        if (sim_run_enqueue(s, s->env_mpc_steps)) return 1;
+        env_bind(s);
+        hipLaunchKernelGGL(env_finish_kernel, dim3(B), dim3(64), 0, c->stream, s->ea);
+        HIPCHK(hipGetLastError());
+        // the value of the step's own observation: the bootstrap of an instance that crashed, and -- to the bit -- the next step's value of one that goes on
+        if (ac_launch(s, s->denv_out + ENV_REC, (int)rec, (int)B, 0, true, 0ull, 0ull, 0u, nullptr, s->dval_term, nullptr, nullptr)) return 1;
+        ca.e = e;
+        hipLaunchKernelGGL(collect_next_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, ca);
+        HIPCHK(hipGetLastError());
+    }
+    double *last_values = buf + EB * (COL_FIELDS + no), *last_dones = last_values + B;
+    if (ac_launch(s, s->dpol_obs, no, (int)B, 0, true, 0ull, 0ull, 0u, nullptr, last_values, nullptr, nullptr)) return 1;
+    GaeArgs g;
+    g.E = n_env_steps; g.B = (int)B; g.gamma = gamma; g.lambda = gae_lambda;
+    g.rewards = buf + COL_REWARD * EB; g.values = buf + COL_VALUE * EB; g.episode_starts = buf + COL_START * EB;
+    g.last_values = last_values; g.last_dones = last_dones; g.adv = buf + COL_ADV * EB; g.ret = buf + COL_RET * EB;
+    hipLaunchKernelGGL(gae_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, g);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, buf, sizeof(double) * total, hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; b++) s->env_ended[b] = out[EB * (COL_FIELDS + no) + B + b] != 0.0 ? 1 : 0;
+    for (int e = 0; e < n_env_steps; e++)
+        if (out[COL_ERR * EB + (size_t)e * B] != 0.0) return fail("env_collect: planner segment longer than PLAN_MAXM points");
     return lin_uniform_check(c);
 }
 

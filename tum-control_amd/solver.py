@@ -77,7 +77,8 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_planner_emulate", "tum_sim_create", "tum_sim_free", "tum_sim_set_state", "tum_sim_plan", "tum_sim_advance",
              "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
              "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step",
-             "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout"]
+             "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout",
+             "tum_sim_policy_attach_value", "tum_sim_policy_eval_ac", "tum_sim_gae", "tum_sim_env_collect"]
 
 
 def load_library(path=None):
@@ -163,6 +164,12 @@ def load_library(path=None):
         L.tum_sim_policy_attach.argtypes = [vp, ci, ip, ctypes.POINTER(vp), ctypes.POINTER(vp)]
         L.tum_sim_policy_eval.argtypes = [vp, dp, ci, dp, dp, ip]
         L.tum_sim_env_rollout.argtypes = [vp, ci, dp, ci, ip, ci, dp, ip, ip, ip]
+    if hasattr(L, "tum_sim_env_collect"):
+        u64 = ctypes.c_ulonglong
+        L.tum_sim_policy_attach_value.argtypes = [vp, ci, ip, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+        L.tum_sim_policy_eval_ac.argtypes = [vp, dp, ci, u64, u64, ctypes.c_uint, ip, dp, dp, dp]
+        L.tum_sim_gae.argtypes = [vp, ci, ci, dp, dp, dp, dp, dp, cd, cd, dp, dp]
+        L.tum_sim_env_collect.argtypes = [vp, ci, dp, dp, ip, u64, u64, cd, cd, dp]
     _libs[p] = L
     if p == LIB_PATH:
         _lib = L
@@ -901,12 +908,12 @@ class DeviceClosedLoop:
                                              int(bool(full_lap)), _dp(sig), _dp(lo_hi), _dp(ob[0]), _dp(ob[1]), iv.ctypes.data_as(ip),
                                              ir.ctypes.data_as(ip), n, self._OBS_STATES[obs_states]), "sim_env_attach")
         self.env_n_obs = 2 + 2 * n
-        self.policy_widths = None          # (attaching an environment detaches the policy of the one before)
+        self.policy_widths = self.value_widths = None          # (attaching an environment detaches the policy of the one before)
 
     def detach_env(self):
         self._chk(self._L.tum_sim_env_attach(self._s, None, 0, 0, 0.0, 0, 0, None, None, None, None, None, None, 0, 0), "sim_env_attach")
         self.env_n_obs = 0
-        self.policy_widths = None
+        self.policy_widths = self.value_widths = None
 
     def _ints(self, a):
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(a), (self.B,)))
@@ -944,29 +951,129 @@ class DeviceClosedLoop:
         return out.astype(np.int64)
 
     # ---- the agent of the environment (enable_WMPC of the controller classes, RL_WMPC/evaluation.py:65-105)
-    def attach_policy(self, policy):
-        """The policy net that picks the environment's actions on the device: `policy` has .weights / .biases, lists of float32 arrays
-        (out, in) / (out,) -- closed_loop.WeightPolicy. 1 to 4 hidden layers up to 256 wide, tanh, up to 128 inputs and 64 actions; its
-        input width is the environment's observation, its action count the rows of the environment's table."""
-        Ws = [np.ascontiguousarray(w) for w in policy.weights]
-        bs = [np.ascontiguousarray(b) for b in policy.biases]
+    @staticmethod
+    def _net(weights, biases, who):
+        """(widths, pointer arrays, the arrays they point into) of a float32 net for the attach calls"""
+        Ws = [np.ascontiguousarray(w) for w in weights]
+        bs = [np.ascontiguousarray(b) for b in biases]
         if len(Ws) != len(bs) or len(Ws) < 1:
-            raise Exception("attach_policy: one bias per weight matrix")
+            raise Exception(who + ": one bias per weight matrix")
         for w, b in zip(Ws, bs):
             if w.dtype != np.float32 or b.dtype != np.float32 or w.ndim != 2 or b.shape != (w.shape[0],):
-                raise Exception("attach_policy: weights are float32 (out, in) matrices, biases float32 (out,) vectors")
+                raise Exception(who + ": weights are float32 (out, in) matrices, biases float32 (out,) vectors")
         for w0, w1 in zip(Ws, Ws[1:]):
             if w1.shape[1] != w0.shape[0]:
-                raise Exception("attach_policy: the layers do not chain")
+                raise Exception(who + ": the layers do not chain")
         widths = np.array([Ws[0].shape[1]] + [w.shape[0] for w in Ws], dtype=np.int32)
         pw = (ctypes.c_void_p * len(Ws))(*[w.ctypes.data for w in Ws])
         pb = (ctypes.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
-        self._chk(self._L.tum_sim_policy_attach(self._s, len(Ws), widths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), pw, pb), "sim_policy_attach")
+        return widths, pw, pb, (Ws, bs)
+
+    def attach_policy(self, policy):
+        """The policy net that picks the environment's actions on the device: `policy` has .weights / .biases, lists of float32 arrays
+        (out, in) / (out,) -- closed_loop.WeightPolicy. 1 to 4 hidden layers up to 256 wide, tanh, up to 128 inputs and 64 actions; its
+        input width is the environment's observation, its action count the rows of the environment's table. A policy that carries a
+        value net (.value_weights / .value_biases) brings it along (attach_value); one that does not leaves none attached."""
+        widths, pw, pb, _keep = self._net(policy.weights, policy.biases, "attach_policy")
+        self._chk(self._L.tum_sim_policy_attach(self._s, len(pw), widths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), pw, pb), "sim_policy_attach")
         self.policy_widths = tuple(int(w) for w in widths)
+        self.value_widths = None          # (attaching a policy detaches the value net of the one before)
+        if getattr(policy, "value_weights", None) is not None:
+            self.attach_value(policy.value_weights, policy.value_biases)
 
     def detach_policy(self):
         self._chk(self._L.tum_sim_policy_attach(self._s, 0, None, None, None), "sim_policy_attach")
-        self.policy_widths = None
+        self.policy_widths = self.value_widths = None
+
+    # ---- collecting PPO training rollouts (stable_baselines3 collect_rollouts + compute_returns_and_advantage)
+    COLLECT_FIELDS = ("actions", "values", "log_probs", "rewards", "rewards_raw", "episode_starts", "advantages", "returns",
+                      "terminated", "truncated", "step_length", "qp_failures", "planner_error")          # TUM_COLLECT_* of tum_nmpc.h
+
+    def attach_value(self, weights, biases):
+        """The value net beside the attached policy: float32 (out, in) matrices / (out,) vectors, its own 1 to 4 hidden layers up to
+        256 wide, the policy's inputs, one output."""
+        widths, pw, pb, _keep = self._net(weights, biases, "attach_value")
+        self._chk(self._L.tum_sim_policy_attach_value(self._s, len(pw), widths.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), pw, pb),
+                  "sim_policy_attach_value")
+        self.value_widths = tuple(int(w) for w in widths)
+
+    def detach_value(self):
+        self._chk(self._L.tum_sim_policy_attach_value(self._s, 0, None, None, None), "sim_policy_attach_value")
+        self.value_widths = None
+
+    def policy_eval_ac(self, obs, seed, t, first_instance=0, values=None):
+        """the attached nets and ONE draw per row on (n, n_obs) observations, independent of the loop's batch: dict of actions (n,)
+        sampled with the uniform of (seed, first_instance + i, t), log_probs, uniforms and -- with a value net attached (values=None) or
+        asked for (values=True: an error without one) -- values"""
+        w = getattr(self, "policy_widths", None)
+        if not w:
+            raise Exception("policy_eval_ac: no policy attached (attach_policy)")
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != w[0] or obs.shape[0] < 1:
+            raise Exception(f"policy_eval_ac: observations are (n, {w[0]}), n >= 1")
+        n = obs.shape[0]
+        want_v = bool(getattr(self, "value_widths", None)) if values is None else bool(values)
+        act, val, lp, u = np.empty(n, dtype=np.int32), np.empty(n), np.empty(n), np.empty(n)
+        self._chk(self._L.tum_sim_policy_eval_ac(self._s, _dp(obs), n, int(seed) & (2 ** 64 - 1), int(t) & (2 ** 64 - 1), int(first_instance) & 0xffffffff,
+                                                 act.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(val) if want_v else None, _dp(lp), _dp(u)),
+                  "sim_policy_eval_ac")
+        out = dict(actions=act.astype(np.int64), log_probs=lp, uniforms=u)
+        if want_v:
+            out["values"] = val
+        return out
+
+    def gae(self, rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda):
+        """gae_kernel alone on (E, B) host arrays: (advantages, returns)"""
+        r = np.ascontiguousarray(rewards, dtype=np.float64)
+        if r.ndim != 2 or r.size < 1:
+            raise Exception("gae: rewards, values and episode_starts are (E, B)")
+        E, B = r.shape
+        v, es = (np.ascontiguousarray(a, dtype=np.float64) for a in (values, episode_starts))
+        lv, ld = (np.ascontiguousarray(a, dtype=np.float64) for a in (last_values, last_dones))
+        if v.shape != (E, B) or es.shape != (E, B) or lv.shape != (B,) or ld.shape != (B,):
+            raise Exception("gae: rewards, values and episode_starts are (E, B), last_values and last_dones (B,)")
+        adv, ret = np.empty((E, B)), np.empty((E, B))
+        self._chk(self._L.tum_sim_gae(self._s, E, B, _dp(r), _dp(v), _dp(es), _dp(lv), _dp(ld), float(gamma), float(gae_lambda), _dp(adv), _dp(ret)), "sim_gae")
+        return adv, ret
+
+    def env_collect(self, n_env_steps, start_table, seed, t0, gamma, gae_lambda, first_obs=None, first_episode_starts=None):
+        """n_env_steps environment steps with SAMPLED actions and everything a RolloutBuffer holds after collect_rollouts and
+        compute_returns_and_advantage, one wait at the end (tum_sim_env_collect). Returns a dict of (E, B) arrays named as
+        COLLECT_FIELDS (without planner_error), observations (E, B, n_obs), last_values and last_dones (B,), and next_observation
+        (B, n_obs): what the policy would see next."""
+        ip = ctypes.POINTER(ctypes.c_int)
+        E, B, no = int(n_env_steps), self.B, getattr(self, "env_n_obs", 0)
+        if E < 1:
+            raise Exception("env_collect: n_env_steps < 1")
+        fo = fs = None
+        if first_obs is not None:
+            fo = np.ascontiguousarray(first_obs, dtype=np.float64)
+            if fo.shape != (B, no):
+                raise Exception(f"env_collect: first_obs is ({B}, {no})")
+        if first_episode_starts is not None:
+            fs = np.ascontiguousarray(first_episode_starts, dtype=np.float64)
+            if fs.shape != (B,):
+                raise Exception(f"env_collect: first_episode_starts is ({B},)")
+        tab = np.asarray(start_table)
+        if tab.shape != (E, B) or not np.issubdtype(tab.dtype, np.integer):
+            raise Exception(f"env_collect: start_table is an integer array ({E}, {B})")
+        tab = np.ascontiguousarray(tab, dtype=np.int32)
+        F = len(self.COLLECT_FIELDS)
+        out = np.zeros(E * B * (F + no) + 2 * B + B * no)
+        self._chk(self._L.tum_sim_env_collect(self._s, E, None if fo is None else _dp(fo), None if fs is None else _dp(fs), tab.ctypes.data_as(ip),
+                                              int(seed) & (2 ** 64 - 1), int(t0) & (2 ** 64 - 1), float(gamma), float(gae_lambda), _dp(out)),
+                  "sim_env_collect")
+        f = out[:F * E * B].reshape(F, E, B)
+        r = {k: f[i].copy() for i, k in enumerate(self.COLLECT_FIELDS) if k != "planner_error"}
+        r["actions"] = r["actions"].astype(np.int64)
+        for k in ("step_length", "qp_failures"):
+            r[k] = r[k].astype(np.int64)
+        for k in ("terminated", "truncated"):
+            r[k] = r[k] != 0
+        r["observations"] = out[F * E * B:(F + no) * E * B].reshape(E, B, no).copy()
+        tail = out[(F + no) * E * B:]
+        r["last_values"], r["last_dones"], r["next_observation"] = tail[:B].copy(), tail[B:2 * B].copy(), tail[2 * B:].reshape(B, no).copy()
+        return r
 
     def policy_eval(self, obs):
         """the attached policy alone on (n, n_obs) observations, independent of the loop's batch: dict of logits (n, A), probabilities
