@@ -541,6 +541,46 @@ enum { TUM_COLLECT_ACTION, TUM_COLLECT_VALUE, TUM_COLLECT_LOG_PROB, TUM_COLLECT_
 int tum_sim_env_collect(tum_sim *s, int n_env_steps, const double *first_obs, const double *first_episode_starts, const int *start_table,
                         unsigned long long seed, unsigned long long t0, double gamma, double gae_lambda, double *out);
 
+/* --- K14: the PPO update on the device (stable_baselines3 PPO.train as rl_training.py:133-155 configures it: normalize_advantage,
+ * clip_range_vf None, target_kl None, separate tanh nets). One minibatch of n rows (obs, a, old_log_prob, adv, ret):
+ *   A = (adv - mean adv) / (std adv + 1e-8), std with the n - 1 divisor (A = adv for n == 1 or normalize_advantage == 0)
+ *   z the policy net's logits on float32(obs); logp = (z - max z) - log sum exp(z - max z) (index order); p = exp(logp)
+ *   H = -sum p logp; lp = logp[a]; r = exp(lp - old_log_prob)
+ *   policy_loss = -mean min(A r, A clip(r, 1 - c, 1 + c)) (the unclipped term carries the gradient where A r <= A clip(r))
+ *   value_loss = mean (ret - V(obs))^2; entropy_loss = -mean H; loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ *   approx_kl = mean((r - 1) - log r); clip_fraction = mean(|r - 1| > c); grad_norm = sqrt(sum g^2) over every weight and bias
+ *   g <- min(1, max_grad_norm / (grad_norm + 1e-6)) g
+ *   Adam (beta 0.9 / 0.999, eps 1e-5, no weight decay), t the step counter:  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2;
+ *   theta <- theta - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ * Precision: the parameters are float32 values (what policy_kernel / policy_ac_kernel act with); everything else -- forward, backward,
+ * reductions, moments -- is FP64; the new parameter is the FP64 result of the Adam line rounded ONCE to float32 (nearest even) and is
+ * written in place into the packed nets: the nets that act are the updated nets, without an upload. No floating-point atomics; the
+ * order of every sum depends on the minibatch size and the widths alone: the same call from the same state gives the same bits.
+ * tum_sim_ppo_attach needs an attached policy WITH a value net; it zeroes the moments and the step counter. Detaching or re-attaching
+ * the policy, the value net or the environment detaches the trainer; tum_sim_ppo_detach does so alone. */
+enum { TUM_PPO_LOSS, TUM_PPO_POLICY_LOSS, TUM_PPO_VALUE_LOSS, TUM_PPO_ENTROPY_LOSS, TUM_PPO_APPROX_KL, TUM_PPO_CLIP_FRACTION,
+       TUM_PPO_GRAD_NORM, TUM_PPO_N, TUM_PPO_STATS };
+int tum_sim_ppo_attach(tum_sim *s, double clip_range, double ent_coef, double vf_coef, double max_grad_norm, int normalize_advantage);
+int tum_sim_ppo_detach(tum_sim *s);
+/* One minibatch of n host rows (obs n x widths[0]; actions n ints inside the policy's range). apply 0: loss, gradients and grad_norm
+ * only -- parameters, moments and the step counter stay untouched. stats_out: TUM_PPO_STATS doubles (TUM_PPO_N: the rows).
+ * grads_out (NULL or n_params doubles): the UNCLIPPED gradients over the flat parameter vector in torch's layout -- per net W_0 (out x
+ * in, row-major), b_0, W_1, b_1, ...; the policy net, then the value net. rows_out (NULL or n x 2): the log-probability of each row's
+ * action and its value as the update computed them: the bits of tum_sim_policy_eval_ac on the same rows. */
+int tum_sim_ppo_step(tum_sim *s, int n, const double *obs, const int *actions, const double *old_log_probs, const double *advantages,
+                     const double *returns, double lr, int apply, double *stats_out, double *grads_out, double *rows_out);
+/* One update: n_epochs passes over the N buffer rows; pass e visits them in the order perm[e][0 .. N) (n_epochs x N ints in [0, N),
+ * the caller's), cut into minibatches [k batch_size, min((k + 1) batch_size, N)) -- the last may be short. Every minibatch is the
+ * chain of tum_sim_ppo_step with apply 1; all of them are enqueued, one wait, one download. stats_out: n_epochs x ceil(N /
+ * min(batch_size, N)) x TUM_PPO_STATS. obs, actions, old_log_probs, advantages, returns all NULL: the rows tum_sim_env_collect last left
+ * on the device (row e B + b); refused when there are none or their number is not N. */
+int tum_sim_ppo_update(tum_sim *s, int N, const double *obs, const int *actions, const double *old_log_probs, const double *advantages,
+                       const double *returns, const int *perm, int n_epochs, int batch_size, double lr, double *stats_out);
+/* The float32 parameters the device acts with, per matrix as the attach functions take them (policy W / b, value net VW / Vb). */
+int tum_sim_ppo_params(tum_sim *s, float *const *W, float *const *b, float *const *VW, float *const *Vb);
+/* Adam's state: the moments over the flat parameter vector (n_params doubles each), the step counter, n_params. Any may be NULL. */
+int tum_sim_ppo_state(tum_sim *s, double *m, double *v, long long *t, int *n_params);
+
 /* development aid: one solve with in-kernel phase timers; out = batch x 12 shader-cycle counters
  * [linearise, condense, ipm-residuals, M assembly, Cholesky, rhs, tri-solves, row updates, (iteration tail), expand+cost] */
 int tum_ocp_profile_phases(tum_ocp *c, long long *out);

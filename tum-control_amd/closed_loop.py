@@ -689,7 +689,8 @@ class WeightScheduleEnv:
         step (step() and rollout() included), so consecutive calls continue one stream, and one episode bookkeeping: episode_starts of
         the first row is what the last reset() / step() / rollout() / collect() left. The policy is attached anew at every call:
         changed weights between two calls are what a training loop has. Needs auto_reset=True; the start waypoints are drawn before
-        the call as rollout() draws them.
+        the call as rollout() draws them. A PPOTrainer in place of the policy: the nets resident on the device -- the trainer's, as
+        its updates left them -- act, and nothing is attached.
         Returns a dict of (E, B[, n_obs]) arrays: observations (what the policy saw), actions, log_probs, values, rewards (with
         gamma V(terminal observation) added where truncated and not terminated: the CRASH, environment.py:152-165), rewards_raw,
         episode_starts, advantages, returns, terminated, truncated, step_length, qp_failures; and last_values, last_dones (B,).
@@ -697,16 +698,21 @@ class WeightScheduleEnv:
         E, B = int(n_steps), self.n_envs
         if not self.auto_reset:
             raise ValueError("WeightScheduleEnv.collect: needs auto_reset=True (an ended instance is reset, as in a VecEnv)")
-        if getattr(policy, "value_weights", None) is None:
+        if isinstance(policy, PPOTrainer):
+            if policy.dev is not self.dev:
+                raise ValueError("WeightScheduleEnv.collect: the trainer belongs to another loop")
+        elif getattr(policy, "value_weights", None) is None:
             raise ValueError("WeightScheduleEnv.collect: the policy carries no value net")
         if E < 1:
             raise ValueError("WeightScheduleEnv.collect: n_steps < 1")
-        self.dev.attach_policy(policy)
+        if not isinstance(policy, PPOTrainer):
+            self.dev.attach_policy(policy)
         self._policy = policy
         table = self._draw(E * B).reshape(E, B)
         r = self.dev.env_collect(E, table, self._seed if seed is None else int(seed), self._t, gamma, gae_lambda,
                                  first_obs=self._next_obs, first_episode_starts=self._episode_starts)
         self._t += E
+        self._collected = E * B
         self._ended = r["terminated"][-1] | r["truncated"][-1]
         self._episode_starts = self._ended.astype(float)
         self._next_obs = r.pop("next_observation")
@@ -905,6 +911,178 @@ class WeightPolicy:
     def predict(self, obs):
         """model.predict(obs, deterministic=True): the first index of the largest logit"""
         return np.argmax(self.logits(obs), axis=-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The PPO update (stable_baselines3 PPO.train as rl_training.py:133-155 configures it). ppo_loss_and_grads and adam_step are the HOST
+# statements -- float64 numpy, the role WeightPolicy._forward has for the nets -- of what ppo_tile_kernel / ppo_wgrad_kernel /
+# ppo_adam_kernel compute on the device.
+
+def learning_rate_schedule(initial, final, k):
+    """helpers.py:88-97: remaining (1 at the start of training, 0 at its end) -> initial (final / initial)^((1 - remaining) k)"""
+    initial, final, k = float(initial), float(final), float(k)
+
+    def func(remaining):
+        return initial * (final / initial) ** ((1.0 - float(remaining)) * k)
+    return func
+
+
+def minibatch_slices(N, batch_size):
+    """[k batch_size, min((k + 1) batch_size, N)) for k = 0, 1, ...: the last minibatch may be short, as in stable_baselines3"""
+    N, bs = int(N), int(batch_size)
+    if N < 1 or bs < 1:
+        raise ValueError("minibatch_slices: N and batch_size must be >= 1")
+    bs = min(bs, N)
+    return [slice(k, min(k + bs, N)) for k in range(0, N, bs)]
+
+
+def _tanh_net(h, weights, biases):
+    """the layers of _forward with the input of every matrix kept: (output (n, out), [h_0, h_1, ...])"""
+    hs = []
+    for i, (w, b) in enumerate(zip(weights, biases)):
+        hs.append(h)
+        h = h @ w.astype(np.float64).T + b.astype(np.float64)
+        if i + 1 < len(weights):
+            h = np.tanh(h)
+    return h, hs
+
+
+def _tanh_net_grads(delta, weights, hs):
+    """delta = dL/d(output) (n, out) back through the layers: ([dW_l], [db_l])"""
+    gW, gb = [None] * len(weights), [None] * len(weights)
+    for l in range(len(weights) - 1, -1, -1):
+        gW[l], gb[l] = delta.T @ hs[l], delta.sum(axis=0)
+        if l:
+            delta = (delta @ weights[l].astype(np.float64)) * (1.0 - hs[l] * hs[l])
+    return gW, gb
+
+
+def ppo_loss_and_grads(policy, obs, actions, old_log_probs, advantages, returns, clip_range=0.2, ent_coef=0.006, vf_coef=0.5,
+                       normalize_advantage=True):
+    """Loss, diagnostics and the gradient of every weight and bias of one minibatch, float64: the host statement of the device's
+    ppo_step(apply=False). `policy`: a WeightPolicy with a value net. Returns a dict: loss, policy_loss, value_loss, entropy_loss,
+    approx_kl, clip_fraction, grad_norm (before clipping), ratio (n,), log_probs (n,), values (n,) and grads = (weights, biases,
+    value_weights, value_biases) lists of float64 arrays shaped as the parameters."""
+    obs = np.atleast_2d(np.asarray(obs, dtype=np.float64))
+    n = len(obs)
+    a = np.asarray(actions, dtype=np.int64).reshape(n)
+    old, adv, ret = (np.asarray(x, dtype=np.float64).reshape(n) for x in (old_log_probs, advantages, returns))
+    if policy.value_weights is None:
+        raise ValueError("ppo_loss_and_grads: the policy carries no value net")
+    A = (adv - adv.mean()) / (adv.std(ddof=1) + 1e-8) if normalize_advantage and n > 1 else adv
+    h0 = obs.astype(np.float32).astype(np.float64)
+    z, hs = _tanh_net(h0, policy.weights, policy.biases)
+    V, vhs = _tanh_net(h0, policy.value_weights, policy.value_biases)
+    V = V[:, 0]
+    d = z - z.max(axis=-1, keepdims=True)
+    logp = d - np.log(np.cumsum(np.exp(d), axis=-1)[:, -1:])          # (the sum in index order: WeightPolicy.log_prob)
+    p = np.exp(logp)
+    H = -(p * logp).sum(axis=-1)
+    rows = np.arange(n)
+    lp = logp[rows, a]
+    lr = lp - old
+    r = np.exp(lr)
+    s1, s2 = A * r, A * np.clip(r, 1.0 - clip_range, 1.0 + clip_range)
+    policy_loss, value_loss, entropy_loss = -np.minimum(s1, s2).mean(), ((ret - V) ** 2).mean(), -H.mean()
+    # backwards: the unclipped term carries the gradient where it is the smaller one (or both are equal)
+    glp = np.where(s1 <= s2, -s1, 0.0)
+    onehot = np.zeros_like(z)
+    onehot[rows, a] = 1.0
+    dz = (glp[:, None] * (onehot - p) + ent_coef * (p * (logp + H[:, None]))) / n
+    dV = (vf_coef * (2.0 * (V - ret)) / n)[:, None]
+    gW, gb = _tanh_net_grads(dz, policy.weights, hs)
+    gVW, gVb = _tanh_net_grads(dV, policy.value_weights, vhs)
+    norm = np.sqrt(sum(float((g * g).sum()) for g in gW + gb + gVW + gVb))
+    return dict(loss=policy_loss + ent_coef * entropy_loss + vf_coef * value_loss, policy_loss=policy_loss, value_loss=value_loss,
+                entropy_loss=entropy_loss, approx_kl=((r - 1.0) - lr).mean(), clip_fraction=(np.abs(r - 1.0) > clip_range).mean(),
+                grad_norm=norm, ratio=r, log_probs=lp, values=V, grads=(gW, gb, gVW, gVb))
+
+
+def adam_step(params, grads, m, v, t, lr, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-5):
+    """Gradient clipping and one Adam step, float64, on lists of arrays: the host statement of ppo_adam_kernel BEFORE the rounding to
+    float32. total = sqrt(sum g^2) over all tensors, g <- min(1, max_grad_norm / (total + 1e-6)) g; then, with t the number of this
+    step (1 for the first), m <- b1 m + (1 - b1) g, v <- b2 v + (1 - b2) g^2, theta <- theta - (lr / (1 - b1^t)) m / (sqrt(v) /
+    sqrt(1 - b2^t) + eps). Returns (new params, new m, new v, total), params and moments float64; the caller rounds."""
+    b1, b2 = betas
+    g64 = [np.asarray(g, dtype=np.float64) for g in grads]
+    total = np.sqrt(sum(float((g * g).sum()) for g in g64))
+    coef = min(1.0, max_grad_norm / (total + 1e-6))
+    step, bc2 = lr / (1.0 - b1 ** t), np.sqrt(1.0 - b2 ** t)
+    P, M, V = [], [], []
+    for th, g, m0, v0 in zip(params, g64, m, v):
+        g = coef * g
+        m1 = b1 * np.asarray(m0, dtype=np.float64) + (1.0 - b1) * g
+        v1 = b2 * np.asarray(v0, dtype=np.float64) + ((1.0 - b2) * g) * g
+        P.append(np.asarray(th, dtype=np.float64) - (step * m1) / (np.sqrt(v1) / bc2 + eps))
+        M.append(m1); V.append(v1)
+    return P, M, V, total
+
+
+class PPOTrainer:
+    """The PPO update of `policy` (a WeightPolicy WITH a value net) on the device of `env_or_loop` (a WeightScheduleEnv, a
+    ClosedLoopBatch with on_device=True or a DeviceClosedLoop): attaches the policy and the trainer. From then on the nets live on the
+    device: step() and update() change them in place, WeightScheduleEnv.collect(trainer, ...) acts with them, policy() downloads them.
+    Parameters are float32, everything else FP64, the new parameter the FP64 Adam result rounded once."""
+
+    def __init__(self, env_or_loop, policy, clip_range=0.2, ent_coef=0.006, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True):
+        if getattr(policy, "value_weights", None) is None:
+            raise ValueError("PPOTrainer: the policy carries no value net")
+        self.env = env_or_loop if isinstance(env_or_loop, WeightScheduleEnv) else None
+        self.dev = getattr(env_or_loop, "dev", env_or_loop)
+        self.settings = dict(clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
+                             normalize_advantage=normalize_advantage)
+        self.dev.attach_policy(policy)
+        self.dev.ppo_attach(**self.settings)
+        if self.env is not None:
+            self.env._policy = self
+
+    def step(self, obs, actions, old_log_probs, advantages, returns, lr, apply=True, want_grads=False, want_rows=False):
+        """one minibatch from host arrays: the dict of diagnostics (DeviceClosedLoop.ppo_step)"""
+        return self.dev.ppo_step(obs, actions, old_log_probs, advantages, returns, lr, apply=apply, want_grads=want_grads, want_rows=want_rows)
+
+    def update(self, buffer=None, perm=None, n_epochs=5, batch_size=4096, lr=3e-4, seed=0):
+        """One update: n_epochs passes over the buffer in minibatches of batch_size, one wait. buffer: what collect() returned (its
+        (E, B) arrays are flattened in C order), or None: the rows the last collect() left on the device. perm (n_epochs, N), or None:
+        numpy.random.RandomState(seed).permutation(N) per epoch, drawn in epoch order from one generator."""
+        if buffer is None:
+            if self.env is None:
+                raise ValueError("PPOTrainer.update: without a buffer the trainer needs a WeightScheduleEnv whose collect() left one on the device")
+            N = getattr(self.env, "_collected", 0)
+            if N < 1:
+                raise ValueError("PPOTrainer.update: no buffer given and nothing collected yet")
+            rows = None
+        else:
+            acts = np.asarray(buffer["actions"])
+            N = acts.size
+            rows = (np.asarray(buffer["observations"], dtype=np.float64).reshape(N, -1), acts.reshape(N),
+                    *(np.asarray(buffer[k], dtype=np.float64).reshape(N) for k in ("log_probs", "advantages", "returns")))
+        if perm is None:
+            rng = np.random.RandomState(seed)
+            perm = np.stack([rng.permutation(N) for _ in range(int(n_epochs))])
+        return self.dev.ppo_update(N, perm, batch_size, lr, buffer=rows)
+
+    def policy(self):
+        """the nets the device acts with, as a WeightPolicy"""
+        return WeightPolicy(*self.dev.ppo_params())
+
+    def state(self):
+        """Adam's moments and step counter (DeviceClosedLoop.ppo_state)"""
+        return self.dev.ppo_state()
+
+
+def learn(env, trainer, n_updates, n_steps, batch_size, n_epochs, gamma, gae_lambda, lr_schedule, seed=0):
+    """The loop of stable_baselines3's model.learn on the device: n_updates x (collect n_steps environment steps with the trainer's
+    resident nets, one update on the buffer collect left on the device). lr_schedule: a number, or a function of the remaining
+    progress (1 -> 0, learning_rate_schedule), evaluated before each update as stable_baselines3 does. The permutations of update u
+    come from RandomState(seed + u). Returns the list of per-update diagnostics (PPOTrainer.update)."""
+    out = []
+    for u in range(int(n_updates)):
+        env.collect(trainer, n_steps, gamma, gae_lambda)
+        # (_update_current_progress_remaining: 1 - num_timesteps / total_timesteps, after the collection)
+        remaining = 1.0 - (u + 1) / float(n_updates)
+        lr = lr_schedule(remaining) if callable(lr_schedule) else float(lr_schedule)
+        out.append(trainer.update(None, None, n_epochs, batch_size, lr, seed=seed + u))
+    return out
 
 
 def run_policy(track_name, policy, table, starts, max_steps=400, n_mpc_steps=20, check_every=1, n_obs_stack=1, **env_kw):

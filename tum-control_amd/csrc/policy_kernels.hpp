@@ -81,7 +81,10 @@ __device__ __forceinline__ void policy_load_obs(const PolicyArgs &a, double *dst
 
 // The layers of one net on the tile whose input is in buf[0]: the result of matrix l is in buf[(l + 1) & 1], a barrier behind every
 // layer. policy_kernel and policy_ac_kernel both run this loop and nothing else on the matrices: one order of sums.
-__device__ __forceinline__ void policy_layers(const PolicyArgs &a, double *const *buf, int lane, int wave)
+// KEEP (ppo_tile_kernel of ppo_kernels.hpp, the same loop and the same sums): the hidden activations also go to memory for the
+// backward pass, instance i0 + column of the tile at keep[l + 1] + (i0 + column) * mp[l].
+template <bool KEEP = false>
+__device__ __forceinline__ void policy_layers(const PolicyArgs &a, double *const *buf, int lane, int wave, double *const *keep = nullptr, int i0 = 0)
 {
     const int col = lane & 15, quad = lane >> 4;
     for (int l = 0; l < a.n_mat; l++) {
@@ -104,7 +107,11 @@ __device__ __forceinline__ void policy_layers(const PolicyArgs &a, double *const
             }
             for (; q < nq; q++) acc = mfma(Wt[(size_t)q * 64], h[q * 4 * POL_TILE], acc);
 #pragma unroll
-            for (int j = 0; j < 4; j++) dst[(16 * t + quad + 4 * j) * POL_TILE + col] = hidden ? policy_tanh(acc[j]) : acc[j];
+            for (int j = 0; j < 4; j++) {
+                const double v = hidden ? policy_tanh(acc[j]) : acc[j];
+                dst[(16 * t + quad + 4 * j) * POL_TILE + col] = v;
+                if (KEEP && hidden) keep[l + 1][(size_t)(i0 + col) * a.mp[l] + 16 * t + quad + 4 * j] = v;
+            }
         }
         __syncthreads();
     }

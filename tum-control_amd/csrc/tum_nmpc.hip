@@ -23,6 +23,7 @@
 #include "env_kernels.hpp"
 #include "policy_kernels.hpp"
 #include "collect_kernels.hpp"
+#include "ppo_kernels.hpp"
 #include "sqp_kernels.hpp"
 #include "rti_kernels.hpp"
 
@@ -2226,13 +2227,35 @@ struct tum_sim {
     PolicyArgs va;
     double *dval_W[POL_MAXMAT], *dval_b[POL_MAXMAT], *dval_term, *dval_starts;
     double *dcol; int *dcol_tab; size_t col_cap;
+    // the trainer (tum_sim_ppo_attach): the true widths of the two nets, the rows the last collection left in dcol, the settings and
+    // Adam's step counter, the training views of the nets, the float32 master / moments / gradient over the flat parameter vector
+    // (policy net then value net), and workspaces grown on demand: minibatch rows, an uploaded buffer, index lists, diagnostics
+    int pol_widths[POL_MAXMAT + 1], val_widths[POL_MAXMAT + 1];
+    size_t col_rows;
+    bool ppo; double ppo_clip, ppo_ent, ppo_vf, ppo_max_norm; int ppo_normalize, ppo_P, ppo_parts; long long ppo_t;
+    PpoNet tp, tv;
+    float *dppo_theta; double *dppo_m, *dppo_v, *dppo_G, *dppo_part, *dppo_advstat, *dppo_rowrec, *dppo_stats, *dppo_data; int *dppo_idx;
+    size_t ppo_rows_cap, ppo_stats_cap, ppo_data_cap, ppo_idx_cap;
 };
+static void ppo_release(tum_sim *s)
+{
+    for (PpoNet *t : {&s->tp, &s->tv})
+        for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(t->WT[l]); (void)hipFree(t->h[l]); (void)hipFree(t->d[l]); }
+    memset(&s->tp, 0, sizeof(s->tp)); memset(&s->tv, 0, sizeof(s->tv));
+    (void)hipFree(s->dppo_theta); (void)hipFree(s->dppo_m); (void)hipFree(s->dppo_v); (void)hipFree(s->dppo_G); (void)hipFree(s->dppo_part);
+    (void)hipFree(s->dppo_advstat); (void)hipFree(s->dppo_rowrec); (void)hipFree(s->dppo_stats); (void)hipFree(s->dppo_data); (void)hipFree(s->dppo_idx);
+    s->dppo_theta = nullptr; s->dppo_idx = nullptr;
+    s->dppo_m = s->dppo_v = s->dppo_G = s->dppo_part = s->dppo_advstat = s->dppo_rowrec = s->dppo_stats = s->dppo_data = nullptr;
+    s->ppo_rows_cap = s->ppo_stats_cap = s->ppo_data_cap = s->ppo_idx_cap = 0;
+    s->ppo = false; s->ppo_t = 0;
+}
 static void value_release(tum_sim *s)
 {
+    ppo_release(s);            // (the trainer updates both nets: it goes with either)
     for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(s->dval_W[l]); (void)hipFree(s->dval_b[l]); s->dval_W[l] = s->dval_b[l] = nullptr; }
     (void)hipFree(s->dval_term); (void)hipFree(s->dval_starts); (void)hipFree(s->dcol); (void)hipFree(s->dcol_tab);
     s->dval_term = s->dval_starts = s->dcol = nullptr; s->dcol_tab = nullptr;
-    s->col_cap = 0; s->va.n_mat = 0;
+    s->col_cap = 0; s->col_rows = 0; s->va.n_mat = 0;
 }
 static void policy_release(tum_sim *s)
 {
@@ -2844,6 +2867,7 @@ extern "C" int tum_sim_policy_attach(tum_sim *s, int n_layers, const int *widths
     PolicyArgs &a = s->pa;
     const size_t B = c->batch;
     bool ok = net_upload(a, n_layers, widths, W, b, s->dpol_W, s->dpol_b);
+    for (int l = 0; l <= n_layers; l++) s->pol_widths[l] = widths[l];
     ok = ok && dalloc(&s->dpol_obs, B * a.n_in) == hipSuccess && dalloc(&s->dpol_live, B) == hipSuccess && dalloc(&s->dpol_nlive, (size_t)1) == hipSuccess;
     ok = ok && hipFuncSetAttribute((const void *)policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
     ok = ok && hipFuncSetAttribute((const void *)policy_ac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
@@ -3004,6 +3028,7 @@ extern "C" int tum_sim_policy_attach_value(tum_sim *s, int n_layers, const int *
     if (!W) return 0;
     const size_t B = c->batch;
     bool ok = net_upload(s->va, n_layers, widths, W, b, s->dval_W, s->dval_b);
+    for (int l = 0; l <= n_layers; l++) s->val_widths[l] = widths[l];
     ok = ok && dalloc(&s->dval_term, B) == hipSuccess && dalloc(&s->dval_starts, B) == hipSuccess;
     ok = ok && hipFuncSetAttribute((const void *)policy_ac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
     ok = ok && hipDeviceSynchronize() == hipSuccess;
@@ -3113,6 +3138,7 @@ extern "C" int tum_sim_env_collect(tum_sim *s, int n_env_steps, const double *fi
     if (flush_inputs(c)) return 1;          // (older setters of x0 / yref in the pinned shadow go first: the begin kernel writes behind them)
     HIPCHK(hipStreamSynchronize(c->stream));
     const size_t total = EB * (COL_FIELDS + no) + 2 * B + B * no;
+    s->col_rows = 0;          // (what tum_sim_ppo_update may train on: set behind a collection that ran to its end)
     if (E > s->col_cap) {
         (void)hipFree(s->dcol); (void)hipFree(s->dcol_tab); s->dcol = nullptr; s->dcol_tab = nullptr; s->col_cap = 0;
         if (dalloc(&s->dcol, total) != hipSuccess || dalloc(&s->dcol_tab, EB) != hipSuccess) { (void)hipGetLastError(); return fail("env_collect: allocation failed"); }
@@ -3168,7 +3194,290 @@ extern "C" int tum_sim_env_collect(tum_sim *s, int n_env_steps, const double *fi
     for (size_t b = 0; b < B; b++) s->env_ended[b] = out[EB * (COL_FIELDS + no) + B + b] != 0.0 ? 1 : 0;
     for (int e = 0; e < n_env_steps; e++)
         if (out[COL_ERR * EB + (size_t)e * B] != 0.0) return fail("env_collect: planner segment longer than PLAN_MAXM points");
+    s->col_rows = EB;
     return lin_uniform_check(c);
+}
+
+
+// ---------------------------------------------------------------------------------------------- K14: the PPO update
+// the training view of one attached net: widths, strides and offsets in the flat parameter vector; the transposed matrices are allocated
+// here (zero: the padding stays zero) and filled by ppo_adam_kernel
+static bool ppo_net(PpoNet &t, const PolicyArgs &a, const int *widths, double *const *dW, double *const *db, int *P)
+{
+    memset(&t, 0, sizeof(t));
+    t.n_mat = a.n_mat;
+    int off = 0;
+    bool ok = true;
+    for (int l = 0; l < a.n_mat && ok; l++) {
+        t.in[l] = widths[l]; t.out[l] = widths[l + 1]; t.kp[l] = a.kp[l]; t.mp[l] = a.mp[l];
+        t.hs[l] = (widths[l] + 15) & ~15; t.kt[l] = (widths[l + 1] + 3) & ~3;
+        t.off[l] = off; off += widths[l + 1] * widths[l] + widths[l + 1];
+        t.W[l] = dW[l]; t.b[l] = db[l];
+        if (l > 0) ok = dalloc(&t.WT[l], (size_t)t.hs[l] * t.kt[l]) == hipSuccess;
+    }
+    *P = off;
+    return ok;
+}
+
+static void ppo_adam_args(tum_sim *s, PpoAdamArgs &a, int mode)
+{
+    memset(&a, 0, sizeof(a));
+    a.net[0] = s->tp; a.net[1] = s->tv; a.goff[0] = 0; a.goff[1] = s->tp.off[s->tp.n_mat - 1] + (s->tp.in[s->tp.n_mat - 1] + 1) * s->tp.out[s->tp.n_mat - 1];
+    a.P = s->ppo_P; a.n_parts = s->ppo_parts; a.mode = mode;
+    a.G = s->dppo_G; a.parts = s->dppo_part; a.theta = s->dppo_theta; a.m = s->dppo_m; a.v = s->dppo_v;
+    a.max_grad_norm = s->ppo_max_norm; a.beta1 = 0.9; a.beta2 = 0.999; a.eps = 1e-5; a.step = 0.0; a.bc2_sqrt = 1.0;
+}
+
+extern "C" int tum_sim_ppo_detach(tum_sim *s)
+{
+    if (!s) return fail("null argument");
+    DevGuard guard(s->c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(s->c->stream));
+    ppo_release(s);
+    return 0;
+}
+
+// The trainer on the attached nets: settings of stable_baselines3's PPO (rl_training.py:133-155), Adam's moments and step counter at
+// zero. The float32 master is read back from the packed policy and value nets -- their entries ARE float32 values -- so what is trained
+// is exactly what acts.
+extern "C" int tum_sim_ppo_attach(tum_sim *s, double clip_range, double ent_coef, double vf_coef, double max_grad_norm, int normalize_advantage)
+{
+    if (!s) return fail("null argument");
+    if (!s->pol) return fail("ppo_attach: no policy attached (tum_sim_policy_attach)");
+    if (s->va.n_mat == 0) return fail("ppo_attach: no value net attached (tum_sim_policy_attach_value)");
+    if (!(clip_range > 0.0) || !(max_grad_norm > 0.0)) return fail("ppo_attach: clip_range and max_grad_norm must be > 0");
+    tum_ocp *c = s->c;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    ppo_release(s);
+    int Pp = 0, Pv = 0;
+    bool ok = ppo_net(s->tp, s->pa, s->pol_widths, s->dpol_W, s->dpol_b, &Pp) && ppo_net(s->tv, s->va, s->val_widths, s->dval_W, s->dval_b, &Pv);
+    const size_t P = (size_t)Pp + Pv;
+    s->ppo_P = (int)P; s->ppo_parts = (int)((P + PPO_SLICE - 1) / PPO_SLICE);
+    ok = ok && dalloc(&s->dppo_theta, P) == hipSuccess && dalloc(&s->dppo_m, P) == hipSuccess && dalloc(&s->dppo_v, P) == hipSuccess;
+    ok = ok && dalloc(&s->dppo_G, P) == hipSuccess && dalloc(&s->dppo_part, (size_t)s->ppo_parts) == hipSuccess && dalloc(&s->dppo_advstat, (size_t)2) == hipSuccess;
+    ok = ok && hipFuncSetAttribute((const void *)ppo_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
+    if (ok) {
+        PpoAdamArgs a;
+        ppo_adam_args(s, a, 2);
+        hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((P + PPO_RED - 1) / PPO_RED)), dim3(PPO_RED), 0, c->stream, a);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+    }
+    if (!ok) { ppo_release(s); (void)hipGetLastError(); return fail("ppo_attach: allocation failed"); }
+    s->ppo_clip = clip_range; s->ppo_ent = ent_coef; s->ppo_vf = vf_coef; s->ppo_max_norm = max_grad_norm; s->ppo_normalize = normalize_advantage ? 1 : 0;
+    s->ppo_t = 0; s->ppo = true;
+    return 0;
+}
+
+// workspaces of a minibatch of up to `rows` rows (a multiple of 16): activations and deltas of every layer, the row records
+static int ppo_reserve_rows(tum_sim *s, size_t rows)
+{
+    if (rows <= s->ppo_rows_cap) return 0;
+    bool ok = true;
+    for (PpoNet *t : {&s->tp, &s->tv})
+        for (int l = 0; l < t->n_mat; l++) {
+            (void)hipFree(t->h[l]); (void)hipFree(t->d[l]); t->h[l] = t->d[l] = nullptr;
+            ok = ok && dalloc(&t->h[l], rows * t->hs[l]) == hipSuccess && dalloc(&t->d[l], rows * t->mp[l]) == hipSuccess;
+        }
+    (void)hipFree(s->dppo_rowrec); s->dppo_rowrec = nullptr;
+    ok = ok && dalloc(&s->dppo_rowrec, rows * PPO_ROW) == hipSuccess;
+    s->ppo_rows_cap = ok ? rows : 0;
+    if (!ok) { (void)hipGetLastError(); return fail("ppo: allocation failed"); }
+    return 0;
+}
+template <typename T>
+static int ppo_reserve(T **p, size_t *cap, size_t n)
+{
+    if (n <= *cap) return 0;
+    (void)hipFree(*p); *p = nullptr; *cap = 0;
+    if (dalloc(p, n) != hipSuccess) { (void)hipGetLastError(); return fail("ppo: allocation failed"); }
+    *cap = n;
+    return 0;
+}
+
+// the columns of a training buffer on the device
+struct PpoData { const double *obs; int stride; const double *act, *old_logp, *adv, *ret; };
+
+// One minibatch on the capsule's stream, nothing waited for: rows idx[0 .. n) of the buffer (idx null: 0 .. n - 1); its diagnostics to
+// dstats. apply 0: loss, gradients and their norm alone.
+static int ppo_minibatch_enqueue(tum_sim *s, const PpoData &d, const int *idx, int n, double lr, int apply, double *dstats)
+{
+    tum_ocp *c = s->c;
+    const int rows = (n + POL_TILE - 1) & ~(POL_TILE - 1);
+    PpoStatsArgs sa;
+    sa.n = n; sa.normalize = s->ppo_normalize; sa.idx = idx; sa.adv = d.adv; sa.out = s->dppo_advstat;
+    hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(PPO_RED), 0, c->stream, sa);
+    HIPCHK(hipGetLastError());
+    PpoTileArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.pi = s->pa; ta.vf = s->va; ta.tp = s->tp; ta.tv = s->tv;
+    ta.pi.n = ta.vf.n = n; ta.pi.obs = ta.vf.obs = d.obs; ta.pi.obs_stride = ta.vf.obs_stride = d.stride;
+    ta.rows = std::max(s->pa.rows, s->va.rows); ta.idx = idx;
+    ta.act = d.act; ta.old_logp = d.old_logp; ta.adv = d.adv; ta.ret = d.ret; ta.advstat = s->dppo_advstat;
+    ta.clip = s->ppo_clip; ta.ent_coef = s->ppo_ent; ta.vf_coef = s->ppo_vf; ta.rowrec = s->dppo_rowrec;
+    hipLaunchKernelGGL(ppo_tile_kernel, dim3(rows / POL_TILE), dim3(64 * POL_WAVES), sizeof(double) * 2 * ta.rows * POL_TILE, c->stream, ta);
+    HIPCHK(hipGetLastError());
+    PpoGradArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.net[0] = s->tp; ga.net[1] = s->tv; ga.rows = rows; ga.G = s->dppo_G;
+    ga.goff[0] = 0; ga.goff[1] = s->tp.off[s->tp.n_mat - 1] + (s->tp.in[s->tp.n_mat - 1] + 1) * s->tp.out[s->tp.n_mat - 1];
+    int tiles = 0;
+    for (int ni = 0; ni < 2; ni++)
+        for (int l = 0; l < POL_MAXMAT; l++) {
+            const PpoNet &t = ga.net[ni];
+            ga.first[ni * POL_MAXMAT + l] = tiles;
+            if (l < t.n_mat) tiles += (t.mp[l] / 16) * (t.hs[l] / 16 + 1);
+        }
+    ga.first[2 * POL_MAXMAT] = tiles;
+    hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(tiles), dim3(64), 0, c->stream, ga);
+    HIPCHK(hipGetLastError());
+    PpoNormArgs na;
+    na.P = s->ppo_P; na.n_parts = s->ppo_parts; na.n = n; na.G = s->dppo_G; na.rowrec = s->dppo_rowrec;
+    na.ent_coef = s->ppo_ent; na.vf_coef = s->ppo_vf; na.parts = s->dppo_part; na.stats = dstats;
+    hipLaunchKernelGGL(ppo_norm_kernel, dim3(s->ppo_parts + 1), dim3(PPO_RED), 0, c->stream, na);
+    HIPCHK(hipGetLastError());
+    PpoAdamArgs aa;
+    ppo_adam_args(s, aa, apply ? 1 : 0);
+    aa.stats = dstats;
+    if (apply) {
+        const double t = (double)(s->ppo_t + 1);
+        aa.step = lr / (1.0 - std::pow(aa.beta1, t)); aa.bc2_sqrt = std::sqrt(1.0 - std::pow(aa.beta2, t));
+    }
+    hipLaunchKernelGGL(ppo_adam_kernel, dim3(apply ? (s->ppo_P + PPO_RED - 1) / PPO_RED : 1), dim3(PPO_RED), 0, c->stream, aa);
+    HIPCHK(hipGetLastError());
+    if (apply) s->ppo_t++;
+    return 0;
+}
+
+// a host buffer of N rows into the trainer's own device copy: observations N x n_obs, then actions (as doubles), old log-probabilities,
+// advantages and returns, N each
+static int ppo_upload(tum_sim *s, size_t N, const double *obs, const int *actions, const double *old_logp, const double *adv, const double *ret, PpoData *d)
+{
+    const size_t no = s->pa.n_in;
+    if (ppo_reserve(&s->dppo_data, &s->ppo_data_cap, N * (no + 4))) return 1;
+    std::vector<double> act(N);
+    for (size_t i = 0; i < N; i++) {
+        if (actions[i] < 0 || actions[i] >= s->pa.n_act) return fail("ppo: action of row " + std::to_string(i) + " is outside the policy's " + std::to_string(s->pa.n_act));
+        act[i] = (double)actions[i];
+    }
+    double *p = s->dppo_data;
+    HIPCHK(hipMemcpy(p, obs, sizeof(double) * N * no, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p + N * no, act.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p + N * (no + 1), old_logp, sizeof(double) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p + N * (no + 2), adv, sizeof(double) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p + N * (no + 3), ret, sizeof(double) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    d->obs = p; d->stride = (int)no; d->act = p + N * no; d->old_logp = p + N * (no + 1); d->adv = p + N * (no + 2); d->ret = p + N * (no + 3);
+    return 0;
+}
+
+// One minibatch of n host rows. apply 0 computes loss and gradients only: parameters, moments and the step counter stay as they are.
+// stats_out: TUM_PPO_STATS doubles. grads_out (optional): the UNCLIPPED gradients, the flat parameter vector in torch's layout (per net
+// W_0 row-major (out, in), b_0, W_1, ...; policy net then value net). rows_out (optional): n x 2, the log-probability of the row's
+// action and its value as the tile kernel computed them.
+extern "C" int tum_sim_ppo_step(tum_sim *s, int n, const double *obs, const int *actions, const double *old_log_probs, const double *advantages,
+                                const double *returns, double lr, int apply, double *stats_out, double *grads_out, double *rows_out)
+{
+    if (!s || !obs || !actions || !old_log_probs || !advantages || !returns || !stats_out) return fail("null argument");
+    if (!s->ppo) return fail("ppo_step: no trainer attached (tum_sim_ppo_attach)");
+    if (n < 1) return fail("ppo_step: n < 1");
+    tum_ocp *c = s->c;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t rows = ((size_t)n + POL_TILE - 1) & ~(size_t)(POL_TILE - 1);
+    PpoData d;
+    if (ppo_upload(s, n, obs, actions, old_log_probs, advantages, returns, &d)) return 1;
+    if (ppo_reserve_rows(s, rows) || ppo_reserve(&s->dppo_stats, &s->ppo_stats_cap, (size_t)PPO_STATS)) return 1;
+    if (ppo_minibatch_enqueue(s, d, nullptr, n, lr, apply, s->dppo_stats)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(stats_out, s->dppo_stats, sizeof(double) * PPO_STATS, hipMemcpyDeviceToHost));
+    if (grads_out) HIPCHK(hipMemcpy(grads_out, s->dppo_G, sizeof(double) * s->ppo_P, hipMemcpyDeviceToHost));
+    if (rows_out) {
+        std::vector<double> rec((size_t)n * PPO_ROW);
+        HIPCHK(hipMemcpy(rec.data(), s->dppo_rowrec, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) { rows_out[2 * i] = rec[(size_t)i * PPO_ROW + PPO_R_LOGP]; rows_out[2 * i + 1] = rec[(size_t)i * PPO_ROW + PPO_R_V]; }
+    }
+    return 0;
+}
+
+// One whole update: n_epochs passes over the N buffer rows, pass e in the order perm[e][0 .. N), cut into minibatches of batch_size
+// rows (the last one may be short); every minibatch's chain is enqueued, one wait, one download of n_epochs x ceil(N / batch_size) x
+// TUM_PPO_STATS diagnostics. obs .. returns all NULL: the buffer the last tum_sim_env_collect left on the device (row e B + b).
+extern "C" int tum_sim_ppo_update(tum_sim *s, int N, const double *obs, const int *actions, const double *old_log_probs, const double *advantages,
+                                  const double *returns, const int *perm, int n_epochs, int batch_size, double lr, double *stats_out)
+{
+    if (!s || !perm || !stats_out) return fail("null argument");
+    if (!s->ppo) return fail("ppo_update: no trainer attached (tum_sim_ppo_attach)");
+    if (N < 1 || n_epochs < 1) return fail("ppo_update: N and n_epochs must be >= 1");
+    if (batch_size < 1) return fail("ppo_update: batch_size < 1");
+    const bool resident = !obs && !actions && !old_log_probs && !advantages && !returns;
+    if (!resident && (!obs || !actions || !old_log_probs || !advantages || !returns)) return fail("ppo_update: a buffer is all five arrays, or none of them");
+    if (resident && s->col_rows == 0) return fail("ppo_update: no buffer given and no collection on the device (tum_sim_env_collect)");
+    if (resident && s->col_rows != (size_t)N) return fail("ppo_update: the collection on the device has " + std::to_string(s->col_rows) + " rows, not " + std::to_string(N));
+    for (size_t i = 0; i < (size_t)n_epochs * N; i++)
+        if (perm[i] < 0 || perm[i] >= N) return fail("ppo_update: perm[" + std::to_string(i / N) + "][" + std::to_string(i % N) + "] is outside the buffer");
+    tum_ocp *c = s->c;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int bs = std::min(batch_size, N), n_mb = (N + bs - 1) / bs;
+    PpoData d;
+    if (resident) {
+        const size_t EB = N;
+        d.obs = s->dcol + COL_FIELDS * EB; d.stride = s->pa.n_in; d.act = s->dcol + COL_ACTION * EB; d.old_logp = s->dcol + COL_LOGP * EB;
+        d.adv = s->dcol + COL_ADV * EB; d.ret = s->dcol + COL_RET * EB;
+    } else if (ppo_upload(s, N, obs, actions, old_log_probs, advantages, returns, &d)) return 1;
+    const size_t n_stats = (size_t)n_epochs * n_mb * PPO_STATS;
+    if (ppo_reserve_rows(s, ((size_t)bs + POL_TILE - 1) & ~(size_t)(POL_TILE - 1)) || ppo_reserve(&s->dppo_stats, &s->ppo_stats_cap, n_stats) ||
+        ppo_reserve(&s->dppo_idx, &s->ppo_idx_cap, (size_t)n_epochs * N)) return 1;
+    HIPCHK(hipMemcpy(s->dppo_idx, perm, sizeof(int) * (size_t)n_epochs * N, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    for (int e = 0; e < n_epochs; e++)
+        for (int k = 0; k < n_mb; k++)
+            if (ppo_minibatch_enqueue(s, d, s->dppo_idx + (size_t)e * N + (size_t)k * bs, std::min(bs, N - k * bs), lr, 1,
+                                      s->dppo_stats + ((size_t)e * n_mb + k) * PPO_STATS)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(stats_out, s->dppo_stats, sizeof(double) * n_stats, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the float32 parameters the device acts with, per matrix as the attach functions take them (W[l]: (out, in) row-major)
+extern "C" int tum_sim_ppo_params(tum_sim *s, float *const *W, float *const *b, float *const *VW, float *const *Vb)
+{
+    if (!s || !W || !b || !VW || !Vb) return fail("null argument");
+    if (!s->ppo) return fail("ppo_params: no trainer attached (tum_sim_ppo_attach)");
+    DevGuard guard(s->c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(s->c->stream));
+    std::vector<float> th(s->ppo_P);
+    HIPCHK(hipMemcpy(th.data(), s->dppo_theta, sizeof(float) * th.size(), hipMemcpyDeviceToHost));
+    size_t base = 0;
+    for (int ni = 0; ni < 2; ni++) {
+        const PpoNet &t = ni ? s->tv : s->tp;
+        float *const *Wo = ni ? VW : W, *const *bo = ni ? Vb : b;
+        size_t end = 0;
+        for (int l = 0; l < t.n_mat; l++) {
+            if (!Wo[l] || !bo[l]) return fail("null argument");
+            const size_t nw = (size_t)t.out[l] * t.in[l];
+            memcpy(Wo[l], &th[base + t.off[l]], sizeof(float) * nw);
+            memcpy(bo[l], &th[base + t.off[l] + nw], sizeof(float) * t.out[l]);
+            end = t.off[l] + nw + t.out[l];
+        }
+        base += end;
+    }
+    return 0;
+}
+
+// Adam's state: the moments over the flat parameter vector (n_params doubles each; either may be NULL) and the step counter
+extern "C" int tum_sim_ppo_state(tum_sim *s, double *m, double *v, long long *t, int *n_params)
+{
+    if (!s) return fail("null argument");
+    if (!s->ppo) return fail("ppo_state: no trainer attached (tum_sim_ppo_attach)");
+    DevGuard guard(s->c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(s->c->stream));
+    if (m) HIPCHK(hipMemcpy(m, s->dppo_m, sizeof(double) * s->ppo_P, hipMemcpyDeviceToHost));
+    if (v) HIPCHK(hipMemcpy(v, s->dppo_v, sizeof(double) * s->ppo_P, hipMemcpyDeviceToHost));
+    if (t) *t = s->ppo_t;
+    if (n_params) *n_params = s->ppo_P;
+    return 0;
 }
 
 

@@ -78,7 +78,8 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
              "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step",
              "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout",
-             "tum_sim_policy_attach_value", "tum_sim_policy_eval_ac", "tum_sim_gae", "tum_sim_env_collect"]
+             "tum_sim_policy_attach_value", "tum_sim_policy_eval_ac", "tum_sim_gae", "tum_sim_env_collect",
+             "tum_sim_ppo_attach", "tum_sim_ppo_detach", "tum_sim_ppo_step", "tum_sim_ppo_update", "tum_sim_ppo_params", "tum_sim_ppo_state"]
 
 
 def load_library(path=None):
@@ -170,6 +171,14 @@ def load_library(path=None):
         L.tum_sim_policy_eval_ac.argtypes = [vp, dp, ci, u64, u64, ctypes.c_uint, ip, dp, dp, dp]
         L.tum_sim_gae.argtypes = [vp, ci, ci, dp, dp, dp, dp, dp, cd, cd, dp, dp]
         L.tum_sim_env_collect.argtypes = [vp, ci, dp, dp, ip, u64, u64, cd, cd, dp]
+    if hasattr(L, "tum_sim_ppo_attach"):
+        pvp = ctypes.POINTER(vp)
+        L.tum_sim_ppo_attach.argtypes = [vp, cd, cd, cd, cd, ci]
+        L.tum_sim_ppo_detach.argtypes = [vp]
+        L.tum_sim_ppo_step.argtypes = [vp, ci, dp, ip, dp, dp, dp, cd, ci, dp, dp, dp]
+        L.tum_sim_ppo_update.argtypes = [vp, ci, dp, ip, dp, dp, dp, ip, ci, ci, cd, dp]
+        L.tum_sim_ppo_params.argtypes = [vp, pvp, pvp, pvp, pvp]
+        L.tum_sim_ppo_state.argtypes = [vp, dp, dp, ctypes.POINTER(ctypes.c_longlong), ip]
     _libs[p] = L
     if p == LIB_PATH:
         _lib = L
@@ -1074,6 +1083,118 @@ class DeviceClosedLoop:
         tail = out[(F + no) * E * B:]
         r["last_values"], r["last_dones"], r["next_observation"] = tail[:B].copy(), tail[B:2 * B].copy(), tail[2 * B:].reshape(B, no).copy()
         return r
+
+    # ---- the PPO update (stable_baselines3 PPO.train)
+    PPO_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "grad_norm", "n")          # TUM_PPO_* of tum_nmpc.h
+
+    def ppo_attach(self, clip_range=0.2, ent_coef=0.006, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True):
+        """The trainer on the attached policy and value net (tum_sim_ppo_attach): Adam's moments and step counter at zero. Detaching or
+        re-attaching the policy or the value net detaches it."""
+        self._chk(self._L.tum_sim_ppo_attach(self._s, float(clip_range), float(ent_coef), float(vf_coef), float(max_grad_norm),
+                                             int(bool(normalize_advantage))), "sim_ppo_attach")
+
+    def ppo_detach(self):
+        self._chk(self._L.tum_sim_ppo_detach(self._s), "sim_ppo_detach")
+
+    def _ppo_shapes(self):
+        """[(out, in), ...] of the policy net and of the value net"""
+        pw, vw = getattr(self, "policy_widths", None), getattr(self, "value_widths", None)
+        if not pw or not vw:
+            raise Exception("ppo: no policy with a value net attached (attach_policy)")
+        return [(o, i) for i, o in zip(pw[:-1], pw[1:])], [(o, i) for i, o in zip(vw[:-1], vw[1:])]
+
+    def _ppo_split(self, flat):
+        """the flat parameter vector (per net W_0, b_0, W_1, ...; policy then value) -> (weights, biases, value_weights, value_biases)"""
+        out, p = [], 0
+        for shapes in self._ppo_shapes():
+            Ws, bs = [], []
+            for o, i in shapes:
+                Ws.append(flat[p:p + o * i].reshape(o, i).copy()); p += o * i
+                bs.append(flat[p:p + o].copy()); p += o
+            out += [Ws, bs]
+        return tuple(out)
+
+    def _ppo_rows(self, who, n, obs, actions, old_log_probs, advantages, returns):
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.shape != (n, self.policy_widths[0]):
+            raise Exception(f"{who}: observations are ({n}, {self.policy_widths[0]})")
+        act = np.asarray(actions)
+        if act.shape != (n,) or not np.issubdtype(act.dtype, np.integer):
+            raise Exception(f"{who}: actions is an integer array ({n},)")
+        cols = [np.ascontiguousarray(a, dtype=np.float64) for a in (old_log_probs, advantages, returns)]
+        if any(a.shape != (n,) for a in cols):
+            raise Exception(f"{who}: old_log_probs, advantages and returns are ({n},)")
+        return [obs, np.ascontiguousarray(act, dtype=np.int32)] + cols
+
+    def ppo_step(self, obs, actions, old_log_probs, advantages, returns, lr, apply=True, want_grads=False, want_rows=False):
+        """One minibatch from host arrays (tum_sim_ppo_step). apply=False: loss and gradients only, nothing changes. Returns the dict of
+        PPO_STATS; with want_grads `grads`: (weights, biases, value_weights, value_biases) lists of float64 arrays, UNCLIPPED; with
+        want_rows `log_probs` and `values` (n,) as the update computed them."""
+        shapes = self._ppo_shapes()
+        n = len(np.asarray(actions))
+        if n < 1:
+            raise Exception("ppo_step: n < 1")
+        obs, act, lp, adv, ret = self._ppo_rows("ppo_step", n, obs, actions, old_log_probs, advantages, returns)
+        P = sum(o * i + o for sh in shapes for o, i in sh)
+        stats, grads, rows = np.zeros(len(self.PPO_STATS)), np.zeros(P), np.zeros((n, 2))
+        self._chk(self._L.tum_sim_ppo_step(self._s, n, _dp(obs), act.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(lp), _dp(adv), _dp(ret),
+                                           float(lr), int(bool(apply)), _dp(stats), _dp(grads) if want_grads else None,
+                                           _dp(rows) if want_rows else None), "sim_ppo_step")
+        out = dict(zip(self.PPO_STATS, stats))
+        out["n"] = int(out["n"])
+        if want_grads:
+            out["grads"] = self._ppo_split(grads)
+        if want_rows:
+            out["log_probs"], out["values"] = rows[:, 0].copy(), rows[:, 1].copy()
+        return out
+
+    def ppo_update(self, N, perm, batch_size, lr, buffer=None):
+        """One update (tum_sim_ppo_update): perm (n_epochs, N) integers in [0, N); buffer None: the rows the last env_collect left on
+        the device, else (obs (N, n_obs), actions, old_log_probs, advantages, returns (N,)). Returns a dict of PPO_STATS arrays
+        (n_epochs, minibatches)."""
+        ip = ctypes.POINTER(ctypes.c_int)
+        N = int(N)
+        perm = np.asarray(perm)
+        if perm.ndim != 2 or perm.shape[1] != N or perm.shape[0] < 1 or not np.issubdtype(perm.dtype, np.integer):
+            raise Exception(f"ppo_update: perm is an integer array (n_epochs, {N})")
+        if int(batch_size) < 1:
+            raise Exception("ppo_update: batch_size < 1")
+        if np.any(perm < 0) or np.any(perm >= N):
+            raise Exception("ppo_update: perm is outside the buffer")
+        perm = np.ascontiguousarray(perm, dtype=np.int32)
+        n_epochs, bs = perm.shape[0], min(int(batch_size), N)
+        n_mb = (N + bs - 1) // bs
+        stats = np.zeros((n_epochs, n_mb, len(self.PPO_STATS)))
+        if buffer is None:
+            args = [None] * 5
+        else:
+            self._ppo_shapes()
+            rows = self._ppo_rows("ppo_update", N, *buffer)
+            args = [_dp(rows[0]), rows[1].ctypes.data_as(ip)] + [_dp(a) for a in rows[2:]]
+        self._chk(self._L.tum_sim_ppo_update(self._s, N, *args, perm.ctypes.data_as(ip), n_epochs, int(batch_size), float(lr), _dp(stats)),
+                  "sim_ppo_update")
+        out = {k: stats[:, :, i].copy() for i, k in enumerate(self.PPO_STATS)}
+        out["n"] = out["n"].astype(np.int64)
+        return out
+
+    def ppo_params(self):
+        """(weights, biases, value_weights, value_biases): the float32 parameters the device acts with"""
+        nets = []
+        for shapes in self._ppo_shapes():
+            nets += [[np.zeros((o, i), dtype=np.float32) for o, i in shapes], [np.zeros(o, dtype=np.float32) for o, i in shapes]]
+        ptrs = [(ctypes.c_void_p * len(a))(*[x.ctypes.data for x in a]) for a in nets]
+        self._chk(self._L.tum_sim_ppo_params(self._s, *ptrs), "sim_ppo_params")
+        return tuple(nets)
+
+    def ppo_state(self):
+        """Adam's state: dict of m and v -- each (weights, biases, value_weights, value_biases) of float64 arrays -- and t, the step counter"""
+        shapes = self._ppo_shapes()
+        P = sum(o * i + o for sh in shapes for o, i in sh)
+        m, v, t, n = np.zeros(P), np.zeros(P), ctypes.c_longlong(0), ctypes.c_int(0)
+        self._chk(self._L.tum_sim_ppo_state(self._s, _dp(m), _dp(v), ctypes.byref(t), ctypes.byref(n)), "sim_ppo_state")
+        if n.value != P:
+            raise Exception(f"ppo_state: the device holds {n.value} parameters, the attached widths say {P}")
+        return dict(m=self._ppo_split(m), v=self._ppo_split(v), t=int(t.value))
 
     def policy_eval(self, obs):
         """the attached policy alone on (n, n_obs) observations, independent of the loop's batch: dict of logits (n, A), probabilities
