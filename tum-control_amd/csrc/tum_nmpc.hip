@@ -2193,1385 +2193,6 @@ extern "C" int tum_ocp_constraints_get(tum_ocp *c, int stage, const char *field,
     return fetch(c, c->dbnd, (size_t)6 * NB, (size_t)row * NB + stage, v, 1, b0, nb, 1);
 }
 
-// ---------------------------------------------------------------------------------------------- K8 / K9: device closed loop
-struct tum_sim {
-    tum_ocp *c;
-    int n_track, loop_circuit, n_elem, step, log_cap;
-    double Tp, Ts;
-    int win[8];
-    double *dtrack, *dxsim, *dpose, *dhist, *dref0;
-    int *dclosest, *derr, *dstep;
-    hipGraphExec_t graph; int graph_steps;            // captured chunk of control steps (tum_sim_run)
-    unsigned graph_epoch; bool graph_fanout;          // configuration of the capsule the chunk was captured with
-    double *lCiLX, *lSimX, *lU, *lREF, *lDBG;
-    hipStream_t s2; hipEvent_t evF, evJ;              // side stream of the linearisation that runs beside the planner, fork / join events
-    double *ddw, *dde; int dist_len;                  // disturbance realisation played back by the loop (tum_sim_set_disturbances)
-    // segment scoring (tum_sim_segments_attach): end index and accumulators per instance, groups of contiguous instances
-    bool seg; int seg_groups; double seg_max_lat, seg_max_acomb;
-    int *dseg_end, *dseg_off, *dseg_steps, *dseg_state, *dseg_qpf;
-    double *dseg_lat, *dseg_ssq, *dseg_acomb, *dseg_ggv, *dseg_out;
-    // RL environment (tum_sim_env_attach): the settings as the kernels take them, the table / indices / bounds and the per-instance state
-    // on the device, pinned staging of the one upload and the one download of an environment step, and which episodes have ended (host)
-    bool env; int env_mpc_steps, env_rec; EnvArgs ea;
-    double *denv_table, *denv_bounds, *denv_acc, *denv_win, *denv_out, *henv_out;
-    int *denv_idx, *denv_in, *denv_ep, *denv_count, *denv_flags, *denv_qpf, *denv_samples, *henv_in;
-    unsigned char *env_ended;
-    // the agent (tum_sim_policy_attach): the policy net in the order policy_kernel reads it, its input inside a rollout, the live flags and
-    // their counter; the device-side log of a rollout (tum_sim_env_rollout), grown on demand
-    bool pol; PolicyArgs pa;
-    double *dpol_W[POL_MAXMAT], *dpol_b[POL_MAXMAT], *dpol_obs;
-    int *dpol_live, *dpol_nlive;
-    double *droll_log; int *droll_ints; size_t roll_cap;
-    // the value net beside it (tum_sim_policy_attach_value), the value of a step's own observation and the episode-start flags of a
-    // collection's first step, and the device-side buffer of a collection with its start table (tum_sim_env_collect), grown on demand
-    PolicyArgs va;
-    double *dval_W[POL_MAXMAT], *dval_b[POL_MAXMAT], *dval_term, *dval_starts;
-    double *dcol; int *dcol_tab; size_t col_cap;
-    // the trainer (tum_sim_ppo_attach): the true widths of the two nets, the rows the last collection left in dcol, the settings and
-    // Adam's step counter, the training views of the nets, the float32 master / moments / gradient over the flat parameter vector
-    // (policy net then value net), and workspaces grown on demand: minibatch rows, an uploaded buffer, index lists, diagnostics
-    int pol_widths[POL_MAXMAT + 1], val_widths[POL_MAXMAT + 1];
-    size_t col_rows;
-    bool ppo; double ppo_clip, ppo_ent, ppo_vf, ppo_max_norm; int ppo_normalize, ppo_P, ppo_parts; long long ppo_t;
-    PpoNet tp, tv;
-    float *dppo_theta; double *dppo_m, *dppo_v, *dppo_G, *dppo_part, *dppo_advstat, *dppo_rowrec, *dppo_stats, *dppo_data; int *dppo_idx;
-    size_t ppo_rows_cap, ppo_stats_cap, ppo_data_cap, ppo_idx_cap;
-};
-static void ppo_release(tum_sim *s)
-{
-    for (PpoNet *t : {&s->tp, &s->tv})
-        for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(t->WT[l]); (void)hipFree(t->h[l]); (void)hipFree(t->d[l]); }
-    memset(&s->tp, 0, sizeof(s->tp)); memset(&s->tv, 0, sizeof(s->tv));
-    (void)hipFree(s->dppo_theta); (void)hipFree(s->dppo_m); (void)hipFree(s->dppo_v); (void)hipFree(s->dppo_G); (void)hipFree(s->dppo_part);
-    (void)hipFree(s->dppo_advstat); (void)hipFree(s->dppo_rowrec); (void)hipFree(s->dppo_stats); (void)hipFree(s->dppo_data); (void)hipFree(s->dppo_idx);
-    s->dppo_theta = nullptr; s->dppo_idx = nullptr;
-    s->dppo_m = s->dppo_v = s->dppo_G = s->dppo_part = s->dppo_advstat = s->dppo_rowrec = s->dppo_stats = s->dppo_data = nullptr;
-    s->ppo_rows_cap = s->ppo_stats_cap = s->ppo_data_cap = s->ppo_idx_cap = 0;
-    s->ppo = false; s->ppo_t = 0;
-}
-static void value_release(tum_sim *s)
-{
-    ppo_release(s);            // (the trainer updates both nets: it goes with either)
-    for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(s->dval_W[l]); (void)hipFree(s->dval_b[l]); s->dval_W[l] = s->dval_b[l] = nullptr; }
-    (void)hipFree(s->dval_term); (void)hipFree(s->dval_starts); (void)hipFree(s->dcol); (void)hipFree(s->dcol_tab);
-    s->dval_term = s->dval_starts = s->dcol = nullptr; s->dcol_tab = nullptr;
-    s->col_cap = 0; s->col_rows = 0; s->va.n_mat = 0;
-}
-static void policy_release(tum_sim *s)
-{
-    value_release(s);          // (the value net takes the policy's inputs: it goes with it)
-    for (int l = 0; l < POL_MAXMAT; l++) { (void)hipFree(s->dpol_W[l]); (void)hipFree(s->dpol_b[l]); s->dpol_W[l] = s->dpol_b[l] = nullptr; }
-    (void)hipFree(s->dpol_obs); (void)hipFree(s->dpol_live); (void)hipFree(s->dpol_nlive); (void)hipFree(s->droll_log); (void)hipFree(s->droll_ints);
-    s->dpol_obs = s->droll_log = nullptr; s->dpol_live = s->dpol_nlive = s->droll_ints = nullptr;
-    s->roll_cap = 0; s->pol = false;
-}
-static void env_release(tum_sim *s)
-{
-    policy_release(s);          // (the policy reads the environment's observation and writes its actions: it goes with it)
-    (void)hipFree(s->denv_table); (void)hipFree(s->denv_bounds); (void)hipFree(s->denv_acc); (void)hipFree(s->denv_win); (void)hipFree(s->denv_out);
-    (void)hipFree(s->denv_idx); (void)hipFree(s->denv_in); (void)hipFree(s->denv_ep); (void)hipFree(s->denv_count); (void)hipFree(s->denv_flags);
-    (void)hipFree(s->denv_qpf); (void)hipFree(s->denv_samples);
-    if (s->henv_out) (void)hipHostFree(s->henv_out);
-    if (s->henv_in) (void)hipHostFree(s->henv_in);
-    free(s->env_ended);
-    s->denv_table = s->denv_bounds = s->denv_acc = s->denv_win = s->denv_out = s->henv_out = nullptr;
-    s->denv_idx = s->denv_in = s->denv_ep = s->denv_count = s->denv_flags = s->denv_qpf = s->denv_samples = s->henv_in = nullptr;
-    s->env_ended = nullptr; s->env = false;
-}
-// episode counters, step accumulators, flags and the estimator's sample numbers back to zero (fills on the NULL stream: the caller synchronises)
-static int env_zero(tum_sim *s)
-{
-    const size_t B = s->c->batch;
-    HIPCHK(hipMemset(s->denv_ep, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->denv_count, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->denv_flags, 0, sizeof(int) * B));
-    HIPCHK(hipMemset(s->denv_qpf, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->denv_samples, 0, sizeof(int) * B));
-    HIPCHK(hipMemset(s->denv_acc, 0, sizeof(double) * B * 4));
-    memset(s->env_ended, 0, B);
-    return 0;
-}
-static void seg_release(tum_sim *s)
-{
-    (void)hipFree(s->dseg_end); (void)hipFree(s->dseg_off); (void)hipFree(s->dseg_steps); (void)hipFree(s->dseg_state); (void)hipFree(s->dseg_qpf);
-    (void)hipFree(s->dseg_lat); (void)hipFree(s->dseg_ssq); (void)hipFree(s->dseg_acomb); (void)hipFree(s->dseg_ggv); (void)hipFree(s->dseg_out);
-    s->dseg_end = s->dseg_off = s->dseg_steps = s->dseg_state = s->dseg_qpf = nullptr;
-    s->dseg_lat = s->dseg_ssq = s->dseg_acomb = s->dseg_ggv = s->dseg_out = nullptr;
-    s->seg = false; s->seg_groups = 0;
-}
-// a new evaluation: accumulators and state words of every segment back to zero (fills on the NULL stream: the caller synchronises)
-static int seg_zero(tum_sim *s)
-{
-    const size_t B = s->c->batch;
-    HIPCHK(hipMemset(s->dseg_steps, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->dseg_state, 0, sizeof(int) * B)); HIPCHK(hipMemset(s->dseg_qpf, 0, sizeof(int) * B));
-    HIPCHK(hipMemset(s->dseg_lat, 0, sizeof(double) * B)); HIPCHK(hipMemset(s->dseg_ssq, 0, sizeof(double) * B)); HIPCHK(hipMemset(s->dseg_acomb, 0, sizeof(double) * B));
-    return 0;
-}
-
-extern "C" int tum_planner_emulate(const double *track, int n_track, const double *pose, int P, int n_points, double Tp,
-                                   int loop_circuit, double *ref_out, int *closest_out, int device)
-{
-    if (!track || !pose || !ref_out) return fail("null argument");
-    if (n_track < 2 || P < 1 || n_points < 2) return fail("planner_emulate: bad sizes");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device: libtumnmpc has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail("planner_emulate: device ordinal out of range");
-    DevGuard guard(device); GUARD_OK(guard);
-    DevTmp tt, tp, tout, tcl, terr;
-    HIPCHK(tt.alloc(sizeof(double) * 4 * n_track)); HIPCHK(tp.alloc(sizeof(double) * 2 * P));
-    HIPCHK(tout.alloc(sizeof(double) * 4 * (size_t)P * n_points)); HIPCHK(tcl.alloc(sizeof(int) * P)); HIPCHK(terr.alloc(sizeof(int)));
-    double *dt = tt.as<double>(), *dp = tp.as<double>(), *dout = tout.as<double>(); int *dcl = tcl.as<int>(), *derr = terr.as<int>();
-    HIPCHK(hipMemset(derr, 0, sizeof(int)));
-    HIPCHK(hipMemcpy(dt, track, sizeof(double) * 4 * n_track, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dp, pose, sizeof(double) * 2 * P, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(planner_kernel, dim3(P), dim3(64), 0, 0, dt, n_track, dp, 2, n_points, Tp, loop_circuit, dout, 4,
-                       (double *)nullptr, dcl, derr, P, (int *)nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    int err = 0;
-    HIPCHK(hipMemcpy(&err, derr, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ref_out, dout, sizeof(double) * 4 * (size_t)P * n_points, hipMemcpyDeviceToHost));
-    if (closest_out) HIPCHK(hipMemcpy(closest_out, dcl, sizeof(int) * P, hipMemcpyDeviceToHost));
-    if (err) return fail("planner_emulate: extracted segment longer than PLAN_MAXM points");
-    return 0;
-}
-
-extern "C" void tum_sim_free(tum_sim *s)
-{
-    if (!s) return;
-    DevGuard guard(s->c->d.device);
-    (void)hipFree(s->dtrack); (void)hipFree(s->dxsim); (void)hipFree(s->dpose); (void)hipFree(s->dhist); (void)hipFree(s->dref0);
-    (void)hipFree(s->dclosest); (void)hipFree(s->derr); (void)hipFree(s->dstep);
-    if (s->graph) (void)hipGraphExecDestroy(s->graph);
-    if (s->s2) { (void)hipStreamSynchronize(s->s2); (void)hipStreamDestroy(s->s2); (void)hipEventDestroy(s->evF); (void)hipEventDestroy(s->evJ); }
-    (void)hipFree(s->lCiLX); (void)hipFree(s->lSimX); (void)hipFree(s->lU); (void)hipFree(s->lREF); (void)hipFree(s->lDBG);
-    (void)hipFree(s->ddw); (void)hipFree(s->dde);
-    seg_release(s);
-    env_release(s);
-    delete s;
-}
-
-extern "C" tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track, double Tp, int loop_circuit, double Ts, int n_elem,
-                                   const int *windows, int log_capacity)
-{
-    if (!c || !track || !windows) { fail("null argument"); return nullptr; }
-    if (n_track < 2 || !(Tp > 0) || !(Ts > 0) || n_elem < 1 || log_capacity < 0) { fail("sim_create: bad arguments"); return nullptr; }
-    for (int i = 0; i < 8; i++) if (windows[i] < 1 || windows[i] > 4) { fail("sim_create: estimator windows must be 1..4"); return nullptr; }
-    if (c->nlp_type) { fail("sim_create: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)"); return nullptr; }
-    if (c->rti_phase) { fail("sim_create: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0"); return nullptr; }
-    DevGuard guard(c->d.device); if (!guard.ok) { fail("hipSetDevice failed"); return nullptr; }
-    if (c->sn) {   // the state estimator writes the nominal x0 only: the samples follow by fan-out
-        if (!c->have_offs) { fail("sim_create: an SNMPC capsule needs its sample offsets (tum_ocp_snmpc_set_offsets)"); return nullptr; }
-        c->fanout = true;
-    }
-    tum_sim *s = new tum_sim();
-    memset(s, 0, sizeof(*s));
-    s->c = c; s->n_track = n_track; s->loop_circuit = loop_circuit; s->n_elem = n_elem; s->Tp = Tp; s->Ts = Ts; s->log_cap = log_capacity;
-    for (int i = 0; i < 8; i++) s->win[i] = windows[i];
-    const size_t B = c->batch, L = log_capacity;
-    bool ok = true;
-    ok &= dalloc(&s->dtrack, (size_t)4 * n_track) == hipSuccess;
-    ok &= dalloc(&s->dxsim, B * 7) == hipSuccess && dalloc(&s->dpose, B * 2) == hipSuccess && dalloc(&s->dhist, B * 32) == hipSuccess;
-    ok &= dalloc(&s->dref0, B * 4) == hipSuccess && dalloc(&s->dclosest, B) == hipSuccess && dalloc(&s->derr, (size_t)1) == hipSuccess && dalloc(&s->dstep, (size_t)2) == hipSuccess;
-    if (L > 0) {
-        ok &= dalloc(&s->lCiLX, (L + 1) * B * 7) == hipSuccess && dalloc(&s->lSimX, (L + 1) * B * 8) == hipSuccess;
-        ok &= dalloc(&s->lU, L * B * 2) == hipSuccess && dalloc(&s->lREF, L * B * 4) == hipSuccess && dalloc(&s->lDBG, L * B * 5) == hipSuccess;
-    }
-    ok = ok && hipMemcpy(s->dtrack, track, sizeof(double) * 4 * n_track, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { fail("sim_create: device allocation failed"); tum_sim_free(s); return nullptr; }
-    return s;
-}
-
-// initial plant state (batch x 7) and controller state (batch x 8): X0_sim / X0_MPC of SimulationMode_main_class.py:60-75
-extern "C" int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *x_mpc, int cold_start)
-{
-    if (!s || !x_sim || !x_mpc) return fail("null argument");
-    tum_ocp *c = s->c; const size_t B = c->batch;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    invalidate(c, CH_X0 | CH_REF | CH_UPLOAD);
-    if (flush_inputs(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(s->dxsim, x_sim, sizeof(double) * B * 7, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->dx0, x_mpc, sizeof(double) * B * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy2D(s->dpose, 2 * 8, x_mpc, 8 * 8, 2 * 8, B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(s->dhist, 0, sizeof(double) * B * 32));
-    HIPCHK(hipMemset(s->dstep, 0, 2 * sizeof(int)));
-    if (s->seg && seg_zero(s)) return 1;
-    if (s->env && env_zero(s)) return 1;
-    HIPCHK(hipDeviceSynchronize());          // (the fills run on the NULL stream, the loop on the capsule's non-blocking one)
-    s->step = 0;
-    if (s->log_cap > 0) {
-        HIPCHK(hipMemcpy(s->lCiLX, x_sim, sizeof(double) * B * 7, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(s->lSimX, x_mpc, sizeof(double) * B * 8, hipMemcpyHostToDevice));
-    }
-    if (cold_start) return tum_ocp_cold_start(c);
-    return 0;
-}
-
-extern "C" int tum_sim_plan(tum_sim *s)
-{
-    if (!s) return fail("null argument");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    if (flush_inputs(c)) return 1;
-    invalidate(c, CH_REF);
-    hipLaunchKernelGGL(planner_kernel, dim3(c->batch), dim3(64), 0, c->stream, s->dtrack, s->n_track, s->dpose, 2, c->N + 1, s->Tp,
-                       s->loop_circuit, c->dyref, 6, s->dref0, s->dclosest, s->derr, c->batch, (int *)nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int tum_sim_advance(tum_sim *s)
-{
-    if (!s) return fail("null argument");
-    tum_ocp *c = s->c;
-    if (!c->solved) return fail("sim_advance: no solve yet");
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    invalidate(c, CH_ITERATE | CH_X0);          // (the plant re-initialises the iterate of an instance whose solve failed, and writes the next x0)
-    if (flush_inputs(c)) return 1;
-    SimArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.N = c->N; sa.batch = c->batch; sa.n_elem = s->n_elem; sa.step_counter = s->dstep; sa.log_cap = s->log_cap; sa.Ts = s->Ts;
-    for (int i = 0; i < 8; i++) sa.win[i] = s->win[i];
-    vehicle_constants(sa.pm, c->d);
-    sa.X = c->dX; sa.U = c->dU; sa.cost = c->dcost; sa.status = c->dstatus; sa.qp_iter = c->dqpiter;
-    sa.ns = c->sn ? c->sa.ns : 0; sa.XS = c->dXS; sa.xs0 = c->dxs0;
-    sa.bnd = c->dbnd; sa.r2 = c->r2 ? 1 : 0; sa.r2_dmin = c->r2_dmin; sa.r2_dmax = c->r2_dmax; sa.r2_uh = c->r2_uh;
-    sa.x_sim = s->dxsim; sa.x0 = c->dx0; sa.pose = s->dpose; sa.hist = s->dhist; sa.ref0 = s->dref0;
-    sa.lCiLX = s->lCiLX; sa.lSimX = s->lSimX; sa.lU = s->lU; sa.lREF = s->lREF; sa.lDBG = s->lDBG;
-    sa.dist_w = s->ddw; sa.dist_e = s->dde; sa.dist_len = s->dist_len;
-    sa.samples = s->env ? s->denv_samples : nullptr;
-    hipLaunchKernelGGL(plant_advance_kernel, dim3((c->batch * PLANT_LANES + 63) / 64), dim3(64), 0, c->stream, sa);
-    HIPCHK(hipGetLastError());
-    s->step++;
-    return 0;
-}
-
-// nsteps x (planner, SQP-RTI solve, plant + estimator) on the capsule's stream; returns after the last one. The loop is
-// launch-bound for small batches (3 short kernels per control step), so chunks of GRAPH_STEPS steps are captured once into
-// a hipGraph and replayed; all per-step state (step counter, ring buffers, logs) lives in device memory, so the captured
-// kernel arguments never change.
-static const int GRAPH_STEPS = 25;
-static int sim_enqueue_step_body(tum_sim *s, bool events);
-static void env_bind(tum_sim *s);
-static int sim_enqueue_step(tum_sim *s, bool events)
-{
-    // whatever goes wrong between the forked linearisation and the solve that consumes it (planner, join, a failed capture): the
-    // capsule must not keep the "linearisation already done" mark for a LATER solve, which would run on stale stage records
-    const int rc = sim_enqueue_step_body(s, events);
-    if (rc) s->c->lin_ahead = false;
-    return rc;
-}
-// scores the control step whose solve is on the stream and whose plant step is not yet (tum_sim_segments_attach)
-static int sim_enqueue_segment_score(tum_sim *s)
-{
-    tum_ocp *c = s->c;
-    SegArgs a;
-    memset(&a, 0, sizeof(a));
-    a.N = c->N; a.batch = c->batch; a.n_ggv = c->d.n_ggv;
-    a.X = c->dX; a.status = c->dstatus; a.x_sim = s->dxsim; a.ref0 = s->dref0; a.closest = s->dclosest;
-    a.end_idx = s->dseg_end; a.ggv = s->dseg_ggv;
-    a.acc_min = c->d.acc_min; a.max_lat_dev = s->seg_max_lat; a.max_a_comb = s->seg_max_acomb;
-    a.steps = s->dseg_steps; a.state = s->dseg_state; a.qp_failures = s->dseg_qpf;
-    a.max_abs_lat = s->dseg_lat; a.sumsq_vel = s->dseg_ssq; a.max_acomb = s->dseg_acomb;
-    hipLaunchKernelGGL(segment_score_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-static int sim_enqueue_step_body(tum_sim *s, bool events)
-{
-    tum_ocp *c = s->c;
-    if (lin_ahead_ok(c)) {
-        // fork: the linearisation of this step's solve on the side stream, behind everything the capsule's stream holds (the plant
-        // of the previous step may have re-initialised the iterate); the planner on the capsule's stream; join in front of the
-        // condensing kernel. Inside a stream capture this becomes two branches of the graph.
-        HIPCHK(hipEventRecord(s->evF, c->stream));
-        HIPCHK(hipStreamWaitEvent(s->s2, s->evF, 0));
-        launch_lin_ahead(c, s->s2);
-        HIPCHK(hipEventRecord(s->evJ, s->s2));
-        if (tum_sim_plan(s)) return 1;
-        HIPCHK(hipStreamWaitEvent(c->stream, s->evJ, 0));
-    } else if (tum_sim_plan(s)) return 1;
-    if (launch(c, events)) return 1;
-    if (s->seg && sim_enqueue_segment_score(s)) return 1;
-    if (s->env) {          // scores the control step whose solve is on the stream and whose plant step is not yet (tum_sim_env_attach)
-        env_bind(s);
-        hipLaunchKernelGGL(env_score_kernel, dim3(c->batch), dim3(64), 0, c->stream, s->ea);
-        HIPCHK(hipGetLastError());
-    }
-    return tum_sim_advance(s);
-}
-
-// the control steps of tum_sim_run on the capsule's stream, without the wait behind them
-static int sim_run_enqueue(tum_sim *s, int nsteps)
-{
-    tum_ocp *c = s->c;
-    if (c->nlp_type) return fail("sim_run: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
-    if (c->rti_phase) return fail("sim_run: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    invalidate(c, CH_ITERATE);          // (the closed loop keeps the general linearisation: its chunks are captured and replayed)
-    if (flush_inputs(c)) return 1;            // (pending host setters go up before anything is captured)
-    if (resolve_kernel(c)) return 1;          // (workspace allocation must not happen inside the capture below)
-    // ... nor the reallocation / synchronisation a changed SNMPC parameter vector can trigger, nor the deferred freeze
-    if (c->sn && (sn_apply_p(c) || sn_materialise(c))) return 1;
-    if (lin_ahead_ok(c) && !s->s2) {          // (created here: not inside the capture below)
-        HIPCHK(hipStreamCreateWithFlags(&s->s2, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&s->evF, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&s->evJ, hipEventDisableTiming));
-    }
-    int done = 0;
-    if (nsteps >= 2 * GRAPH_STEPS) {
-        // a captured chunk holds the kernel variant, the schedule flag, the SNMPC horizon / risk parameter / work-buffer
-        // pointers and the R2 attachment BY VALUE: after any of them changed the chunk is captured again
-        if (s->graph && (s->graph_epoch != c->epoch || s->graph_fanout != c->fanout)) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
-        if (!s->graph) {
-            s->graph_epoch = c->epoch; s->graph_fanout = c->fanout;
-            hipGraph_t g = nullptr;
-            const int step0 = s->step;
-            bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            c->capturing = ok;
-            if (ok) {
-                c->solved = true;                                      // the captured solve precedes every captured advance
-                for (int i = 0; i < GRAPH_STEPS && ok; i++) ok = sim_enqueue_step(s, false) == 0;
-                ok = (hipStreamEndCapture(c->stream, &g) == hipSuccess) && ok;
-                c->capturing = false;
-                s->step = step0;                                       // nothing ran yet
-            }
-            if (ok && g) ok = hipGraphInstantiate(&s->graph, g, nullptr, nullptr, 0) == hipSuccess;
-            if (g) (void)hipGraphDestroy(g);
-            if (!ok) { s->graph = nullptr; c->lin_ahead = false; (void)hipGetLastError(); }  // fall back to plain launches
-            s->graph_steps = GRAPH_STEPS;
-        }
-        while (s->graph && nsteps - done >= s->graph_steps) {
-            HIPCHK(hipGraphLaunch(s->graph, c->stream));
-            done += s->graph_steps; s->step += s->graph_steps;
-            if (solve_done(c, SOLVE_REPLAY, false)) return 1;
-        }
-    }
-    for (; done < nsteps; done++)
-        if (sim_enqueue_step(s, true)) return 1;
-    return 0;
-}
-
-extern "C" int tum_sim_run(tum_sim *s, int nsteps)
-{
-    if (!s || nsteps < 0) return fail("bad argument");
-    tum_ocp *c = s->c;
-    if (sim_run_enqueue(s, nsteps)) return 1;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int err = 0;
-    HIPCHK(hipMemcpy(&err, s->derr, sizeof(int), hipMemcpyDeviceToHost));
-    if (err) return fail("sim_run: planner segment longer than PLAN_MAXM points");
-    return 0;
-}
-
-extern "C" int tum_sim_steps(const tum_sim *s) { return s ? s->step : -1; }
-
-// Disturbance realisation of the loop (Utils/SimulationMode_main_class.py:121-143 with disturbance_playback, and what
-// Utils/MPC_sim_utils.py:54-67 generate_disturbances draws otherwise -- drawn on the host, closed_loop.DisturbanceModel): w_deriv
-// (additive on the state derivatives, constant over a control step) and e_est (additive state estimation error), n_steps x batch x 7
-// each (host, step-major), either may be null. Control step i >= n_steps runs undisturbed. n_steps = 0 removes the realisation.
-extern "C" int tum_sim_set_disturbances(tum_sim *s, const double *w_deriv, const double *e_est, int n_steps)
-{
-    if (!s || n_steps < 0) return fail("bad argument");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(s->ddw); (void)hipFree(s->dde); s->ddw = s->dde = nullptr; s->dist_len = 0;
-    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }          // (the pointers are kernel arguments of a captured chunk)
-    if (n_steps == 0 || (!w_deriv && !e_est)) return 0;
-    const size_t n = (size_t)n_steps * c->batch * 7;
-    if (w_deriv) { HIPCHK(hipMalloc((void **)&s->ddw, sizeof(double) * n)); HIPCHK(hipMemcpy(s->ddw, w_deriv, sizeof(double) * n, hipMemcpyHostToDevice)); }
-    if (e_est) { HIPCHK(hipMalloc((void **)&s->dde, sizeof(double) * n)); HIPCHK(hipMemcpy(s->dde, e_est, sizeof(double) * n, hipMemcpyHostToDevice)); }
-    s->dist_len = n_steps;
-    return 0;
-}
-
-// Track segments of a weight sweep (Learning_To_Adapt/SafeRL_WMPC/BO_WMPC/objective_function.py:57-200): instance b is scored every control
-// step until the planner's index equals end_idx[b] or a crash test fires; groups are contiguous runs of instances.
-extern "C" int tum_sim_segments_attach(tum_sim *s, const int *end_idx, const int *group_offsets, int n_groups, double max_lat_dev, double max_a_comb)
-{
-    if (!s) return fail("null argument");
-    tum_ocp *c = s->c; const int B = c->batch;
-    if (end_idx && s->env) return fail("segments_attach: this loop is an RL environment (tum_sim_env_attach): an instance is scored by one set of rules; detach the environment first");
-    if (end_idx) {
-        if (max_lat_dev != max_lat_dev || max_a_comb != max_a_comb) return fail("segments_attach: a threshold is NaN (an infinite one disables its crash test)");
-        if (group_offsets) {
-            if (n_groups < 1) return fail("segments_attach: n_groups < 1");
-            if (group_offsets[0] != 0 || group_offsets[n_groups] != B) return fail("segments_attach: group_offsets must start at 0 and end at batch");
-            for (int g = 0; g < n_groups; g++)
-                if (group_offsets[g + 1] <= group_offsets[g]) return fail("segments_attach: group_offsets must increase (no empty group)");
-        }
-    }
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }          // (a captured chunk holds the extra launch, or lacks it)
-    seg_release(s);
-    if (!end_idx) return 0;
-    std::vector<int> off;
-    if (group_offsets) off.assign(group_offsets, group_offsets + n_groups + 1);
-    else { n_groups = B; off.resize(B + 1); for (int i = 0; i <= B; i++) off[i] = i; }
-    double ggv[48];
-    for (int i = 0; i < 16; i++) { ggv[i] = c->d.ggv_v[i]; ggv[16 + i] = c->d.ggv_ax[i]; ggv[32 + i] = c->d.ggv_ay[i]; }
-    bool ok = true;
-    ok &= dalloc(&s->dseg_end, (size_t)B) == hipSuccess && dalloc(&s->dseg_off, (size_t)n_groups + 1) == hipSuccess;
-    ok &= dalloc(&s->dseg_steps, (size_t)B) == hipSuccess && dalloc(&s->dseg_state, (size_t)B) == hipSuccess && dalloc(&s->dseg_qpf, (size_t)B) == hipSuccess;
-    ok &= dalloc(&s->dseg_lat, (size_t)B) == hipSuccess && dalloc(&s->dseg_ssq, (size_t)B) == hipSuccess && dalloc(&s->dseg_acomb, (size_t)B) == hipSuccess;
-    ok &= dalloc(&s->dseg_ggv, (size_t)48) == hipSuccess && dalloc(&s->dseg_out, (size_t)4 * n_groups) == hipSuccess;
-    ok = ok && hipMemcpy(s->dseg_end, end_idx, sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(s->dseg_off, off.data(), sizeof(int) * (n_groups + 1), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(s->dseg_ggv, ggv, sizeof(ggv), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { seg_release(s); (void)hipGetLastError(); return fail("segments_attach: device allocation failed"); }
-    s->seg = true; s->seg_groups = n_groups; s->seg_max_lat = max_lat_dev; s->seg_max_acomb = max_a_comb;
-    return 0;
-}
-
-// segments whose state word is still 0 (the loop's stream is idle)
-static int seg_count_active(tum_sim *s, int *active)
-{
-    std::vector<int> st(s->c->batch);
-    HIPCHK(hipMemcpy(st.data(), s->dseg_state, sizeof(int) * st.size(), hipMemcpyDeviceToHost));
-    int n = 0;
-    for (int v : st) n += v == 0;
-    *active = n;
-    return 0;
-}
-
-// tum_sim_run in chunks of check_every control steps until no segment is active or max_steps have run. The reference's
-// `while not done and not crash` has no cap; segments still active at the end have timed out (neither done nor crashed).
-extern "C" int tum_sim_run_segments(tum_sim *s, int max_steps, int check_every)
-{
-    if (!s || max_steps < 0) return fail("bad argument");
-    if (!s->seg) return fail("sim_run_segments: no segments attached (tum_sim_segments_attach)");
-    if (check_every <= 0) check_every = 100;
-    DevGuard guard(s->c->d.device); GUARD_OK(guard);
-    for (int done = 0; done < max_steps;) {
-        const int n = std::min(check_every, max_steps - done);
-        if (tum_sim_run(s, n)) return 1;
-        done += n;
-        int active = 0;
-        if (seg_count_active(s, &active)) return 1;
-        if (active == 0) break;
-    }
-    return 0;
-}
-
-
-// ---------------------------------------------------------------------------------------------- K11: RL environment
-// what the environment cannot run on, at attach time and again at every step (a capsule can change behind an attached environment)
-static int env_refuse(const tum_sim *s, const char *who)
-{
-    const tum_ocp *c = s->c;
-    const std::string w(who);
-    if (c->sn) return fail(w + ": the RL environment runs the nominal OCP; this is a coupled SNMPC capsule");
-    if (c->r2) return fail(w + ": the RL environment runs the nominal OCP; this capsule has the R2 back-off attached (its reset restores bounds the environment does not know)");
-    if (c->dWf) return fail(w + ": the RL environment installs a diagonal W (update_cost_function_weights); this capsule keeps a full W");
-    if (c->nlp_type) return fail(w + ": the RL environment runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
-    if (c->rti_phase) return fail(w + ": the RL environment runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
-    if (c->kmode == KMode::FUSED || (c->ka.flags & KF_DEBUG)) return fail(w + ": the RL environment runs on the pipeline, not on the development kernel 'fused'");
-    if (s->seg) return fail(w + ": this loop has track segments attached (tum_sim_segments_attach): an instance is scored by one set of rules; detach them first");
-    return 0;
-}
-
-extern "C" int tum_sim_env_attach(tum_sim *s, const double *table, int n_actions, int n_mpc_steps, double max_lat_dev, int episode_length, int full_lap,
-                                  const double *sigmas, const double *lims, const double *obs_lo, const double *obs_hi,
-                                  const int *idx_v, const int *idx_yawrate, int n_samples, int obs_states)
-{
-    if (!s) return fail("null argument");
-    tum_ocp *c = s->c; const size_t B = c->batch; const int N = c->N;
-    if (table) {
-        if (!sigmas || !lims || !obs_lo || !obs_hi || !idx_v || !idx_yawrate) return fail("null argument");
-        if (env_refuse(s, "env_attach")) return 1;
-        if (n_actions < 1 || n_mpc_steps < 1 || episode_length < 1 || n_samples < 1) return fail("env_attach: n_actions, n_mpc_steps, episode_length and n_samples must be >= 1");
-        if (N < ENV_MA || N + 1 > ENV_MAXPTS) return fail("env_attach: the observation's 10-tap moving average of the yaw rate needs 10 <= N <= 127");
-        if (max_lat_dev != max_lat_dev) return fail("env_attach: max_lat_dev is NaN (an infinite one disables the crash test)");
-        if (obs_states != 0 && obs_states != 1) return fail("env_attach: obs_states must be 0 (reference) or 1 (last_step)");
-        for (int i = 0; i < 2; i++) {
-            if (!(sigmas[i] > 0.0)) return fail("env_attach: sigmas must be positive");
-            if (!(lims[2 + i] != lims[i])) return fail("env_attach: lims[1] must differ from lims[0]");
-        }
-        for (int i = 0; i < n_samples; i++) {
-            if (idx_v[i] < 0 || idx_v[i] > N) return fail("env_attach: a velocity sample index is outside 0..N");
-            if (idx_yawrate[i] < 0 || idx_yawrate[i] > N - ENV_MA) return fail("env_attach: a yaw rate sample index is outside 0..N-10");
-        }
-        for (int i = 0; i < 2 + 2 * n_samples; i++)
-            if (!(obs_hi[i] != obs_lo[i])) return fail("env_attach: an observation bound has no width");
-    }
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }          // (a captured chunk holds the extra launch and the sample counters, or lacks them)
-    env_release(s);
-    if (!table) return 0;
-    const int no = 2 + 2 * n_samples, rec = ENV_REC + no;
-    std::vector<double> bounds(2 * (size_t)no);
-    for (int i = 0; i < no; i++) { bounds[i] = obs_lo[i]; bounds[no + i] = obs_hi[i]; }
-    std::vector<int> idx(2 * (size_t)n_samples), samples(B, s->step);
-    for (int i = 0; i < n_samples; i++) { idx[i] = idx_v[i]; idx[n_samples + i] = idx_yawrate[i]; }
-    bool ok = true;
-    ok &= dalloc(&s->denv_table, (size_t)n_actions * 7) == hipSuccess && dalloc(&s->denv_bounds, bounds.size()) == hipSuccess;
-    ok &= dalloc(&s->denv_acc, B * 4) == hipSuccess && dalloc(&s->denv_win, B * 2 * (N + 1)) == hipSuccess && dalloc(&s->denv_out, B * rec) == hipSuccess;
-    ok &= dalloc(&s->denv_idx, idx.size()) == hipSuccess && dalloc(&s->denv_in, B * 3) == hipSuccess && dalloc(&s->denv_ep, B) == hipSuccess;
-    ok &= dalloc(&s->denv_count, B) == hipSuccess && dalloc(&s->denv_flags, B) == hipSuccess && dalloc(&s->denv_qpf, B) == hipSuccess && dalloc(&s->denv_samples, B) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&s->henv_out, sizeof(double) * B * rec, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&s->henv_in, sizeof(int) * B * 3, hipHostMallocDefault) == hipSuccess;
-    ok = ok && (s->env_ended = (unsigned char *)calloc(B, 1)) != nullptr;
-    ok = ok && hipMemcpy(s->denv_table, table, sizeof(double) * 7 * n_actions, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(s->denv_bounds, bounds.data(), sizeof(double) * bounds.size(), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(s->denv_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice) == hipSuccess;
-    // the estimator of every instance has seen as many samples as the loop has run control steps: attaching changes nothing the loop computes
-    ok = ok && hipMemcpy(s->denv_samples, samples.data(), sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { env_release(s); (void)hipGetLastError(); return fail("env_attach: allocation failed"); }
-    EnvArgs &a = s->ea;
-    memset(&a, 0, sizeof(a));
-    a.N = N; a.batch = c->batch; a.n_track = s->n_track; a.n_actions = n_actions; a.n_samples = n_samples; a.episode_length = episode_length;
-    a.full_lap = full_lap ? 1 : 0; a.obs_last_step = obs_states; a.log_cap = s->log_cap;
-    a.max_lat_dev = max_lat_dev; a.Ts = s->Ts;
-    for (int i = 0; i < 2; i++) a.sig[i] = sigmas[i];
-    for (int i = 0; i < 4; i++) a.lim[i] = lims[i];
-    a.track = s->dtrack; a.table = s->denv_table; a.in = s->denv_in; a.obs_idx = s->denv_idx; a.obs_bounds = s->denv_bounds;
-    a.x_sim = s->dxsim; a.pose = s->dpose; a.hist = s->dhist; a.ref0 = s->dref0; a.closest = s->dclosest; a.step_counter = s->dstep; a.err = s->derr;
-    a.lCiLX = s->lCiLX; a.lSimX = s->lSimX;
-    a.ep_steps = s->denv_ep; a.count = s->denv_count; a.flags = s->denv_flags; a.qpf = s->denv_qpf; a.samples = s->denv_samples;
-    a.acc = s->denv_acc; a.win = s->denv_win; a.out = s->denv_out;
-    s->env = true; s->env_mpc_steps = n_mpc_steps; s->env_rec = rec;
-    return 0;
-}
-
-// the capsule's arrays as they are NOW (tum_ocp_bind_device moves x0 / yref; a captured chunk is dropped with the epoch then)
-static void env_bind(tum_sim *s)
-{
-    tum_ocp *c = s->c; EnvArgs &a = s->ea;
-    a.X = c->dX; a.U = c->dU; a.x0 = c->dx0; a.W = c->dW; a.pen = c->dpen; a.qp_lam = c->dqplam; a.yref = c->dyref; a.status = c->dstatus;
-}
-
-// uploads actions | reset mask | start indices (any may be null: none) and runs the begin kernel; the caller holds the device guard
-static int env_begin(tum_sim *s, const int *actions, const int *reset_mask, const int *start_idx, const char *who)
-{
-    tum_ocp *c = s->c; const int B = c->batch;
-    const std::string w(who);
-    bool any_reset = false;
-    for (int b = 0; b < B; b++) {
-        const bool r = reset_mask && reset_mask[b] == 1, go_on = reset_mask && reset_mask[b] == 2;
-        if (reset_mask && !r && !go_on && reset_mask[b] != 0) return fail(w + ": a reset mask holds 0 (nothing), 1 (reset) or 2 (an ended episode drives on)");
-        if (r && (!start_idx || start_idx[b] < 0 || start_idx[b] >= s->n_track)) return fail(w + ": start index of instance " + std::to_string(b) + " is outside the track");
-        if (actions && (actions[b] < 0 || actions[b] >= s->ea.n_actions))
-            return fail(w + ": action " + std::to_string(actions[b]) + " of instance " + std::to_string(b) + " is outside the table of " + std::to_string(s->ea.n_actions) + " rows");
-        if (actions && s->env_ended[b] && !r && !go_on) return fail(w + ": the episode of instance " + std::to_string(b) + " has ended and it is not marked for reset");
-        any_reset |= r;
-    }
-    if (flush_inputs(c)) return 1;          // (older setters of x0 / yref in the pinned shadow go first: the begin kernel writes behind them)
-    for (int b = 0; b < B; b++) {
-        const bool r = reset_mask && reset_mask[b] == 1;
-        if (reset_mask && reset_mask[b] == 2) s->env_ended[b] = 0;
-        s->henv_in[b] = actions ? actions[b] : 0; s->henv_in[B + b] = r ? 1 : 0; s->henv_in[2 * B + b] = r ? start_idx[b] : 0;
-        if (r) s->env_ended[b] = 0;
-    }
-    HIPCHK(hipMemcpyAsync(s->denv_in, s->henv_in, sizeof(int) * 3 * B, hipMemcpyHostToDevice, c->stream));
-    // the begin kernel writes W, the penalties and -- of the instances it resets -- the iterate, x0 and the pose the planner reads. Never
-    // CH_RESTART: a partly reset batch is not stage-uniform
-    invalidate(c, (actions ? (CH_W | CH_BOUNDS) : 0u) | (any_reset ? (CH_ITERATE | CH_X0 | CH_REF) : 0u));
-    env_bind(s);
-    hipLaunchKernelGGL(env_begin_kernel, dim3(B), dim3(64), 0, c->stream, s->ea, actions ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int tum_sim_env_reset(tum_sim *s, const int *mask, const int *start_idx)
-{
-    if (!s || !start_idx) return fail("null argument");
-    if (!s->env) return fail("env_reset: no environment attached (tum_sim_env_attach)");
-    if (env_refuse(s, "env_reset")) return 1;
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    std::vector<int> all;
-    if (!mask) { all.assign(c->batch, 1); mask = all.data(); }
-    if (env_begin(s, nullptr, mask, start_idx, "env_reset")) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int tum_sim_env_step(tum_sim *s, const int *actions, const int *reset_mask, const int *start_idx, double *out)
-{
-    if (!s || !actions || !out) return fail("null argument");
-    if (!s->env) return fail("env_step: no environment attached (tum_sim_env_attach)");
-    if (env_refuse(s, "env_step")) return 1;
-    tum_ocp *c = s->c; const size_t B = c->batch;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    if (env_begin(s, actions, reset_mask, start_idx, "env_step")) return 1;
-    if (sim_run_enqueue(s, s->env_mpc_steps)) return 1;
-    env_bind(s);
-    hipLaunchKernelGGL(env_finish_kernel, dim3(c->batch), dim3(64), 0, c->stream, s->ea);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->henv_out, s->denv_out, sizeof(double) * B * s->env_rec, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (s->henv_out[5] != 0.0) return fail("env_step: planner segment longer than PLAN_MAXM points");
-    memcpy(out, s->henv_out, sizeof(double) * B * s->env_rec);
-    for (size_t b = 0; b < B; b++)
-        if (out[b * s->env_rec + 1] != 0.0 || out[b * s->env_rec + 2] != 0.0) s->env_ended[b] = 1;
-    return lin_uniform_check(c);
-}
-
-// ---------------------------------------------------------------------------------------------- K12: the agent, whole episodes
-// The policy net of the reference's agent (a stable_baselines3 MlpPolicy with tanh activations; inference only: model.predict(obs,
-// deterministic=True) and helpers.py:100-105 get_action_probabilities) in the layout policy_kernel reads. widths[n_layers + 1]: inputs,
-// hidden widths..., actions; W[l] row-major (out, in) as torch stores it. W == NULL detaches. On a loop with an environment the widths
-// must fit it; on one without, the policy serves tum_sim_policy_eval alone (attaching an environment detaches it). Nothing a captured
-// chunk of control steps holds changes: the policy runs outside sim_run_enqueue.
-// a net in the layout policy_layers reads, on the device; false where an allocation or a copy failed (the caller releases)
-static bool net_upload(PolicyArgs &a, int n_layers, const int *widths, const float *const *W, const float *const *b, double **dW, double **db)
-{
-    memset(&a, 0, sizeof(a));
-    a.n_mat = n_layers; a.n_in = widths[0]; a.n_act = widths[n_layers];
-    bool ok = true;
-    for (int l = 0; l < n_layers && ok; l++) {
-        const int in = widths[l], out = widths[l + 1], kp = (in + 3) & ~3, mp = (out + 15) & ~15;
-        a.kp[l] = kp; a.mp[l] = mp; a.rows = std::max(a.rows, std::max(kp, mp));
-        // float -> double is exact; the A operand of product (t, q) is 64 consecutive doubles: lane holds W[16 t + (lane & 15)][4 q + (lane >> 4)]
-        std::vector<double> Wp((size_t)mp * kp, 0.0), bp(mp, 0.0);
-        for (int t = 0; t < mp / 16; t++)
-            for (int q = 0; q < kp / 4; q++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int r = 16 * t + (lane & 15), k = 4 * q + (lane >> 4);
-                    if (r < out && k < in) Wp[((size_t)t * (kp / 4) + q) * 64 + lane] = (double)W[l][(size_t)r * in + k];
-                }
-        for (int r = 0; r < out; r++) bp[r] = (double)b[l][r];
-        ok = ok && dalloc(&dW[l], Wp.size()) == hipSuccess && dalloc(&db[l], bp.size()) == hipSuccess;
-        ok = ok && hipMemcpy(dW[l], Wp.data(), sizeof(double) * Wp.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(db[l], bp.data(), sizeof(double) * bp.size(), hipMemcpyHostToDevice) == hipSuccess;
-        a.W[l] = dW[l]; a.b[l] = db[l];
-    }
-    return ok;
-}
-
-extern "C" int tum_sim_policy_attach(tum_sim *s, int n_layers, const int *widths, const float *const *W, const float *const *b)
-{
-    if (!s) return fail("null argument");
-    tum_ocp *c = s->c;
-    if (W) {
-        if (!widths || !b) return fail("null argument");
-        if (n_layers < 2 || n_layers > POL_MAXMAT) return fail("policy_attach: 1 to 4 hidden layers (n_layers 2..5 with the action layer)");
-        for (int l = 0; l < n_layers; l++) if (!W[l] || !b[l]) return fail("null argument");
-        if (widths[0] < 1 || widths[0] > POL_MAXIN) return fail("policy_attach: 1 to 128 inputs");
-        for (int l = 1; l < n_layers; l++)
-            if (widths[l] < 1 || widths[l] > POL_MAXWIDTH) return fail("policy_attach: hidden layers are 1 to 256 wide");
-        if (widths[n_layers] < 1 || widths[n_layers] > POL_MAXACT) return fail("policy_attach: 1 to 64 actions");
-        // without an environment the policy serves tum_sim_policy_eval alone; with one it reads its observation and picks rows of its table
-        if (s->env && widths[0] != s->env_rec - ENV_REC)
-            return fail("policy_attach: the policy takes " + std::to_string(widths[0]) + " inputs, the environment's observation has " + std::to_string(s->env_rec - ENV_REC) + " entries");
-        if (s->env && widths[n_layers] != s->ea.n_actions)
-            return fail("policy_attach: the policy has " + std::to_string(widths[n_layers]) + " actions, the environment's table has " + std::to_string(s->ea.n_actions) + " rows");
-    }
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    policy_release(s);
-    if (!W) return 0;
-    PolicyArgs &a = s->pa;
-    const size_t B = c->batch;
-    bool ok = net_upload(a, n_layers, widths, W, b, s->dpol_W, s->dpol_b);
-    for (int l = 0; l <= n_layers; l++) s->pol_widths[l] = widths[l];
-    ok = ok && dalloc(&s->dpol_obs, B * a.n_in) == hipSuccess && dalloc(&s->dpol_live, B) == hipSuccess && dalloc(&s->dpol_nlive, (size_t)1) == hipSuccess;
-    ok = ok && hipFuncSetAttribute((const void *)policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
-    ok = ok && hipFuncSetAttribute((const void *)policy_ac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
-    ok = ok && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { policy_release(s); (void)hipGetLastError(); return fail("policy_attach: allocation failed"); }
-    s->pol = true;
-    return 0;
-}
-
-// one launch of the policy on the capsule's stream: n instances, observations [n][stride] on the device
-static int policy_launch(tum_sim *s, const double *dobs, int stride, int n, double *dlogits, double *dprobs, int *dactions)
-{
-    PolicyArgs a = s->pa;
-    a.n = n; a.obs = dobs; a.obs_stride = stride; a.logits = dlogits; a.probs = dprobs; a.actions = dactions;
-    hipLaunchKernelGGL(policy_kernel, dim3((n + POL_TILE - 1) / POL_TILE), dim3(64 * POL_WAVES), sizeof(double) * 2 * a.rows * POL_TILE, s->c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// the policy alone on n host observations (n x widths[0]), independent of the loop's batch: logits and probabilities n x actions, actions n
-extern "C" int tum_sim_policy_eval(tum_sim *s, const double *obs, int n, double *logits, double *probs, int *actions)
-{
-    if (!s || !obs) return fail("null argument");
-    if (!s->pol) return fail("policy_eval: no policy attached (tum_sim_policy_attach)");
-    if (n < 1) return fail("policy_eval: n < 1");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    const size_t ni = (size_t)n * s->pa.n_in, na = (size_t)n * s->pa.n_act;
-    DevTmp to, tl, tp, ta;
-    HIPCHK(to.alloc(sizeof(double) * ni)); HIPCHK(tl.alloc(sizeof(double) * na)); HIPCHK(tp.alloc(sizeof(double) * na)); HIPCHK(ta.alloc(sizeof(int) * n));
-    HIPCHK(hipMemcpy(to.as<double>(), obs, sizeof(double) * ni, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    if (policy_launch(s, to.as<double>(), s->pa.n_in, n, logits ? tl.as<double>() : nullptr, probs ? tp.as<double>() : nullptr, actions ? ta.as<int>() : nullptr)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (logits) HIPCHK(hipMemcpy(logits, tl.as<double>(), sizeof(double) * na, hipMemcpyDeviceToHost));
-    if (probs) HIPCHK(hipMemcpy(probs, tp.as<double>(), sizeof(double) * na, hipMemcpyDeviceToHost));
-    if (actions) HIPCHK(hipMemcpy(actions, ta.as<int>(), sizeof(int) * n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// n_env_steps x (policy, begin, n_mpc_steps control steps, finish, next) on the capsule's stream without a host wait in between; one
-// download behind the last step (and the 4-byte counter of live instances every check_every steps where asked for).
-//   first_obs (B x n_obs, NULL: zeros -- what a reset returns) is what the policy sees first.
-//   on_end 0: an instance whose episode ends is frozen out: it drives on as with reset mask 2 of tum_sim_env_step, live = 0 from the
-//             next step on and its later rows are not results. An instance whose episode had ended BEFORE the call starts with live = 0.
-//   on_end 1: it is reset at the start of step e + 1 to start_table[e + 1][b] and the policy sees zeros for it; an instance whose
-//             episode had ended before the call is reset to start_table[0][b] at step 0. start_table: n_env_steps x B.
-// The host does not know which instances the begin kernel resets: every step invalidates as if any had been. env_ended[] afterwards:
-// the flags of the last step that ran, which is what tum_sim_env_step leaves when an ended instance drives on.
-extern "C" int tum_sim_env_rollout(tum_sim *s, int n_env_steps, const double *first_obs, int on_end, const int *start_table,
-                                   int check_every, double *out, int *actions_out, int *live_out, int *steps_run)
-{
-    if (!s || !out || !actions_out || !live_out || !steps_run) return fail("null argument");
-    if (!s->env) return fail("env_rollout: no environment attached (tum_sim_env_attach)");
-    if (env_refuse(s, "env_rollout")) return 1;
-    if (!s->pol) return fail("env_rollout: no policy attached (tum_sim_policy_attach)");
-    if (n_env_steps < 1) return fail("env_rollout: n_env_steps < 1");
-    if (on_end != 0 && on_end != 1) return fail("env_rollout: on_end is 0 (an ended instance is frozen out) or 1 (it is reset)");
-    if (on_end == 1 && !start_table) return fail("env_rollout: on_end 1 resets ended instances and needs a start table (n_env_steps x batch)");
-    tum_ocp *c = s->c; const size_t B = c->batch, E = n_env_steps, rec = s->env_rec; const int no = s->pa.n_in;
-    if (start_table)
-        for (size_t i = 0; i < E * B; i++)
-            if (start_table[i] < 0 || start_table[i] >= s->n_track)
-                return fail("env_rollout: start index of instance " + std::to_string(i % B) + " at step " + std::to_string(i / B) + " is outside the track");
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    if (flush_inputs(c)) return 1;          // (older setters of x0 / yref in the pinned shadow go first: the begin kernel writes behind them)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (E > s->roll_cap) {
-        (void)hipFree(s->droll_log); (void)hipFree(s->droll_ints); s->droll_log = nullptr; s->droll_ints = nullptr; s->roll_cap = 0;
-        if (dalloc(&s->droll_log, E * B * rec) != hipSuccess || dalloc(&s->droll_ints, 3 * E * B) != hipSuccess) { (void)hipGetLastError(); return fail("env_rollout: allocation failed"); }
-        s->roll_cap = E;
-    }
-    int *dact = s->droll_ints, *dlive = dact + E * B, *dtab = dlive + E * B;
-    // step 0: what the host knows -- the episodes that have ended, the first observation
-    std::vector<double> obs0(B * no, 0.0);
-    std::vector<int> live0(B, 1);
-    int n_live = 0;
-    for (size_t b = 0; b < B; b++) {
-        const bool r = on_end == 1 && s->env_ended[b];
-        s->henv_in[b] = 0; s->henv_in[B + b] = r ? 1 : 0; s->henv_in[2 * B + b] = r ? start_table[b] : 0;
-        if (first_obs && !r) memcpy(&obs0[b * no], first_obs + b * no, sizeof(double) * no);
-        if (on_end == 0 && s->env_ended[b]) live0[b] = 0;
-        n_live += live0[b];
-    }
-    HIPCHK(hipMemcpy(s->denv_in, s->henv_in, sizeof(int) * 3 * B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->dpol_obs, obs0.data(), sizeof(double) * B * no, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->dpol_live, live0.data(), sizeof(int) * B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->dpol_nlive, &n_live, sizeof(int), hipMemcpyHostToDevice));
-    if (start_table) HIPCHK(hipMemcpy(dtab, start_table, sizeof(int) * E * B, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    RolloutArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.batch = (int)B; ra.rec = (int)rec; ra.head = ENV_REC; ra.n_obs = no; ra.n_env_steps = n_env_steps; ra.on_end = on_end;
-    ra.out = s->denv_out; ra.in = s->denv_in; ra.start_table = start_table ? dtab : nullptr; ra.pol_obs = s->dpol_obs;
-    ra.live = s->dpol_live; ra.n_live = s->dpol_nlive; ra.log = s->droll_log; ra.act_log = dact; ra.live_log = dlive;
-    int ran = 0;
-    *steps_run = 0;
-    if (!(check_every > 0 && n_live == 0))
-        for (int e = 0; e < n_env_steps; e++) {
-            if (policy_launch(s, s->dpol_obs, no, (int)B, nullptr, nullptr, s->denv_in)) return 1;
-            // the begin kernel writes W and the penalties, and -- of the instances the DEVICE marked -- the iterate, x0 and the pose. Never
-            // CH_RESTART: a partly reset batch is not stage-uniform
-            invalidate(c, CH_W | CH_BOUNDS | CH_ITERATE | CH_X0 | CH_REF);
-            env_bind(s);
-            hipLaunchKernelGGL(env_begin_kernel, dim3(B), dim3(64), 0, c->stream, s->ea, 1);
-            HIPCHK(hipGetLastError());
-            if (sim_run_enqueue(s, s->env_mpc_steps)) return 1;
-            env_bind(s);
-            hipLaunchKernelGGL(env_finish_kernel, dim3(B), dim3(64), 0, c->stream, s->ea);
-            HIPCHK(hipGetLastError());
-            ra.e = e;
-            hipLaunchKernelGGL(rollout_next_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, ra);
-            HIPCHK(hipGetLastError());
-            ran = e + 1;
-            if (check_every > 0 && ran % check_every == 0 && ran < n_env_steps) {
-                int nl = 0;
-                HIPCHK(hipStreamSynchronize(c->stream));
-                HIPCHK(hipMemcpy(&nl, s->dpol_nlive, sizeof(int), hipMemcpyDeviceToHost));
-                if (nl == 0) break;
-            }
-        }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *steps_run = ran;
-    if (ran == 0) return 0;
-    HIPCHK(hipMemcpy(out, s->droll_log, sizeof(double) * ran * B * rec, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(actions_out, dact, sizeof(int) * ran * B, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(live_out, dlive, sizeof(int) * ran * B, hipMemcpyDeviceToHost));
-    const double *last = out + (size_t)(ran - 1) * B * rec;
-    for (size_t b = 0; b < B; b++) s->env_ended[b] = (last[b * rec + 1] != 0.0 || last[b * rec + 2] != 0.0) ? 1 : 0;
-    for (int e = 0; e < ran; e++)
-        if (out[(size_t)e * B * rec + 5] != 0.0) return fail("env_rollout: planner segment longer than PLAN_MAXM points");
-    return lin_uniform_check(c);
-}
-
-
-// ---------------------------------------------------------------------------------------------- K13: collecting PPO training rollouts
-// The value net of the agent (mlp_extractor.value_net.<i>, value_net of a stable_baselines3 MlpPolicy) beside the attached policy:
-// widths[n_layers + 1] = inputs, hidden widths..., 1; the inputs are the policy's. W == NULL detaches. Detaching or re-attaching the
-// policy or the environment detaches it.
-extern "C" int tum_sim_policy_attach_value(tum_sim *s, int n_layers, const int *widths, const float *const *W, const float *const *b)
-{
-    if (!s) return fail("null argument");
-    tum_ocp *c = s->c;
-    if (W) {
-        if (!widths || !b) return fail("null argument");
-        if (!s->pol) return fail("policy_attach_value: no policy attached (tum_sim_policy_attach): the value net takes the policy's inputs");
-        if (n_layers < 2 || n_layers > POL_MAXMAT) return fail("policy_attach_value: 1 to 4 hidden layers (n_layers 2..5 with the value layer)");
-        for (int l = 0; l < n_layers; l++) if (!W[l] || !b[l]) return fail("null argument");
-        if (widths[0] != s->pa.n_in)
-            return fail("policy_attach_value: the value net takes " + std::to_string(widths[0]) + " inputs, the policy " + std::to_string(s->pa.n_in));
-        for (int l = 1; l < n_layers; l++)
-            if (widths[l] < 1 || widths[l] > POL_MAXWIDTH) return fail("policy_attach_value: hidden layers are 1 to 256 wide");
-        if (widths[n_layers] != 1) return fail("policy_attach_value: the last matrix of a value net has one row");
-    }
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    value_release(s);
-    if (!W) return 0;
-    const size_t B = c->batch;
-    bool ok = net_upload(s->va, n_layers, widths, W, b, s->dval_W, s->dval_b);
-    for (int l = 0; l <= n_layers; l++) s->val_widths[l] = widths[l];
-    ok = ok && dalloc(&s->dval_term, B) == hipSuccess && dalloc(&s->dval_starts, B) == hipSuccess;
-    ok = ok && hipFuncSetAttribute((const void *)policy_ac_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
-    ok = ok && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { value_release(s); (void)hipGetLastError(); return fail("policy_attach_value: allocation failed"); }
-    return 0;
-}
-
-// one launch of the actor-critic evaluation on the capsule's stream: n instances, observations [n][stride] on the device. do_pi 0: the
-// value net alone. with_value 0: the policy net alone (dvalues must be null then)
-static int ac_launch(tum_sim *s, const double *dobs, int stride, int n, int do_pi, bool with_value, unsigned long long seed, unsigned long long t,
-                     unsigned first, int *dactions, double *dvalues, double *dlogp, double *du)
-{
-    AcArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pi = s->pa;
-    if (with_value) a.vf = s->va;
-    a.pi.n = a.vf.n = n; a.pi.obs = a.vf.obs = dobs; a.pi.obs_stride = a.vf.obs_stride = stride;
-    a.pi.logits = a.pi.probs = nullptr; a.pi.actions = dactions;
-    a.rows = std::max(do_pi ? s->pa.rows : 0, with_value ? s->va.rows : 0);
-    a.do_pi = do_pi; a.seed = seed; a.t = t; a.first = first;
-    a.values = dvalues; a.log_probs = dlogp; a.uniforms = du;
-    hipLaunchKernelGGL(policy_ac_kernel, dim3((n + POL_TILE - 1) / POL_TILE), dim3(64 * POL_WAVES), sizeof(double) * 2 * a.rows * POL_TILE, s->c->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// the two nets and one draw on n host observations (n x widths[0]), independent of the loop's batch; instance i draws with counter word
-// first_instance + i at decision t. Any output may be NULL; values needs the value net, the others do not.
-extern "C" int tum_sim_policy_eval_ac(tum_sim *s, const double *obs, int n, unsigned long long seed, unsigned long long t, unsigned first_instance,
-                                      int *actions, double *values, double *log_probs, double *uniforms)
-{
-    if (!s || !obs) return fail("null argument");
-    if (!s->pol) return fail("policy_eval_ac: no policy attached (tum_sim_policy_attach)");
-    if (values && s->va.n_mat == 0) return fail("policy_eval_ac: values asked for and no value net attached (tum_sim_policy_attach_value)");
-    if (n < 1) return fail("policy_eval_ac: n < 1");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    const size_t ni = (size_t)n * s->pa.n_in;
-    DevTmp to, td, ta;
-    HIPCHK(to.alloc(sizeof(double) * ni)); HIPCHK(td.alloc(sizeof(double) * 3 * n)); HIPCHK(ta.alloc(sizeof(int) * n));
-    double *dv = td.as<double>(), *dl = dv + n, *du = dl + n;
-    HIPCHK(hipMemcpy(to.as<double>(), obs, sizeof(double) * ni, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    const int do_pi = (actions || log_probs || uniforms) ? 1 : 0;
-    if (!do_pi && !values) return 0;
-    if (ac_launch(s, to.as<double>(), s->pa.n_in, n, do_pi, values != nullptr, seed, t, first_instance, actions ? ta.as<int>() : nullptr,
-                  values ? dv : nullptr, log_probs ? dl : nullptr, uniforms ? du : nullptr)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (actions) HIPCHK(hipMemcpy(actions, ta.as<int>(), sizeof(int) * n, hipMemcpyDeviceToHost));
-    if (values) HIPCHK(hipMemcpy(values, dv, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (log_probs) HIPCHK(hipMemcpy(log_probs, dl, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (uniforms) HIPCHK(hipMemcpy(uniforms, du, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// generalised advantage estimation alone, on host arrays: rewards, values, episode_starts E x B, last_values and last_dones B -> adv, ret E x B
-extern "C" int tum_sim_gae(tum_sim *s, int E, int B, const double *rewards, const double *values, const double *episode_starts,
-                           const double *last_values, const double *last_dones, double gamma, double lambda, double *adv, double *ret)
-{
-    if (!s || !rewards || !values || !episode_starts || !last_values || !last_dones || !adv || !ret) return fail("null argument");
-    if (E < 1 || B < 1) return fail("gae: E and B must be >= 1");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    const size_t EB = (size_t)E * B;
-    DevTmp tb;
-    HIPCHK(tb.alloc(sizeof(double) * (5 * EB + 2 * B)));
-    double *d = tb.as<double>();
-    HIPCHK(hipMemcpy(d, rewards, sizeof(double) * EB, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + EB, values, sizeof(double) * EB, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + 2 * EB, episode_starts, sizeof(double) * EB, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + 5 * EB, last_values, sizeof(double) * B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + 5 * EB + B, last_dones, sizeof(double) * B, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    GaeArgs g;
-    g.E = E; g.B = B; g.gamma = gamma; g.lambda = lambda;
-    g.rewards = d; g.values = d + EB; g.episode_starts = d + 2 * EB; g.last_values = d + 5 * EB; g.last_dones = d + 5 * EB + B;
-    g.adv = d + 3 * EB; g.ret = d + 4 * EB;
-    hipLaunchKernelGGL(gae_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, g);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(adv, g.adv, sizeof(double) * EB, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ret, g.ret, sizeof(double) * EB, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// tum_sim_env_rollout with on_end 1, SAMPLED actions and the record of a stable_baselines3 RolloutBuffer: per step the actor-critic
-// evaluation (decision counter t0 + e), begin, n_mpc_steps control steps, finish, the value net on the step's own observation, the record;
-// behind the last step the value net on what the policy would see next (last_values) and gae_kernel. One wait, one download.
-//   first_obs (B x n_obs, NULL: zeros), first_episode_starts (B, NULL: ones): what the policy sees first, and whether that begins an episode
-//   out: TUM_COLLECT_FIELDS fields of E x B doubles each (TUM_COLLECT_* in tum_nmpc.h), the observations E x B x n_obs, last_values B,
-//        last_dones B, and what the policy would see next B x n_obs (the first_obs of a following call)
-extern "C" int tum_sim_env_collect(tum_sim *s, int n_env_steps, const double *first_obs, const double *first_episode_starts, const int *start_table,
-                                   unsigned long long seed, unsigned long long t0, double gamma, double gae_lambda, double *out)
-{
-    if (!s || !out) return fail("null argument");
-    if (!s->env) return fail("env_collect: no environment attached (tum_sim_env_attach)");
-    if (env_refuse(s, "env_collect")) return 1;
-    if (!s->pol) return fail("env_collect: no policy attached (tum_sim_policy_attach)");
-    if (s->va.n_mat == 0) return fail("env_collect: no value net attached (tum_sim_policy_attach_value)");
-    if (n_env_steps < 1) return fail("env_collect: n_env_steps < 1");
-    if (!start_table) return fail("env_collect: ended instances are reset and need a start table (n_env_steps x batch)");
-    tum_ocp *c = s->c; const size_t B = c->batch, E = n_env_steps, EB = E * B, rec = s->env_rec; const int no = s->pa.n_in;
-    for (size_t i = 0; i < EB; i++)
-        if (start_table[i] < 0 || start_table[i] >= s->n_track)
-            return fail("env_collect: start index of instance " + std::to_string(i % B) + " at step " + std::to_string(i / B) + " is outside the track");
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    if (flush_inputs(c)) return 1;          // (older setters of x0 / yref in the pinned shadow go first: the begin kernel writes behind them)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const size_t total = EB * (COL_FIELDS + no) + 2 * B + B * no;
-    s->col_rows = 0;          // (what tum_sim_ppo_update may train on: set behind a collection that ran to its end)
-    if (E > s->col_cap) {
-        (void)hipFree(s->dcol); (void)hipFree(s->dcol_tab); s->dcol = nullptr; s->dcol_tab = nullptr; s->col_cap = 0;
-        if (dalloc(&s->dcol, total) != hipSuccess || dalloc(&s->dcol_tab, EB) != hipSuccess) { (void)hipGetLastError(); return fail("env_collect: allocation failed"); }
-        s->col_cap = E;
-    }
-    // step 0: what the host knows -- the episodes that have ended, the first observation and its episode-start flags
-    std::vector<double> obs0(B * no, 0.0), st0(B, 1.0);
-    for (size_t b = 0; b < B; b++) {
-        const bool r = s->env_ended[b];
-        s->henv_in[b] = 0; s->henv_in[B + b] = r ? 1 : 0; s->henv_in[2 * B + b] = r ? start_table[b] : 0;
-        if (first_obs && !r) memcpy(&obs0[b * no], first_obs + b * no, sizeof(double) * no);
-        if (first_episode_starts) st0[b] = first_episode_starts[b] != 0.0 ? 1.0 : 0.0;
-    }
-    HIPCHK(hipMemcpy(s->denv_in, s->henv_in, sizeof(int) * 3 * B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->dpol_obs, obs0.data(), sizeof(double) * B * no, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->dval_starts, st0.data(), sizeof(double) * B, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->dcol_tab, start_table, sizeof(int) * EB, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    double *buf = s->dcol;
-    CollectArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.batch = (int)B; ca.rec = (int)rec; ca.head = ENV_REC; ca.n_obs = no; ca.n_env_steps = n_env_steps; ca.gamma = gamma;
-    ca.out = s->denv_out; ca.in = s->denv_in; ca.start_table = s->dcol_tab; ca.pol_obs = s->dpol_obs; ca.term_val = s->dval_term;
-    ca.first_starts = s->dval_starts; ca.buf = buf;
-    for (int e = 0; e < n_env_steps; e++) {
-        if (ac_launch(s, s->dpol_obs, no, (int)B, 1, true, seed, t0 + (unsigned long long)e, 0u, s->denv_in,
-                      buf + COL_VALUE * EB + e * B, buf + COL_LOGP * EB + e * B, nullptr)) return 1;
-        // as in tum_sim_env_rollout: the host does not know which instances the begin kernel resets
-        invalidate(c, CH_W | CH_BOUNDS | CH_ITERATE | CH_X0 | CH_REF);
-        env_bind(s);
-        hipLaunchKernelGGL(env_begin_kernel, dim3(B), dim3(64), 0, c->stream, s->ea, 1);
-        HIPCHK(hipGetLastError());
-        if (sim_run_enqueue(s, s->env_mpc_steps)) return 1;
-        env_bind(s);
-        hipLaunchKernelGGL(env_finish_kernel, dim3(B), dim3(64), 0, c->stream, s->ea);
-        HIPCHK(hipGetLastError());
-        // the value of the step's own observation: the bootstrap of an instance that crashed, and -- to the bit -- the next step's value of one that goes on
-        if (ac_launch(s, s->denv_out + ENV_REC, (int)rec, (int)B, 0, true, 0ull, 0ull, 0u, nullptr, s->dval_term, nullptr, nullptr)) return 1;
-        ca.e = e;
-        hipLaunchKernelGGL(collect_next_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, ca);
-        HIPCHK(hipGetLastError());
-    }
-    double *last_values = buf + EB * (COL_FIELDS + no), *last_dones = last_values + B;
-    if (ac_launch(s, s->dpol_obs, no, (int)B, 0, true, 0ull, 0ull, 0u, nullptr, last_values, nullptr, nullptr)) return 1;
-    GaeArgs g;
-    g.E = n_env_steps; g.B = (int)B; g.gamma = gamma; g.lambda = gae_lambda;
-    g.rewards = buf + COL_REWARD * EB; g.values = buf + COL_VALUE * EB; g.episode_starts = buf + COL_START * EB;
-    g.last_values = last_values; g.last_dones = last_dones; g.adv = buf + COL_ADV * EB; g.ret = buf + COL_RET * EB;
-    hipLaunchKernelGGL(gae_kernel, dim3((B + 63) / 64), dim3(64), 0, c->stream, g);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out, buf, sizeof(double) * total, hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < B; b++) s->env_ended[b] = out[EB * (COL_FIELDS + no) + B + b] != 0.0 ? 1 : 0;
-    for (int e = 0; e < n_env_steps; e++)
-        if (out[COL_ERR * EB + (size_t)e * B] != 0.0) return fail("env_collect: planner segment longer than PLAN_MAXM points");
-    s->col_rows = EB;
-    return lin_uniform_check(c);
-}
-
-
-// ---------------------------------------------------------------------------------------------- K14: the PPO update
-// the training view of one attached net: widths, strides and offsets in the flat parameter vector; the transposed matrices are allocated
-// here (zero: the padding stays zero) and filled by ppo_adam_kernel
-static bool ppo_net(PpoNet &t, const PolicyArgs &a, const int *widths, double *const *dW, double *const *db, int *P)
-{
-    memset(&t, 0, sizeof(t));
-    t.n_mat = a.n_mat;
-    int off = 0;
-    bool ok = true;
-    for (int l = 0; l < a.n_mat && ok; l++) {
-        t.in[l] = widths[l]; t.out[l] = widths[l + 1]; t.kp[l] = a.kp[l]; t.mp[l] = a.mp[l];
-        t.hs[l] = (widths[l] + 15) & ~15; t.kt[l] = (widths[l + 1] + 3) & ~3;
-        t.off[l] = off; off += widths[l + 1] * widths[l] + widths[l + 1];
-        t.W[l] = dW[l]; t.b[l] = db[l];
-        if (l > 0) ok = dalloc(&t.WT[l], (size_t)t.hs[l] * t.kt[l]) == hipSuccess;
-    }
-    *P = off;
-    return ok;
-}
-
-static void ppo_adam_args(tum_sim *s, PpoAdamArgs &a, int mode)
-{
-    memset(&a, 0, sizeof(a));
-    a.net[0] = s->tp; a.net[1] = s->tv; a.goff[0] = 0; a.goff[1] = s->tp.off[s->tp.n_mat - 1] + (s->tp.in[s->tp.n_mat - 1] + 1) * s->tp.out[s->tp.n_mat - 1];
-    a.P = s->ppo_P; a.n_parts = s->ppo_parts; a.mode = mode;
-    a.G = s->dppo_G; a.parts = s->dppo_part; a.theta = s->dppo_theta; a.m = s->dppo_m; a.v = s->dppo_v;
-    a.max_grad_norm = s->ppo_max_norm; a.beta1 = 0.9; a.beta2 = 0.999; a.eps = 1e-5; a.step = 0.0; a.bc2_sqrt = 1.0;
-}
-
-extern "C" int tum_sim_ppo_detach(tum_sim *s)
-{
-    if (!s) return fail("null argument");
-    DevGuard guard(s->c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(s->c->stream));
-    ppo_release(s);
-    return 0;
-}
-
-// The trainer on the attached nets: settings of stable_baselines3's PPO (rl_training.py:133-155), Adam's moments and step counter at
-// zero. The float32 master is read back from the packed policy and value nets -- their entries ARE float32 values -- so what is trained
-// is exactly what acts.
-extern "C" int tum_sim_ppo_attach(tum_sim *s, double clip_range, double ent_coef, double vf_coef, double max_grad_norm, int normalize_advantage)
-{
-    if (!s) return fail("null argument");
-    if (!s->pol) return fail("ppo_attach: no policy attached (tum_sim_policy_attach)");
-    if (s->va.n_mat == 0) return fail("ppo_attach: no value net attached (tum_sim_policy_attach_value)");
-    if (!(clip_range > 0.0) || !(max_grad_norm > 0.0)) return fail("ppo_attach: clip_range and max_grad_norm must be > 0");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    ppo_release(s);
-    int Pp = 0, Pv = 0;
-    bool ok = ppo_net(s->tp, s->pa, s->pol_widths, s->dpol_W, s->dpol_b, &Pp) && ppo_net(s->tv, s->va, s->val_widths, s->dval_W, s->dval_b, &Pv);
-    const size_t P = (size_t)Pp + Pv;
-    s->ppo_P = (int)P; s->ppo_parts = (int)((P + PPO_SLICE - 1) / PPO_SLICE);
-    ok = ok && dalloc(&s->dppo_theta, P) == hipSuccess && dalloc(&s->dppo_m, P) == hipSuccess && dalloc(&s->dppo_v, P) == hipSuccess;
-    ok = ok && dalloc(&s->dppo_G, P) == hipSuccess && dalloc(&s->dppo_part, (size_t)s->ppo_parts) == hipSuccess && dalloc(&s->dppo_advstat, (size_t)2) == hipSuccess;
-    ok = ok && hipFuncSetAttribute((const void *)ppo_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
-    if (ok) {
-        PpoAdamArgs a;
-        ppo_adam_args(s, a, 2);
-        hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((P + PPO_RED - 1) / PPO_RED)), dim3(PPO_RED), 0, c->stream, a);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
-    }
-    if (!ok) { ppo_release(s); (void)hipGetLastError(); return fail("ppo_attach: allocation failed"); }
-    s->ppo_clip = clip_range; s->ppo_ent = ent_coef; s->ppo_vf = vf_coef; s->ppo_max_norm = max_grad_norm; s->ppo_normalize = normalize_advantage ? 1 : 0;
-    s->ppo_t = 0; s->ppo = true;
-    return 0;
-}
-
-// workspaces of a minibatch of up to `rows` rows (a multiple of 16): activations and deltas of every layer, the row records
-static int ppo_reserve_rows(tum_sim *s, size_t rows)
-{
-    if (rows <= s->ppo_rows_cap) return 0;
-    bool ok = true;
-    for (PpoNet *t : {&s->tp, &s->tv})
-        for (int l = 0; l < t->n_mat; l++) {
-            (void)hipFree(t->h[l]); (void)hipFree(t->d[l]); t->h[l] = t->d[l] = nullptr;
-            ok = ok && dalloc(&t->h[l], rows * t->hs[l]) == hipSuccess && dalloc(&t->d[l], rows * t->mp[l]) == hipSuccess;
-        }
-    (void)hipFree(s->dppo_rowrec); s->dppo_rowrec = nullptr;
-    ok = ok && dalloc(&s->dppo_rowrec, rows * PPO_ROW) == hipSuccess;
-    s->ppo_rows_cap = ok ? rows : 0;
-    if (!ok) { (void)hipGetLastError(); return fail("ppo: allocation failed"); }
-    return 0;
-}
-template <typename T>
-static int ppo_reserve(T **p, size_t *cap, size_t n)
-{
-    if (n <= *cap) return 0;
-    (void)hipFree(*p); *p = nullptr; *cap = 0;
-    if (dalloc(p, n) != hipSuccess) { (void)hipGetLastError(); return fail("ppo: allocation failed"); }
-    *cap = n;
-    return 0;
-}
-
-// the columns of a training buffer on the device
-struct PpoData { const double *obs; int stride; const double *act, *old_logp, *adv, *ret; };
-
-// One minibatch on the capsule's stream, nothing waited for: rows idx[0 .. n) of the buffer (idx null: 0 .. n - 1); its diagnostics to
-// dstats. apply 0: loss, gradients and their norm alone.
-static int ppo_minibatch_enqueue(tum_sim *s, const PpoData &d, const int *idx, int n, double lr, int apply, double *dstats)
-{
-    tum_ocp *c = s->c;
-    const int rows = (n + POL_TILE - 1) & ~(POL_TILE - 1);
-    PpoStatsArgs sa;
-    sa.n = n; sa.normalize = s->ppo_normalize; sa.idx = idx; sa.adv = d.adv; sa.out = s->dppo_advstat;
-    hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(PPO_RED), 0, c->stream, sa);
-    HIPCHK(hipGetLastError());
-    PpoTileArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.pi = s->pa; ta.vf = s->va; ta.tp = s->tp; ta.tv = s->tv;
-    ta.pi.n = ta.vf.n = n; ta.pi.obs = ta.vf.obs = d.obs; ta.pi.obs_stride = ta.vf.obs_stride = d.stride;
-    ta.rows = std::max(s->pa.rows, s->va.rows); ta.idx = idx;
-    ta.act = d.act; ta.old_logp = d.old_logp; ta.adv = d.adv; ta.ret = d.ret; ta.advstat = s->dppo_advstat;
-    ta.clip = s->ppo_clip; ta.ent_coef = s->ppo_ent; ta.vf_coef = s->ppo_vf; ta.rowrec = s->dppo_rowrec;
-    hipLaunchKernelGGL(ppo_tile_kernel, dim3(rows / POL_TILE), dim3(64 * POL_WAVES), sizeof(double) * 2 * ta.rows * POL_TILE, c->stream, ta);
-    HIPCHK(hipGetLastError());
-    PpoGradArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.net[0] = s->tp; ga.net[1] = s->tv; ga.rows = rows; ga.G = s->dppo_G;
-    ga.goff[0] = 0; ga.goff[1] = s->tp.off[s->tp.n_mat - 1] + (s->tp.in[s->tp.n_mat - 1] + 1) * s->tp.out[s->tp.n_mat - 1];
-    int tiles = 0;
-    for (int ni = 0; ni < 2; ni++)
-        for (int l = 0; l < POL_MAXMAT; l++) {
-            const PpoNet &t = ga.net[ni];
-            ga.first[ni * POL_MAXMAT + l] = tiles;
-            if (l < t.n_mat) tiles += (t.mp[l] / 16) * (t.hs[l] / 16 + 1);
-        }
-    ga.first[2 * POL_MAXMAT] = tiles;
-    hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(tiles), dim3(64), 0, c->stream, ga);
-    HIPCHK(hipGetLastError());
-    PpoNormArgs na;
-    na.P = s->ppo_P; na.n_parts = s->ppo_parts; na.n = n; na.G = s->dppo_G; na.rowrec = s->dppo_rowrec;
-    na.ent_coef = s->ppo_ent; na.vf_coef = s->ppo_vf; na.parts = s->dppo_part; na.stats = dstats;
-    hipLaunchKernelGGL(ppo_norm_kernel, dim3(s->ppo_parts + 1), dim3(PPO_RED), 0, c->stream, na);
-    HIPCHK(hipGetLastError());
-    PpoAdamArgs aa;
-    ppo_adam_args(s, aa, apply ? 1 : 0);
-    aa.stats = dstats;
-    if (apply) {
-        const double t = (double)(s->ppo_t + 1);
-        aa.step = lr / (1.0 - std::pow(aa.beta1, t)); aa.bc2_sqrt = std::sqrt(1.0 - std::pow(aa.beta2, t));
-    }
-    hipLaunchKernelGGL(ppo_adam_kernel, dim3(apply ? (s->ppo_P + PPO_RED - 1) / PPO_RED : 1), dim3(PPO_RED), 0, c->stream, aa);
-    HIPCHK(hipGetLastError());
-    if (apply) s->ppo_t++;
-    return 0;
-}
-
-// a host buffer of N rows into the trainer's own device copy: observations N x n_obs, then actions (as doubles), old log-probabilities,
-// advantages and returns, N each
-static int ppo_upload(tum_sim *s, size_t N, const double *obs, const int *actions, const double *old_logp, const double *adv, const double *ret, PpoData *d)
-{
-    const size_t no = s->pa.n_in;
-    if (ppo_reserve(&s->dppo_data, &s->ppo_data_cap, N * (no + 4))) return 1;
-    std::vector<double> act(N);
-    for (size_t i = 0; i < N; i++) {
-        if (actions[i] < 0 || actions[i] >= s->pa.n_act) return fail("ppo: action of row " + std::to_string(i) + " is outside the policy's " + std::to_string(s->pa.n_act));
-        act[i] = (double)actions[i];
-    }
-    double *p = s->dppo_data;
-    HIPCHK(hipMemcpy(p, obs, sizeof(double) * N * no, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p + N * no, act.data(), sizeof(double) * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p + N * (no + 1), old_logp, sizeof(double) * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p + N * (no + 2), adv, sizeof(double) * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p + N * (no + 3), ret, sizeof(double) * N, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    d->obs = p; d->stride = (int)no; d->act = p + N * no; d->old_logp = p + N * (no + 1); d->adv = p + N * (no + 2); d->ret = p + N * (no + 3);
-    return 0;
-}
-
-// One minibatch of n host rows. apply 0 computes loss and gradients only: parameters, moments and the step counter stay as they are.
-// stats_out: TUM_PPO_STATS doubles. grads_out (optional): the UNCLIPPED gradients, the flat parameter vector in torch's layout (per net
-// W_0 row-major (out, in), b_0, W_1, ...; policy net then value net). rows_out (optional): n x 2, the log-probability of the row's
-// action and its value as the tile kernel computed them.
-extern "C" int tum_sim_ppo_step(tum_sim *s, int n, const double *obs, const int *actions, const double *old_log_probs, const double *advantages,
-                                const double *returns, double lr, int apply, double *stats_out, double *grads_out, double *rows_out)
-{
-    if (!s || !obs || !actions || !old_log_probs || !advantages || !returns || !stats_out) return fail("null argument");
-    if (!s->ppo) return fail("ppo_step: no trainer attached (tum_sim_ppo_attach)");
-    if (n < 1) return fail("ppo_step: n < 1");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const size_t rows = ((size_t)n + POL_TILE - 1) & ~(size_t)(POL_TILE - 1);
-    PpoData d;
-    if (ppo_upload(s, n, obs, actions, old_log_probs, advantages, returns, &d)) return 1;
-    if (ppo_reserve_rows(s, rows) || ppo_reserve(&s->dppo_stats, &s->ppo_stats_cap, (size_t)PPO_STATS)) return 1;
-    if (ppo_minibatch_enqueue(s, d, nullptr, n, lr, apply, s->dppo_stats)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(stats_out, s->dppo_stats, sizeof(double) * PPO_STATS, hipMemcpyDeviceToHost));
-    if (grads_out) HIPCHK(hipMemcpy(grads_out, s->dppo_G, sizeof(double) * s->ppo_P, hipMemcpyDeviceToHost));
-    if (rows_out) {
-        std::vector<double> rec((size_t)n * PPO_ROW);
-        HIPCHK(hipMemcpy(rec.data(), s->dppo_rowrec, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; i++) { rows_out[2 * i] = rec[(size_t)i * PPO_ROW + PPO_R_LOGP]; rows_out[2 * i + 1] = rec[(size_t)i * PPO_ROW + PPO_R_V]; }
-    }
-    return 0;
-}
-
-// One whole update: n_epochs passes over the N buffer rows, pass e in the order perm[e][0 .. N), cut into minibatches of batch_size
-// rows (the last one may be short); every minibatch's chain is enqueued, one wait, one download of n_epochs x ceil(N / batch_size) x
-// TUM_PPO_STATS diagnostics. obs .. returns all NULL: the buffer the last tum_sim_env_collect left on the device (row e B + b).
-extern "C" int tum_sim_ppo_update(tum_sim *s, int N, const double *obs, const int *actions, const double *old_log_probs, const double *advantages,
-                                  const double *returns, const int *perm, int n_epochs, int batch_size, double lr, double *stats_out)
-{
-    if (!s || !perm || !stats_out) return fail("null argument");
-    if (!s->ppo) return fail("ppo_update: no trainer attached (tum_sim_ppo_attach)");
-    if (N < 1 || n_epochs < 1) return fail("ppo_update: N and n_epochs must be >= 1");
-    if (batch_size < 1) return fail("ppo_update: batch_size < 1");
-    const bool resident = !obs && !actions && !old_log_probs && !advantages && !returns;
-    if (!resident && (!obs || !actions || !old_log_probs || !advantages || !returns)) return fail("ppo_update: a buffer is all five arrays, or none of them");
-    if (resident && s->col_rows == 0) return fail("ppo_update: no buffer given and no collection on the device (tum_sim_env_collect)");
-    if (resident && s->col_rows != (size_t)N) return fail("ppo_update: the collection on the device has " + std::to_string(s->col_rows) + " rows, not " + std::to_string(N));
-    for (size_t i = 0; i < (size_t)n_epochs * N; i++)
-        if (perm[i] < 0 || perm[i] >= N) return fail("ppo_update: perm[" + std::to_string(i / N) + "][" + std::to_string(i % N) + "] is outside the buffer");
-    tum_ocp *c = s->c;
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const int bs = std::min(batch_size, N), n_mb = (N + bs - 1) / bs;
-    PpoData d;
-    if (resident) {
-        const size_t EB = N;
-        d.obs = s->dcol + COL_FIELDS * EB; d.stride = s->pa.n_in; d.act = s->dcol + COL_ACTION * EB; d.old_logp = s->dcol + COL_LOGP * EB;
-        d.adv = s->dcol + COL_ADV * EB; d.ret = s->dcol + COL_RET * EB;
-    } else if (ppo_upload(s, N, obs, actions, old_log_probs, advantages, returns, &d)) return 1;
-    const size_t n_stats = (size_t)n_epochs * n_mb * PPO_STATS;
-    if (ppo_reserve_rows(s, ((size_t)bs + POL_TILE - 1) & ~(size_t)(POL_TILE - 1)) || ppo_reserve(&s->dppo_stats, &s->ppo_stats_cap, n_stats) ||
-        ppo_reserve(&s->dppo_idx, &s->ppo_idx_cap, (size_t)n_epochs * N)) return 1;
-    HIPCHK(hipMemcpy(s->dppo_idx, perm, sizeof(int) * (size_t)n_epochs * N, hipMemcpyHostToDevice));
-    HIPCHK(hipDeviceSynchronize());
-    for (int e = 0; e < n_epochs; e++)
-        for (int k = 0; k < n_mb; k++)
-            if (ppo_minibatch_enqueue(s, d, s->dppo_idx + (size_t)e * N + (size_t)k * bs, std::min(bs, N - k * bs), lr, 1,
-                                      s->dppo_stats + ((size_t)e * n_mb + k) * PPO_STATS)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(stats_out, s->dppo_stats, sizeof(double) * n_stats, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// the float32 parameters the device acts with, per matrix as the attach functions take them (W[l]: (out, in) row-major)
-extern "C" int tum_sim_ppo_params(tum_sim *s, float *const *W, float *const *b, float *const *VW, float *const *Vb)
-{
-    if (!s || !W || !b || !VW || !Vb) return fail("null argument");
-    if (!s->ppo) return fail("ppo_params: no trainer attached (tum_sim_ppo_attach)");
-    DevGuard guard(s->c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(s->c->stream));
-    std::vector<float> th(s->ppo_P);
-    HIPCHK(hipMemcpy(th.data(), s->dppo_theta, sizeof(float) * th.size(), hipMemcpyDeviceToHost));
-    size_t base = 0;
-    for (int ni = 0; ni < 2; ni++) {
-        const PpoNet &t = ni ? s->tv : s->tp;
-        float *const *Wo = ni ? VW : W, *const *bo = ni ? Vb : b;
-        size_t end = 0;
-        for (int l = 0; l < t.n_mat; l++) {
-            if (!Wo[l] || !bo[l]) return fail("null argument");
-            const size_t nw = (size_t)t.out[l] * t.in[l];
-            memcpy(Wo[l], &th[base + t.off[l]], sizeof(float) * nw);
-            memcpy(bo[l], &th[base + t.off[l] + nw], sizeof(float) * t.out[l]);
-            end = t.off[l] + nw + t.out[l];
-        }
-        base += end;
-    }
-    return 0;
-}
-
-// Adam's state: the moments over the flat parameter vector (n_params doubles each; either may be NULL) and the step counter
-extern "C" int tum_sim_ppo_state(tum_sim *s, double *m, double *v, long long *t, int *n_params)
-{
-    if (!s) return fail("null argument");
-    if (!s->ppo) return fail("ppo_state: no trainer attached (tum_sim_ppo_attach)");
-    DevGuard guard(s->c->d.device); GUARD_OK(guard);
-    HIPCHK(hipStreamSynchronize(s->c->stream));
-    if (m) HIPCHK(hipMemcpy(m, s->dppo_m, sizeof(double) * s->ppo_P, hipMemcpyDeviceToHost));
-    if (v) HIPCHK(hipMemcpy(v, s->dppo_v, sizeof(double) * s->ppo_P, hipMemcpyDeviceToHost));
-    if (t) *t = s->ppo_t;
-    if (n_params) *n_params = s->ppo_P;
-    return 0;
-}
-
-
-static int env_get(tum_sim *s, const std::string &f, double *out, long long len)
-{
-    const long long B = s->c->batch;
-    if (!s->env) return fail("sim_get " + f + ": no environment attached (tum_sim_env_attach)");
-    if (len != B) return fail("sim_get " + f + ": len != batch");
-    if (f == "env_ended") { for (long long i = 0; i < B; i++) out[i] = s->env_ended[i]; return 0; }
-    const int *src = f == "env_episode_steps" ? s->denv_ep : f == "env_step_length" ? s->denv_count : f == "env_flags" ? s->denv_flags :
-                     f == "env_qp_failures" ? s->denv_qpf : f == "env_samples" ? s->denv_samples : nullptr;
-    if (!src) return fail("sim_get: unknown field '" + f + "'");
-    std::vector<int> t(B);
-    HIPCHK(hipMemcpy(t.data(), src, sizeof(int) * B, hipMemcpyDeviceToHost));
-    for (long long i = 0; i < B; i++) out[i] = t[i];
-    return 0;
-}
-
-static int seg_get(tum_sim *s, const std::string &f, double *out, long long len)
-{
-    tum_ocp *c = s->c; const long long B = c->batch;
-    if (!s->seg) return fail("sim_get " + f + ": no segments attached (tum_sim_segments_attach)");
-    if (f == "seg_active") {
-        if (len != 1) return fail("sim_get seg_active: len != 1");
-        int n = 0;
-        if (seg_count_active(s, &n)) return 1;
-        out[0] = n;
-        return 0;
-    }
-    if (f == "seg_groups") {
-        if (len != 4LL * s->seg_groups) return fail("sim_get seg_groups: len != 4 * n_groups");
-        hipLaunchKernelGGL(segment_group_kernel, dim3(s->seg_groups), dim3(64), 0, c->stream, s->dseg_off, s->seg_groups, s->dseg_steps,
-                           s->dseg_state, s->dseg_lat, s->dseg_ssq, s->dseg_out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(out, s->dseg_out, sizeof(double) * len, hipMemcpyDeviceToHost));
-        return 0;
-    }
-    if (len != B) return fail("sim_get " + f + ": len != batch");
-    const int *isrc = f == "seg_steps" ? s->dseg_steps : f == "seg_state" ? s->dseg_state : f == "seg_qp_failures" ? s->dseg_qpf : nullptr;
-    if (isrc) {
-        std::vector<int> t(B);
-        HIPCHK(hipMemcpy(t.data(), isrc, sizeof(int) * B, hipMemcpyDeviceToHost));
-        for (long long i = 0; i < B; i++) out[i] = t[i];
-        return 0;
-    }
-    if (f == "seg_max_lat_dev") { HIPCHK(hipMemcpy(out, s->dseg_lat, sizeof(double) * B, hipMemcpyDeviceToHost)); return 0; }
-    if (f == "seg_max_a_comb") { HIPCHK(hipMemcpy(out, s->dseg_acomb, sizeof(double) * B, hipMemcpyDeviceToHost)); return 0; }
-    if (f == "seg_rms_vel_dev") {          // sqrt(sumsq_vel / steps): get_root_mean_square of objective_function.py:184 (0 before the first step)
-        std::vector<int> t(B);
-        HIPCHK(hipMemcpy(t.data(), s->dseg_steps, sizeof(int) * B, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out, s->dseg_ssq, sizeof(double) * B, hipMemcpyDeviceToHost));
-        for (long long i = 0; i < B; i++) out[i] = t[i] > 0 ? std::sqrt(out[i] / (double)t[i]) : 0.0;
-        return 0;
-    }
-    return fail("sim_get: unknown field '" + f + "'");
-}
-
-extern "C" int tum_sim_get(tum_sim *s, const char *field, double *out, long long len)
-{
-    if (!s || !field || !out) return fail("null argument");
-    tum_ocp *c = s->c; const long long B = c->batch;
-    const long long L = s->step < s->log_cap ? s->step : s->log_cap;
-    const std::string f(field);
-    DevGuard guard(c->d.device); GUARD_OK(guard);
-    if (flush_inputs(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const double *src = nullptr; long long want = 0;
-    if (f.compare(0, 4, "seg_") == 0) return seg_get(s, f, out, len);
-    if (f.compare(0, 4, "env_") == 0) return env_get(s, f, out, len);
-    if (f == "x_sim") { src = s->dxsim; want = B * 7; }
-    else if (f == "x_mpc") { src = c->dx0; want = B * 8; }
-    else if (f == "pose") { src = s->dpose; want = B * 2; }
-    else if (f == "ref0") { src = s->dref0; want = B * 4; }
-    else if (f == "graph_steps") {         // control steps per captured hipGraph chunk (0: plain launches)
-        if (len != 1) return fail("sim_get graph_steps: len != 1");
-        out[0] = s->graph ? s->graph_steps : 0;
-        return 0;
-    }
-    else if (f == "closest") {
-        if (len != B) return fail("sim_get closest: len != batch");
-        std::vector<int> t(B);
-        HIPCHK(hipMemcpy(t.data(), s->dclosest, sizeof(int) * B, hipMemcpyDeviceToHost));
-        for (long long i = 0; i < B; i++) out[i] = t[i];
-        return 0;
-    }
-    else if (f == "CiLX") { src = s->lCiLX; want = (L + 1) * B * 7; }
-    else if (f == "MPC_SimX") { src = s->lSimX; want = (L + 1) * B * 8; }
-    else if (f == "simU") { src = s->lU; want = L * B * 2; }
-    else if (f == "simREF") { src = s->lREF; want = L * B * 4; }
-    else if (f == "simSolverDebug") { src = s->lDBG; want = L * B * 5; }
-    else return fail("sim_get: unknown field '" + f + "'");
-    if (!src) return fail("sim_get: logging disabled (log_capacity 0)");
-    if (len != want) return fail("sim_get " + f + ": len mismatch");
-    if (want > 0) HIPCHK(hipMemcpy(out, src, sizeof(double) * want, hipMemcpyDeviceToHost));
-    return 0;
-}
+// the device closed loop on the capsule above, host code like the rest of this file in headers of its own
+#include "sim_loop.hpp"          // K8 / K9: tum_sim, the control step, segment scoring, the getters
+#include "sim_rl.hpp"            // K11 to K14: the RL environment, the agent, collection, the trainer
