@@ -232,7 +232,10 @@ int tum_ocp_get_cost(tum_ocp *c, double *out, int b0, int nb);
  *   at alpha = 0 (zeros for an instance that never searched)
  * "merit_weights" -> nb x 2 doubles: mu_eq, mu_in
  * "lin_uniform" -> 1 int: linearisations of this capsule that took the uniform path (options_set "lin_dedup") since it was created.
- * "records_skipped" -> 1 int: solves of this capsule that ran without stage records (options_set "uniform_records") since it was created. */
+ * "records_skipped" -> 1 int: solves of this capsule that ran without stage records (options_set "uniform_records") since it was created.
+ * "lpt_order" -> nb ints: entries b0 .. b0 + nb - 1 of the longest-first order the NEXT solve dispatches in (tum_ocp_set_schedule): the
+ *   last solve's iteration counts, clipped to 0..63, descending; instances of one count by ascending index. The identity map while no
+ *   order is kept (a batch of at most 1024, before the first solve). */
 int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b0, int nb);
 /* acados_solver.reset()   NMPC_class.py:251 -- zero the iterate of every instance */
 int tum_ocp_reset(tum_ocp *c);

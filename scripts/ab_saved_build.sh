@@ -1,12 +1,13 @@
 #!/bin/bash
 # A/B of a SAVED build of the parent commit against the library of the working tree, run from the same tree on one box
 # (the protocol of profiles/lin_uniform_ab.txt and profiles/uniform_records_ab.txt):
-#   scripts/ab_saved_build.sh <parent libtumnmpc.so> [headline] [trace] [full] | [ktrace] [onestream] [dump] [fullbench]
+#   scripts/ab_saved_build.sh <parent libtumnmpc.so> [headline] [trace] [full] | [ktrace] [ktrace3] [onestream] [dump] [fullbench]
 #     headline  python bench.py, six fresh processes each, interleaved parent / change
 #     trace     rocprofv3 --kernel-trace --stats -- python bench.py --streams 1 (kernel trace only, no counters) for each build: average and
 #               standard deviation per kernel; then bench.py --full --no-other-configs --no-cpu-baseline for each (value_single_stream)
 #     full      bench.py --dump-outputs (--steps 20 --warmup 3) for each build and the bitwise comparison of every .npy, then bench.py --full
 #     ktrace, onestream | dump, fullbench: the two halves of trace | of full on their own
+#     ktrace3   the kernel trace of the DEFAULT run (three streams) for each build: kernels that wait for room beside the other capsules' kernels
 # The parent's library is built by the same compiler from `git archive <parent>` with the command line of __graft_entry__.build() and
 # loaded through TUM_NMPC_LIB. Every process runs under its own timeout; the chain stops at the first non-zero exit.
 # Results under $AB_OUT (default: ab_out/, which git ignores).
@@ -28,23 +29,25 @@ headline)
     grep metric $OUT/${w}_$i.out > $OUT/${w}_$i.json
     python -c "import json; d = json.load(open('$OUT/${w}_$i.json')); print('$w', $i, 'value', round(d['value']), 'ms/step', round(d['ms_per_step'], 4))"
   done; done ;;
-ktrace)
+ktrace|ktrace3)
+  # ktrace: one stream; ktrace3: the default run's three streams (what a kernel waits for beside the other capsules' kernels shows here only)
+  if [ $leg = ktrace3 ]; then TR_ARGS=""; TR=trace3; else TR_ARGS="--streams 1"; TR=trace; fi
   for w in parent change; do
     use $w
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$w -o s -- python bench.py --streams 1 --no-cpu-baseline \
-        --no-schedule-legs --no-other-configs --steps 20 --warmup 3 > $OUT/trace_$w.log 2>&1 < /dev/null || die "trace $w" $?
-    python - $OUT/stats_$w > $OUT/kernel_avg_std_$w.txt <<'EOF' || die "trace summary $w" $?
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$w -o s -- python bench.py $TR_ARGS --no-cpu-baseline \
+        --no-schedule-legs --no-other-configs --steps 20 --warmup 3 > $OUT/${TR}_$w.log 2>&1 < /dev/null || die "$TR $w" $?
+    python - $OUT/stats_$w > $OUT/kernel_avg_std_${TR}_$w.txt <<'EOF' || die "$TR summary $w" $?
 import collections, csv, glob, statistics, sys
 d = collections.defaultdict(list)
 for f in glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         d[r["Kernel_Name"]].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
 for k, v in sorted(d.items(), key=lambda kv: -sum(kv[1])):
-    if any(s in k for s in ("lin_", "cond_", "ipm_", "expand_")):
+    if any(s in k for s in ("lin_", "cond_", "ipm_", "expand_", "lpt_", "cold_start")):
         print("%-64s n %3d  avg %9.0f ns  std %8.0f  min %9d  max %9d" % (k[:64], len(v), statistics.mean(v), statistics.pstdev(v), min(v), max(v)))
 EOF
     rm -rf $OUT/stats_$w
-    echo "$w: traced value $(grep metric $OUT/trace_$w.log | python -c "import json, sys; print(round(json.loads(sys.stdin.read())['value']))")"; cat $OUT/kernel_avg_std_$w.txt
+    echo "$w: $TR, traced value $(grep metric $OUT/${TR}_$w.log | python -c "import json, sys; print(round(json.loads(sys.stdin.read())['value']))")"; cat $OUT/kernel_avg_std_${TR}_$w.txt
   done ;;
 onestream)
   for w in parent change; do

@@ -942,6 +942,10 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_columns_k
 //            before stage 33, no lane-63 arrangement. Weights, residual lanes (the reference two stages ahead), aop = bop wl ahead of
 //            the matrix instructions and the order of the matrix instructions are the column form's; q0 / q1 add the same products in
 //            the same order. Hand-over unchanged (tests/test_gpu_uniform_powers.py holds it against the column form, to the bit).
+//   waits    (profiles/cond_uniform_pipeline_ab.txt) every global load of the instance is issued at the head and waited for once; the
+//            five-tile build keeps the reference rows in LDS, so that no stage waits on the vector-memory counter (which would also
+//            wait for the stage's own gg-row store), and requests a stage's matrix operands one stage ahead (stage_body_pf;
+//            tests/test_gpu_cond_uniform_edges.py).
 template <int NT_> struct CondPow {
     static constexpr int NVP = 16 * NT_, NMAX = 8 * NT_;
     static constexpr int PAD = 2;               // in front of a row: the one step the P rows run beyond m = N - 1 lands here at N = NMAX
@@ -951,7 +955,9 @@ template <int NT_> struct CondPow {
     static constexpr int R_HR = 4, NROW = 5;    // rows 0..3: the cost rows, row 4: the gg-row entry
     static constexpr int TAB = 0, GS = TAB + NROW * ROW;          // g_s: 8 doubles per s = 0..NMAX (entry 4: its gg-row sum)
     static constexpr int DUMP = GS + (NMAX + 1) * 8;              // where the idle lanes of phase 1 store
-    static constexpr int U0 = DUMP + 64, WT = U0 + NVP, LDS = (WT + (NMAX + 1) * 6 + 1) & ~1;
+    // YR (five tiles only): the reference rows -- the residual lanes read the reference two stages ahead here, not from global memory:
+    // a global load in the stage loop makes every stage wait for the write acknowledgement of its own gg-row store (one counter)
+    static constexpr int U0 = DUMP + 64, WT = U0 + NVP, YR = (WT + (NMAX + 1) * 6 + 1) & ~1, LDS = YR + ((NT_ == 5) ? ((NMAX + 1) * 6 + 1) & ~1 : 0);
     static_assert(LDS * 8 <= 20 * 1024, "eight workgroups per CU");
 };
 // acc += (lane L of the row of b) * x      (b must be settled: two wait states behind the vector instruction that wrote it)
@@ -962,6 +968,17 @@ template <int L> __device__ __forceinline__ void fmac_bc(double &acc, double b, 
 }
 __device__ __forceinline__ void settle_dpp(double &v) { asm volatile("s_nop 1" : "+v"(v)); }
 
+// what a stage of the five-tile build requests one stage ahead (cond_powers_instance, stage_body_pf): scalars, not an array -- carried
+// round the stage loop an array stays in scratch memory
+struct CondAhead {
+    double wl, hr, hr1, b0, b1, b2, b3, b4;
+    template <int I> __device__ __forceinline__ double &bop()
+    {
+        static_assert(I >= 0 && I < 5, "five tiles");
+        if constexpr (I == 0) return b0; else if constexpr (I == 1) return b1; else if constexpr (I == 2) return b2; else if constexpr (I == 3) return b3; else return b4;
+    }
+    template <int I> __device__ __forceinline__ double bop() const { return const_cast<CondAhead *>(this)->template bop<I>(); }
+};
 template <int NT_>
 __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const double *lin1)
 {
@@ -982,38 +999,69 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
     const double *gyref = ka.yref + (size_t)b * (N + 1) * 6;
     const double *gW = ka.W + (size_t)b * (N + 1) * 6;
     double *gvec = pa.vec + (size_t)b * PVEC;
-    // the weights as the sums take them: dt W_s of the stages s < N, W_e of stage N
-    for (int i = lane; i < (N + 1) * 6; i += 64) sWt[i] = ((i < 6 * N) ? dt : 1.0) * gW[i];
-    sU0[lane] = (lane < nv) ? gU[lane] : 0.0;
-    if (lane < NB1) sU0[64 + lane] = (64 + lane < nv) ? gU[64 + lane] : 0.0;
-    // the zero pad behind every table row: the columns that are not there yet
+    constexpr bool PF = (NT_ == 5);          // the stage of the five-tile build (stage_body_pf below)
+    // ---- the head: EVERY global load of the instance first, branch-free (an index that is not wanted is clamped to one that is valid,
+    // the value dropped by a select), so that they are in flight together and the wavefront waits for memory once. Loads under lane
+    // conditions and the copy loops to LDS (load, wait, store, four times over) were thirteen waits one behind the other: a fifth of the
+    // wavefront's cycles (profiles/cond_uniform_pipeline_ab.txt).
+    constexpr int NW = ((NMAX + 1) * 6 + 63) / 64;
+    const int nw = (N + 1) * 6;
+    double wv[NW], yv[PF ? NW : 1];
 #pragma unroll
-    for (int r = 0; r < T::NROW; r++)
-        for (int i = lane; i < ROW - PAD - 2 * NMAX; i += 64) sTab[r * ROW + PAD + 2 * NMAX + i] = 0.0;
+    for (int j = 0; j < NW; j++) {
+        const int ic = (lane + 64 * j < nw) ? lane + 64 * j : nw - 1;
+        wv[j] = gW[ic];
+        if constexpr (PF) yv[j] = gyref[ic];
+    }
+    const double u0v = gU[(lane < nv) ? lane : 0], u1v = gU[(lane < NB1 && 64 + lane < nv) ? 64 + lane : 0];
     // the residual lanes (fields 52..55 of the column form's fourth register: lanes 4..7 of every row), what they subtract the reference
     // from, and the reference two stages ahead (one value for the even stages, one for the odd ones)
     const bool ures = (lane & 12) == 4;
     const double *uyp = gyref + (ures ? (lane & 3) : 0);
-    const double x2w = wrap_yaw(gX[2]);
-    const double uxr = ((lane & 3) == 2) ? x2w : gX[lane & 3];
-    double res = ures ? uxr - uyp[6] : 0.0;          // stage 1
+    const double gx2 = gX[2], gxl = gX[lane & 3], gx6 = gX[6];
+    const double uy1 = uyp[6], uy2 = uyp[((2 <= N) ? 2 : N) * 6], uy3 = uyp[((3 <= N) ? 3 : N) * 6];
+    // phase 1's: the coefficients of row i of A, the defect, the gg row's, P_0 / g_0
+    const int p = lane & 15, i = lane & 7, vrow = lane >> 4, r = vrow & 1;
+    const bool isP = vrow < 2;
+    const int i6 = (i < 6) ? i : 0;
+    const double lc2 = lin1b[i & 1];
+    double lcS[5];
+#pragma unroll
+    for (int c = 0; c < 5; c++) lcS[c] = lin1b[2 + i6 * 7 + c];
+    const double lxn = lin1b[L1_XN + i], gxi = gX[i], gx0i = gx0[i], lb = lin1b[2 + i6 * 7 + 5 + r];
+    const double g3 = lin1b[L1_GH + 0], g5 = lin1b[L1_GH + 1], g7 = lin1b[L1_GH + 2], gh3 = lin1b[L1_GH + 3];
+    // the zero pad behind every table row: the columns that are not there yet
+#pragma unroll
+    for (int rr = 0; rr < T::NROW; rr++)
+        for (int ii = lane; ii < ROW - PAD - 2 * NMAX; ii += 64) sTab[rr * ROW + PAD + 2 * NMAX + ii] = 0.0;
+    // the weights as the sums take them: dt W_s of the stages s < N, W_e of stage N
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        const int ii = lane + 64 * j;
+        if (ii < nw) {
+            sWt[ii] = ((ii < 6 * N) ? dt : 1.0) * wv[j];
+            if constexpr (PF) lds[T::YR + ii] = yv[j];
+        }
+    }
+    sU0[lane] = (lane < nv) ? u0v : 0.0;
+    if (lane < NB1) sU0[64 + lane] = (64 + lane < nv) ? u1v : 0.0;
+    const double x2w = wrap_yaw(gx2);
+    const double uxr = ((lane & 3) == 2) ? x2w : gxl;
+    double res = ures ? uxr - uy1 : 0.0;          // stage 1
     double uy[2] = {0.0, 0.0};
-    if (2 <= N) uy[0] = uyp[2 * 6];
-    if (3 <= N) uy[1] = uyp[3 * 6];
+    if (2 <= N) uy[0] = uy2;
+    if (3 <= N) uy[1] = uy3;
 
     // ---- phase 1: the sequences
     {
-        const int p = lane & 15, i = lane & 7, vrow = lane >> 4, r = vrow & 1;
-        const bool isP = vrow < 2;
         const bool keep = i < 3 || i >= 6;          // rows 0..2 are updated in place, 6 / 7 are the integrators; 3..5 start from zero
-        const double c2 = (i < 2) ? lin1b[i] : 0.0;          // Sp
+        const double c2 = (i < 2) ? lc2 : 0.0;          // Sp
         double cS[5];
 #pragma unroll
-        for (int c = 0; c < 5; c++) cS[c] = (i < 6) ? lin1b[2 + i * 7 + c] : 0.0;
-        const double dsel = isP ? 0.0 : lin1b[L1_XN + i] - gX[i];          // the defect, on the rows that carry g
-        const double g3 = lin1b[L1_GH + 0], g5 = lin1b[L1_GH + 1], g7 = lin1b[L1_GH + 2];
+        for (int c = 0; c < 5; c++) cS[c] = (i < 6) ? lcS[c] : 0.0;
+        const double dsel = isP ? 0.0 : lxn - gxi;          // the defect, on the rows that carry g
         // P_0: column r of B over the integrator of input r; g_0 = x0 - X_0
-        double w = isP ? ((i < 6) ? lin1b[2 + i * 7 + 5 + r] : (((i == 6) == (r == 1)) ? dt : 0.0)) : gx0[i] - gX[i];
+        double w = isP ? ((i < 6) ? lb : (((i == 6) == (r == 1)) ? dt : 0.0)) : gx0i - gxi;
         // what a lane stores of its vector: P rows the entries 0..3 and the gg-row entry (lane 4), towards smaller indices (m grows);
         // the g row its entries 0..7 (lane 4: the gg-row sum), s upwards; everybody else into a slot of its own
         const bool act = isP ? p < T::NROW : (vrow == 2 && p < 8);
@@ -1045,8 +1093,8 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
     wsync();
     // d of the two rows of every stage: X_0[6] + g_s[6] and h + the gg-row sum of g_s
     if (lane < N) {
-        gvec[PV_D + 2 * lane] = sG[(lane + 1) * 8 + 6] + gX[6];
-        gvec[PV_D + 2 * lane + 1] = sG[(lane + 1) * 8 + 4] + lin1b[L1_GH + 3];
+        gvec[PV_D + 2 * lane] = sG[(lane + 1) * 8 + 6] + gx6;
+        gvec[PV_D + 2 * lane + 1] = sG[(lane + 1) * 8 + 4] + gh3;
     }
 
     // ---- phase 2: the stages
@@ -1111,14 +1159,118 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
         if (k + 1 < N) res = ures ? uxr - uyq : res;
         if (k + 3 < N) uyq = uyp[(size_t)(k + 4) * 6];
     };
-    // stage s = k+1 touches columns < 2s, i.e. ceil(s/8) tiles: one instantiation of the stage per segment of 8 stages
-    static_for<1, NT>([&](auto tsc) {
+    // ---- the stage of the five-tile build (PF): the same sums from the same operands in the same order, but no stage waits for its own
+    // LDS reads in front of its matrix instructions.
+    //   ahead    what the matrix instructions and the workspace store take (the B operands, wl, the gg-row entries) is requested ONE
+    //            STAGE AHEAD, into a second register set, before the previous stage's matrix instructions are issued;
+    //   behind   what the gradient sum takes (the weights, g_s, the lane's cost rows) is requested at the top of the stage and used
+    //            BEHIND the stage's matrix instructions: its wait and its ~20 vector instructions run while the matrix pipe works.
+    // A second set of everything (24 doubles) does not fit beside the 15 tiles at two wavefronts per SIMD (256 VGPRs, 30 of them
+    // spilled); this split carries eight doubles from stage to stage. The products bop wl are held in front of the matrix instructions
+    // by an asm that ties their registers: a memory clobber there would hold the next stage's reads back as well. Six and seven tiles
+    // have no registers for either at their occupancy and keep the stage above.
+    using Ahead = CondAhead;
+    const double *sYr = lds + T::YR + (ures ? (lane & 3) : 0);          // (the reference as uyp addresses it)
+    auto fetch_ahead = [&](const int s, auto tsc, Ahead &o) __attribute__((always_inline)) {
         constexpr int Ts = decltype(tsc)::value;
-        for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k += 2) {
-            stage_body(k, tsc, uy[0]);
-            if (k + 1 < N) stage_body(k + 1, tsc, uy[1]);
+        const double *tb = sTab + PAD + 2 * (NMAX - s);
+        o.hr = tb[T::R_HR * ROW + lane];
+        if constexpr (Ts >= 5) o.hr1 = tb[T::R_HR * ROW + l1];
+        o.wl = sWt[s * 6 + lq];
+        static_for<0, Ts - 1>([&](auto tc) { constexpr int Tc = decltype(tc)::value; o.template bop<Tc>() = tb[lq * ROW + 16 * Tc + lc]; });
+    };
+    // ENDS: the call site of the odd k, the stages that may close a segment -- the stage behind such a one has one tile more, and
+    // stage 33 the operands of bank 1
+    auto stage_body_pf = [&](const int k, auto tsc, auto endsc, const Ahead &cur, Ahead &nxt, double &uyq) __attribute__((always_inline)) {
+        constexpr int Ts = decltype(tsc)::value;
+        constexpr bool ENDS = decltype(endsc)::value;
+        constexpr bool B1 = Ts >= 5;                 // columns 64.. exist from stage 33 on
+        const int s = k + 1;
+        const double *tb = sTab + PAD + 2 * (NMAX - s);
+        const double one = 1.0;
+        settle_dpp(res);
+        // the gg row of stage s goes straight to the workspace in the MFMA operand layout the interior point kernel loads it in
+        {
+            const int c_ = (s - 1) >> 2;
+            double *gcs = pa.cws + (size_t)b * NCH * 64 + 16 * ((s - 1) & 3) + lc;
+            if (2 * lq <= c_) gcs[cidx(c_, lq) * 64] = cur.hr;
+            if constexpr (B1) {
+                const int T1 = 4 + lq;
+                if (lane < NB1 && 2 * T1 <= c_) gcs[cidx(c_, T1) * 64] = cur.hr1;
+            }
         }
-    });
+        // the weighted operands of the stage: all of them AHEAD of the matrix instructions (as the column form)
+        double aopv[Ts];
+        static_for<0, Ts - 1>([&](auto kc) { constexpr int K = decltype(kc)::value; aopv[K] = cur.template bop<K>() * cur.wl; });
+        double wr[4], gsr[4], gt[4], gt1[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) wr[r] = sWt[s * 6 + r];          // (the stage's own weights, scaled; stage N: W_e)
+#pragma unroll
+        for (int r = 0; r < 4; r++) gsr[r] = sG[s * 8 + r];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            gt[r] = tb[r * ROW + lane];
+            if constexpr (B1) gt1[r] = tb[r * ROW + l1];
+        }
+        if (k + 1 < N) {
+            fetch_ahead(s + 1, tsc, nxt);
+            if constexpr (ENDS && Ts < NT) {
+                if (k + 1 == 8 * Ts) {          // the next stage opens a segment: one tile more, and stage 33 bank 1's gg-row entry
+                    const double *tbn = tb - 2;          // (the table columns of stage s + 1)
+                    nxt.template bop<Ts>() = tbn[lq * ROW + 16 * Ts + lc];
+                    if constexpr (Ts + 1 >= 5) nxt.hr1 = tbn[T::R_HR * ROW + l1];
+                }
+            }
+        }
+        static_assert(Ts <= 5, "the asm below lists five products");
+        if constexpr (Ts == 1) asm volatile("" : "+v"(aopv[0]));
+        if constexpr (Ts == 2) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]));
+        if constexpr (Ts == 3) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]));
+        if constexpr (Ts == 4) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]), "+v"(aopv[3]));
+        if constexpr (Ts == 5) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]), "+v"(aopv[3]), "+v"(aopv[4]));
+        static_for<0, Ts - 1>([&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            static_for<K, Ts - 1>([&](auto ic) { constexpr int I = decltype(ic)::value; Ht[tidx(K, I)] = mfma(aopv[K], cur.template bop<I>(), Ht[tidx(K, I)]); });
+        });
+        __builtin_amdgcn_sched_barrier(0);          // (the gradient sum and its wait stay behind the matrix instructions)
+        {
+            double a0 = 0.0, a1 = 0.0;
+            static_for<0, 3>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                double gs = gsr[r];
+                fmac_bc<4 + r>(gs, res, one);          // residual + g_s
+                const double e = wr[r] * gs;
+                a0 += e * gt[r];
+                if constexpr (B1) a1 += e * gt1[r];
+            });
+            q0 += a0;
+            if constexpr (B1) q1 += (lane < NB1) ? a1 : 0.0;
+        }
+        // the residuals of the next stage onto their four lanes, the reference of the stage two on behind them: a plain vector write of
+        // a DPP operand -- settle_dpp at the top of the next stage stands between it and the first read
+        if (k + 1 < N) res = ures ? uxr - uyq : res;
+        if (k + 3 < N) uyq = sYr[(k + 4) * 6];
+    };
+    // stage s = k+1 touches columns < 2s, i.e. ceil(s/8) tiles: one instantiation of the stage per segment of 8 stages
+    if constexpr (PF) {
+        Ahead oa, ob;
+        fetch_ahead(1, std::integral_constant<int, 1>(), oa);          // (N >= 1)
+        static_for<1, NT>([&](auto tsc) {
+            constexpr int Ts = decltype(tsc)::value;
+            for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k += 2) {
+                stage_body_pf(k, tsc, std::false_type(), oa, ob, uy[0]);
+                if (k + 1 < N) stage_body_pf(k + 1, tsc, std::true_type(), ob, oa, uy[1]);
+            }
+        });
+    } else {
+        static_for<1, NT>([&](auto tsc) {
+            constexpr int Ts = decltype(tsc)::value;
+            for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k += 2) {
+                stage_body(k, tsc, uy[0]);
+                if (k + 1 < N) stage_body(k + 1, tsc, uy[1]);
+            }
+        });
+    }
     for (int s = N + 1; s <= NMAX; s++) {          // rows beyond the horizon: zeros
         const int c_ = (s - 1) >> 2;
         double *gcs = pa.cws + (size_t)b * NCH * 64 + 16 * ((s - 1) & 3) + lc;
@@ -1137,10 +1289,12 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
                 Ht[tidx(K, K)][jj] += (idx < nv) ? sWt[(idx >> 1) * 6 + 4 + (idx & 1)] : 1.0;
             }
         }
-    if (lane < nv) q0 += sWt[j0 * 6 + 4 + r0] * (sU0[lane] - gyref[j0 * 6 + 4 + r0]);
+    // (the inputs' reference: from the copy in LDS where there is one)
+    auto yref_at = [&](const int idx) __attribute__((always_inline)) { if constexpr (PF) return lds[T::YR + idx]; else return gyref[idx]; };
+    if (lane < nv) q0 += sWt[j0 * 6 + 4 + r0] * (sU0[lane] - yref_at(j0 * 6 + 4 + r0));
     {
         const int j1 = 32 + j0;
-        if (lane < NB1 && 64 + lane < nv) q1 += sWt[j1 * 6 + 4 + r0] * (sU0[64 + lane] - gyref[j1 * 6 + 4 + r0]);
+        if (lane < NB1 && 64 + lane < nv) q1 += sWt[j1 * 6 + 4 + r0] * (sU0[64 + lane] - yref_at(j1 * 6 + 4 + r0));
     }
     // ---- hand-over: H tiles, q (the gg rows went out stage by stage)
     {

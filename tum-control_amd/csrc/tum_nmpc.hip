@@ -1234,7 +1234,7 @@ static int solve_done(tum_ocp *c, SolveKind kind, bool ipm_timed)
 {
     if (c->lpt && c->batch > 1024) {
         if (kind != SOLVE_REPLAY) {
-            hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->dqpiter, c->dorder, c->batch);
+            hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(64), 0, c->stream, c->dqpiter, c->dorder, c->batch);
             HIPCHK(hipGetLastError());
         }
         c->order_valid = true;
@@ -1661,6 +1661,9 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
     if (f == "qp_iter") { HIPCHK(hipMemcpy(out, c->dqpiter + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "status") { HIPCHK(hipMemcpy(out, c->dstatus + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "qp_status") { HIPCHK(hipMemcpy(out, c->dqpstatus + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
+    // the longest-first order the next solve dispatches in (entries b0 .. b0 + nb - 1 of the permutation); the identity map while no
+    // order is kept: a batch of at most 1024, or before the first solve
+    if (f == "lpt_order") { HIPCHK(hipMemcpy(out, c->dorder + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "res") { HIPCHK(hipMemcpy(out, c->dres + (size_t)b0 * 3, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "sqp_iter") { HIPCHK(hipMemcpy(out, c->dsqpiter + b0, sizeof(int) * nb, hipMemcpyDeviceToHost)); return 0; }
     if (f == "residuals") { HIPCHK(hipMemcpy(out, c->dnlpres + (size_t)b0 * 4, sizeof(double) * 4 * nb, hipMemcpyDeviceToHost)); return 0; }

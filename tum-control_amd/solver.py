@@ -428,7 +428,7 @@ class BatchedOcpSolver:
             o = ctypes.c_double(0.0)
             self._chk(self._L.tum_ocp_get_stats(self._h, field.encode(), ctypes.byref(o), 0, 1), "get_stats")
             return o.value
-        if field in ("sqp_iter", "qp_iter", "status", "qp_status"):
+        if field in ("sqp_iter", "qp_iter", "status", "qp_status", "lpt_order"):
             out = np.zeros(self.batch, dtype=np.int32)
             self._chk(self._L.tum_ocp_get_stats(self._h, field.encode(), out.ctypes.data_as(ctypes.c_void_p), 0, self.batch), "get_stats")
             if field == "sqp_iter" and self.batch == 1:
