@@ -584,6 +584,50 @@ int tum_sim_ppo_params(tum_sim *s, float *const *W, float *const *b, float *cons
 /* Adam's state: the moments over the flat parameter vector (n_params doubles each), the step counter, n_params. Any may be NULL. */
 int tum_sim_ppo_state(tum_sim *s, double *m, double *v, long long *t, int *n_params);
 
+/* --- K15: candidate selection of the Bayesian-optimisation step (Learning_To_Adapt/SafeRL_WMPC/BO_WMPC/acquisition.py): the
+ * feasibility-weighted expected hypervolume improvement of C candidates x in [0,1]^d, two objectives, both maximised.
+ * Four exact GPs g (objective 0, 1 on the n_t feasible trials Xt; class 0, 1 of the Dirichlet classification GP on all n_c trials Xc),
+ * each with k_g(x,x') = s_g exp(-1/2 sum_j ((x_j - x'_j) ils_gj)^2), constant mean c_g, a_g = A_g^-1 (y_g - c_g) and V_g = L_A^-1
+ * (A_g = K_g + noise = L_A L_A^T; n x n row-major, the lower triangle is read). Per objective o the baseline Xb (n_b points) with
+ * H_o = K_o(Xb,Xt) V_o^T (n_b x n_t), R_o = chol(K_o(Xb,Xb) - H_o H_o^T + jitter_o I)^-1 (lower), the base samples Z_o (S x n_b) and
+ * zeta_o (S), and per sample s the front of the baseline draw: front_count[s] points of fronts[s] (P_max x 2, ascending in objective
+ * 0), non-dominated and strictly better than ref. For a candidate x and each o:
+ *   k_t = k_o(Xt, x); q = V_o k_t; mu = c_o + k_t . a_o; sig = k_o(Xb, x) - H_o q; l = R_o sig
+ *   d2 = max(s_o - q.q - l.l, jitter_o); f_s,o = mu + Z_o[s] . l + sqrt(d2) zeta_o[s]
+ *   HVI_s = sum_{i=0..P} max(0, min(f_s,0, x_{i+1}) - x_i) max(0, f_s,1 - h_i), x_0 = ref_0, x_i = p_i,0, x_{P+1} = +inf, h_i = p_{i+1},1, h_P = ref_1
+ * and for the classes m_k = c_k + k_c . a_k, v_k = s_k - |V_k k_c|^2, t ~ N(m_1 - m_0, max(v_0 + v_1, 0)):
+ *   p = E sigmoid(t), sd = sqrt(E (sigmoid(t) - p)^2), both by the K-node rule (gh_x, gh_w) for a standard normal: E g = sum w g(m + sd_t x)
+ *   factor = eps p + (1 - eps) sd;  alpha(x) = factor (1 / S) sum_s HVI_s
+ * All pointers are host pointers; the matrices stay on the device across evaluations. keep_gp != 0: the four GPs of the last
+ * tum_bo_model stay (d, n_t, n_c must match; Xt, Xc, ils, a, V, s, c are not read) and only the baseline, the samples, the fronts and
+ * the scalars are replaced -- what appending a pick changes. Limits: d 1..16, n_t and n_c 1..4096, n_b 1..512, S 1..4096,
+ * P_max 1..n_b, K 1..64, any C >= 1 (candidates are processed 512 at a time). No floating-point atomics: the order of every sum
+ * depends on the model's sizes alone, the same call gives the same bits, and a candidate's value does not depend on the others. */
+typedef struct tum_bo tum_bo;
+typedef struct tum_bo_model_desc {
+    int d, n_t, n_b, n_c, S, P_max, K, keep_gp;
+    double eps, ref[2], jitter[2];
+    double s[4], c[4];                  /* objective 0, 1, class 0, 1 */
+    const double *Xt, *Xb, *Xc;         /* n_t x d, n_b x d, n_c x d */
+    const double *ils[4];               /* d inverse length scales each */
+    const double *a[4];                 /* n_t, n_t, n_c, n_c */
+    const double *V[4];                 /* n x n */
+    const double *H[2], *R[2];          /* n_b x n_t, n_b x n_b */
+    const double *Z[2], *zeta[2];       /* S x n_b, S */
+    const double *fronts;               /* S x P_max x 2 */
+    const int *front_count;             /* S */
+    const double *gh_x, *gh_w;          /* K */
+} tum_bo_model_desc;
+enum { TUM_BO_MU0, TUM_BO_MU1, TUM_BO_D20, TUM_BO_D21, TUM_BO_HVI, TUM_BO_P, TUM_BO_SD, TUM_BO_FACTOR, TUM_BO_DETAIL };
+tum_bo *tum_bo_create(int device);
+void tum_bo_free(tum_bo *b);
+int tum_bo_model(tum_bo *b, const tum_bo_model_desc *m);
+/* X: C x d; alpha_out: C; detail_out: NULL or C x TUM_BO_DETAIL. Refused: no model, C < 1, a NaN or an infinity in X. */
+int tum_bo_evaluate(tum_bo *b, const double *X, int C, double *alpha_out, double *detail_out);
+/* Measurement aid: on != 0 times the seven launches of the following evaluations with events; ms_out (NULL or 7 doubles): the
+ * milliseconds of the last evaluation -- kernel values, V products, moments, H product, R product, samples and HVI, final. */
+int tum_bo_profile(tum_bo *b, int on, double *ms_out);
+
 /* development aid: one solve with in-kernel phase timers; out = batch x 12 shader-cycle counters
  * [linearise, condense, ipm-residuals, M assembly, Cholesky, rhs, tri-solves, row updates, (iteration tail), expand+cost] */
 int tum_ocp_profile_phases(tum_ocp *c, long long *out);

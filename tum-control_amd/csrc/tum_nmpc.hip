@@ -26,6 +26,7 @@
 #include "ppo_kernels.hpp"
 #include "sqp_kernels.hpp"
 #include "rti_kernels.hpp"
+#include "bo_kernels.hpp"
 
 using namespace tum;
 
@@ -2199,3 +2200,4 @@ extern "C" int tum_ocp_constraints_get(tum_ocp *c, int stage, const char *field,
 // the device closed loop on the capsule above, host code like the rest of this file in headers of its own
 #include "sim_loop.hpp"          // K8 / K9: tum_sim, the control step, segment scoring, the getters
 #include "sim_rl.hpp"            // K11 to K14: the RL environment, the agent, collection, the trainer
+#include "bo.hpp"                // K15: tum_bo, the acquisition value of the Bayesian-optimisation step

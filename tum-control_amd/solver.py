@@ -80,6 +80,9 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout",
              "tum_sim_policy_attach_value", "tum_sim_policy_eval_ac", "tum_sim_gae", "tum_sim_env_collect",
              "tum_sim_ppo_attach", "tum_sim_ppo_detach", "tum_sim_ppo_step", "tum_sim_ppo_update", "tum_sim_ppo_params", "tum_sim_ppo_state"]
+# the entry points of the Bayesian-optimisation step (bo.py), declared in the same header; a list of their own because
+# tests/test_host_logic.py::test_cabi_exports_every_declared_symbol holds C_SYMBOLS to the tum_ocp / tum_pce / tum_sim / tum_planner names
+BO_SYMBOLS = ["tum_bo_create", "tum_bo_free", "tum_bo_model", "tum_bo_evaluate", "tum_bo_profile"]
 
 
 def load_library(path=None):
@@ -179,6 +182,12 @@ def load_library(path=None):
         L.tum_sim_ppo_update.argtypes = [vp, ci, dp, ip, dp, dp, dp, ip, ci, ci, cd, dp]
         L.tum_sim_ppo_params.argtypes = [vp, pvp, pvp, pvp, pvp]
         L.tum_sim_ppo_state.argtypes = [vp, dp, dp, ctypes.POINTER(ctypes.c_longlong), ip]
+    if hasattr(L, "tum_bo_create"):
+        L.tum_bo_create.restype = vp; L.tum_bo_create.argtypes = [ci]
+        L.tum_bo_free.restype = None; L.tum_bo_free.argtypes = [vp]
+        L.tum_bo_model.argtypes = [vp, vp]
+        L.tum_bo_evaluate.argtypes = [vp, dp, ci, dp, dp]
+        L.tum_bo_profile.argtypes = [vp, ci, dp]
     _libs[p] = L
     if p == LIB_PATH:
         _lib = L
