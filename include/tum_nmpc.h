@@ -628,6 +628,34 @@ int tum_bo_evaluate(tum_bo *b, const double *X, int C, double *alpha_out, double
  * milliseconds of the last evaluation -- kernel values, V products, moments, H product, R product, samples and HVI, final. */
 int tum_bo_profile(tum_bo *b, int on, double *ms_out);
 
+/* --- K16: fitting the surrogates of the Bayesian-optimisation step: the exact marginal log-likelihood of one GP and its gradient.
+ * Data X (n x d), y (n) and a fixed noise per point (NULL: none); hyperparameters theta = [log ls (d), log s, c, log noise]:
+ *   A = s exp(-1/2 sum_j ((x_ij - x_kj) / ls_j)^2) + diag(fixed + noise_floor + [learn_noise] e^theta_noise) = L L^T
+ *   MLL = -1/2 r^T A^-1 r - sum_i log L_ii - 1/2 n log 2 pi,  r = y - c
+ * and, with alpha = A^-1 r and W = alpha alpha^T - A^-1, the gradient in the order of theta:
+ *   d / d log ls_j = 1/2 sum_ik W_ik K_ik ((x_ij - x_kj) / ls_j)^2     (K: the kernel alone, without the noise)
+ *   d / d log s    = 1/2 sum_ik W_ik K_ik
+ *   d / d c        = sum_i alpha_i
+ *   d / d log noise = 1/2 e^theta_noise tr W                            (0 where learn_noise is 0)
+ * ok: 1 where the factorisation met positive finite pivots only, the MLL is finite and min L_ii > 1e-7 sqrt(s); a matrix that is not
+ * positive definite is a result, not an error: a failed pivot is replaced by 1, the chain finishes and ok is 0.
+ * The factorisation is a blocked right-looking Cholesky (64 x 64 blocks, panel and trailing update on the matrix cores), V = L^-1 is
+ * formed block-wise and A^-1 = V^T V. No floating-point atomics: the order of every sum depends on n and d alone; the same call
+ * gives the same bits, also after a larger problem on the same handle. All pointers are host pointers. Limits: n 1..4096, d 1..16;
+ * three n x n matrices (n padded to 64) live on the device, allocated at the first tum_gp_data that needs them and grown on demand.
+ * Refused: a null argument, n or d out of range, a NaN or an infinity in X, y, the noise or theta, an evaluation before the data. */
+typedef struct tum_gp tum_gp;
+tum_gp *tum_gp_create(int device);
+void tum_gp_free(tum_gp *g);
+int tum_gp_data(tum_gp *g, const double *X, const double *y, const double *fixed_noise, int n, int d);
+/* grad_out: NULL (the value only: A^-1 is not formed) or d + 3 doubles. */
+int tum_gp_mll(tum_gp *g, const double *theta, int learn_noise, double noise_floor, double *mll_out, double *grad_out, int *ok_out);
+/* What tum_bo_model takes of a fitted GP: V_out = L^-1 (n x n row-major, zero above the diagonal), a_out = A^-1 (y - c). */
+int tum_gp_factor(tum_gp *g, const double *theta, int learn_noise, double noise_floor, double *V_out, double *a_out, int *ok_out);
+/* Measurement aid: on != 0 times the following calls with events; ms_out (NULL or 7 doubles): the milliseconds of the last call --
+ * kernel matrix, Cholesky, V = L^-1, A^-1 = V^T V, w and alpha, gradient tiles, reduction. */
+int tum_gp_profile(tum_gp *g, int on, double *ms_out);
+
 /* development aid: one solve with in-kernel phase timers; out = batch x 12 shader-cycle counters
  * [linearise, condense, ipm-residuals, M assembly, Cholesky, rhs, tri-solves, row updates, (iteration tail), expand+cost] */
 int tum_ocp_profile_phases(tum_ocp *c, long long *out);

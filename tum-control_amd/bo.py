@@ -6,6 +6,7 @@ everything around it is torch float64 / numpy on the host. botorch and gpytorch 
 of the same mathematics (INTEGRATION.md lists the differences).
 
   fit_gp, ObjectiveModel, ConstraintModel      exact GPs with ARD RBF kernels, fitted by L-BFGS on the marginal log-likelihood
+  gp_mll_grad_host, DeviceGP                    likelihood, gradient and factor of one GP: numpy statement and the device path
   pack_model, append_pick                       the arrays tum_bo_model takes; a pick appended to the baseline without refactoring
   host_acquisition, HostAcquisition             numpy statement of the acquisition value (the CPU path)
   DeviceAcquisition                             the device path
@@ -205,10 +206,11 @@ class PackedModel:
         return np.ascontiguousarray(self.Zfull[:, self.n_b, o])
 
 
-def pack_model(Xt, Y, obj_hyp, Xc, feasible, cls_hyp, Xb, Z, ref, eps=0.8, jitter=1e-8, K=64, alpha_eps=0.001):
+def pack_model(Xt, Y, obj_hyp, Xc, feasible, cls_hyp, Xb, Z, ref, eps=0.8, jitter=1e-8, K=64, alpha_eps=0.001, factor=None):
     """Xt (n_t x d) feasible trials with Y (n_t x 2, the units the GPs model); obj_hyp two GPHyper; Xc (n_c x d) all trials with their
     feasibility flags; cls_hyp two GPHyper whose noise is the LEARNED extra noise (the fixed Dirichlet noise is added here); Xb the
-    baseline; Z (S x ncol x 2, ncol >= n_b + 1) base samples; ref the reference point in the units of Y."""
+    baseline; Z (S x ncol x 2, ncol >= n_b + 1) base samples; ref the reference point in the units of Y. factor: what forms the four
+    (V, a), gp_factor by default or a callable of its signature such as DeviceGP.gp_factor."""
     Xt, Xb, Xc = (np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64))) for a in (Xt, Xb, Xc))
     Y = np.asarray(Y, dtype=np.float64).reshape(len(Xt), 2)
     d = Xt.shape[1]
@@ -216,9 +218,10 @@ def pack_model(Xt, Y, obj_hyp, Xc, feasible, cls_hyp, Xb, Z, ref, eps=0.8, jitte
         raise ValueError("pack_model: the base samples need n_b + 1 columns")
     targets, fixed = dirichlet_targets(feasible, alpha_eps)
     hyps = [obj_hyp[0], obj_hyp[1]] + [replace(cls_hyp[k], noise=fixed[:, k] + np.asarray(cls_hyp[k].noise)) for k in range(2)]
+    factor = gp_factor if factor is None else factor
     V, a = [], []
     for g, h in enumerate(hyps):
-        Vg, ag = gp_factor(Xt if g < 2 else Xc, Y[:, g] if g < 2 else targets[:, g - 2], h)
+        Vg, ag = factor(Xt if g < 2 else Xc, Y[:, g] if g < 2 else targets[:, g - 2], h)
         V.append(Vg); a.append(ag)
     jit = np.broadcast_to(np.asarray(jitter, dtype=np.float64), (2,)).copy()
     gh_x, gh_w = gauss_hermite(K)
@@ -520,13 +523,185 @@ def gp_mll(X, y, hyp, fixed_noise=None, noise_floor=0.0):
     return float(_mll_torch(theta, X, y, fn, True, noise_floor)[0])
 
 
-def fit_gp(X, y, fixed_noise=None, learn_noise=True, noise_floor=1e-6, init=None, max_iter=100, device="cpu", return_trace=False):
+def gp_mll_grad_host(X, y, theta, fixed_noise=None, learn_noise=True, noise_floor=0.0):
+    """The numpy statement of the device chain (csrc/gp_kernels.hpp; include/tum_nmpc.h states the mathematics): the marginal
+    log-likelihood at theta = [log ls (d), log s, c, log noise], its analytic gradient from W = alpha alpha^T - A^-1, and ok.
+    Returns (mll, grad (d + 3), ok); a matrix numpy's Cholesky refuses gives (nan, nans, False)."""
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    y, theta = np.asarray(y, dtype=np.float64).reshape(-1), np.asarray(theta, dtype=np.float64)
+    n, d = X.shape
+    ils, s, c = np.exp(-theta[:d]), float(np.exp(theta[d])), float(theta[d + 1])
+    learned = float(np.exp(theta[d + 2])) if learn_noise else 0.0
+    fixed = np.zeros(n) if fixed_noise is None else np.asarray(fixed_noise, dtype=np.float64)
+    T2 = [((X[:, j, None] - X[None, :, j]) * ils[j]) ** 2 for j in range(d)]
+    R = np.zeros((n, n))
+    for t2 in T2:
+        R += t2
+    K = s * np.exp(-0.5 * R)
+    A = K.copy()
+    A[np.diag_indices_from(A)] += (fixed + noise_floor) + learned
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        return float("nan"), np.full(d + 3, np.nan), False
+    V = _tri_inv(L)
+    w = V @ (y - c)
+    alpha = V.T @ w
+    mll = (-0.5 * (w @ w) - np.log(np.diag(L)).sum()) - 0.5 * n * np.log(2.0 * np.pi)
+    WK = (np.outer(alpha, alpha) - V.T @ V) * K
+    grad = np.array([0.5 * (WK * t2).sum() for t2 in T2] +
+                    [0.5 * WK.sum(), alpha.sum(), 0.5 * learned * ((alpha @ alpha) - (V * V).sum()) if learn_noise else 0.0])
+    ok = bool(np.isfinite(L).all() and np.isfinite(mll) and np.diag(L).min() > 1e-7 * np.exp(0.5 * theta[d]))
+    return float(mll), grad, ok
+
+
+class DeviceGP:
+    """The marginal log-likelihood of one GP, its gradient and its factor on the device: tum_gp_create / tum_gp_data / tum_gp_mll /
+    tum_gp_factor (csrc/gp_kernels.hpp). One handle serves any number of GPs one after the other; its three n x n matrices grow on
+    demand. There is no CPU fallback behind it."""
+
+    def __init__(self, device=0):
+        from . import solver
+        self._L = solver.load_library()
+        self._h = self._L.tum_gp_create(int(device))
+        if not self._h:
+            raise Exception("tum_gp_create: " + self._L.tum_ocp_last_error().decode())
+        self.n = self.d = None
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise Exception(f"{what}: " + self._L.tum_ocp_last_error().decode())
+
+    def set_data(self, X, y, fixed_noise=None):
+        dp = ctypes.POINTER(ctypes.c_double)
+        X = np.ascontiguousarray(np.atleast_2d(np.asarray(X, dtype=np.float64)))
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+        if len(y) != len(X):
+            raise Exception(f"tum_gp_data: y has {len(y)} entries, X has {len(X)} rows")
+        fn = None if fixed_noise is None else np.ascontiguousarray(np.broadcast_to(np.asarray(fixed_noise, dtype=np.float64), (len(X),)))
+        self.n = self.d = None
+        self._check(self._L.tum_gp_data(self._h, X.ctypes.data_as(dp), y.ctypes.data_as(dp), None if fn is None else fn.ctypes.data_as(dp),
+                                        X.shape[0], X.shape[1]), "tum_gp_data")
+        self.n, self.d = X.shape
+
+    def _theta(self, theta, what):
+        theta = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(-1))
+        if self.d is not None and len(theta) != self.d + 3:
+            raise Exception(f"{what}: theta has {len(theta)} entries, the data have d + 3 = {self.d + 3}")
+        return theta
+
+    def mll_grad(self, theta, learn_noise=True, noise_floor=0.0, grad=True):
+        """(mll, grad (d + 3), ok) at theta = [log ls (d), log s, c, log noise]; grad=False: (mll, None, ok), A^-1 is not formed."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        theta = self._theta(theta, "tum_gp_mll")
+        mll, ok = ctypes.c_double(), ctypes.c_int()
+        g = np.zeros(len(theta)) if grad else None
+        self._check(self._L.tum_gp_mll(self._h, theta.ctypes.data_as(dp), int(bool(learn_noise)), float(noise_floor), ctypes.byref(mll),
+                                       g.ctypes.data_as(dp) if grad else None, ctypes.byref(ok)), "tum_gp_mll")
+        return mll.value, g, bool(ok.value)
+
+    def factor(self, hyp):
+        """V = L^-1 and a = A^-1 (y - c) at a GPHyper on the data of set_data; hyp.noise (a scalar) is added to their fixed noise."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        theta = self._theta(np.concatenate([np.log(hyp.ls), [np.log(hyp.s), hyp.c, 0.0]]), "tum_gp_factor")
+        if self.n is None:
+            raise Exception("tum_gp_factor: no data (tum_gp_data first)")
+        V, a, ok = np.zeros((self.n, self.n)), np.zeros(self.n), ctypes.c_int()
+        self._check(self._L.tum_gp_factor(self._h, theta.ctypes.data_as(dp), 0, float(hyp.noise), V.ctypes.data_as(dp), a.ctypes.data_as(dp),
+                                          ctypes.byref(ok)), "tum_gp_factor")
+        if not ok.value:
+            raise ModelFittingError("GP kernel matrix: not positive definite on the device")
+        return V, a
+
+    def gp_factor(self, X, y, hyp):
+        """gp_factor's signature (pack_model's factor=): hyp.noise is the whole noise, a scalar or one value per point."""
+        self.set_data(X, y, fixed_noise=hyp.noise)
+        return self.factor(replace(hyp, noise=0.0))
+
+    def profile(self, on=True):
+        """Time the kernels of the following calls; returns the seven times (ms) of the last one: kernel matrix, Cholesky, V = L^-1,
+        A^-1 = V^T V, w and alpha, gradient tiles, reduction."""
+        ms = np.zeros(7)
+        self._check(self._L.tum_gp_profile(self._h, int(on), ms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "tum_gp_profile")
+        return ms
+
+    def close(self):
+        if self._h:
+            self._L.tum_gp_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fit_gp_device(Xn, y, fixed_noise, learn_noise, noise_floor, init, max_iter, return_trace, gp):
+    """fit_gp's optimiser around DeviceGP.mll_grad: the same L-BFGS, options, box, start and refusals; theta lives on the host."""
+    import torch
+    yn = np.asarray(y, dtype=np.float64).reshape(-1)
+    n, d = Xn.shape
+    own = gp is None
+    if own:
+        gp = DeviceGP()
+    try:
+        gp.set_data(Xn, yn, fixed_noise)
+        if init is None:
+            yt = torch.as_tensor(yn, dtype=torch.float64)
+            init = GPHyper(c=float(yt.mean()), s=max(float(yt.var()) if len(yt) > 1 else 1.0, 1e-3), ls=np.full(d, 0.5), noise=1e-2)
+        theta0 = torch.tensor(np.concatenate([np.log(init.ls), [np.log(init.s), init.c, np.log(init.noise)]]), dtype=torch.float64)
+        theta = theta0.clone().requires_grad_(True)
+        start, _, ok = gp.mll_grad(theta0.numpy(), learn_noise, noise_floor, grad=False)
+        if not ok:
+            raise ModelFittingError("fit_gp: the kernel matrix at the initial hyperparameters is not positive definite")
+        opt = torch.optim.LBFGS([theta], lr=1.0, max_iter=int(max_iter), tolerance_grad=1e-8, tolerance_change=1e-12, history_size=10,
+                                line_search_fn="strong_wolfe")
+        lo = torch.tensor([np.log(1e-2)] * d + [np.log(1e-3), -20.0, np.log(1e-8)], dtype=torch.float64)
+        hi = torch.tensor([np.log(1e1)] * d + [np.log(1e3), 20.0, np.log(1e2)], dtype=torch.float64)
+
+        def closure():
+            opt.zero_grad()
+            t = theta.detach()
+            th = torch.maximum(torch.minimum(t, hi), lo)
+            if not torch.isfinite(th).all():
+                return torch.tensor(float("inf"), dtype=torch.float64)
+            mll, g, ok = gp.mll_grad(th.numpy(), learn_noise, noise_floor)
+            if not ok:
+                return torch.tensor(float("inf"), dtype=torch.float64)
+            inside = ((t >= lo) & (t <= hi)).to(torch.float64)          # (the clamp passes no gradient to a component outside the box)
+            theta.grad = torch.as_tensor(-g / n, dtype=torch.float64) * inside
+            return torch.tensor(-mll / n, dtype=torch.float64)
+        opt.step(closure)
+        th = torch.maximum(torch.minimum(theta.detach(), hi), lo)
+        if not torch.isfinite(th).all():
+            raise ModelFittingError("fit_gp: the kernel matrix at the fitted hyperparameters is not positive definite")
+        end, _, ok = gp.mll_grad(th.numpy(), learn_noise, noise_floor, grad=False)
+        if not ok:
+            raise ModelFittingError("fit_gp: the kernel matrix at the fitted hyperparameters is not positive definite")
+        if float(end) < float(start):          # (a line search that ended on a failed evaluation: keep the start)
+            th, end = theta0, start
+        t = th.numpy()
+        hyp = GPHyper(c=float(t[d + 1]), s=float(np.exp(t[d])), ls=np.exp(t[:d]), noise=float(noise_floor + (np.exp(t[d + 2]) if learn_noise else 0.0)))
+        return (hyp, float(start), float(end)) if return_trace else hyp
+    finally:
+        if own:
+            gp.close()
+
+
+def fit_gp(X, y, fixed_noise=None, learn_noise=True, noise_floor=1e-6, init=None, max_iter=100, device="cpu", return_trace=False,
+           backend="torch", gp=None):
     """Maximise the exact marginal log-likelihood over log length scales, log output scale, the constant mean and (learn_noise) the log
     of a scalar noise, by L-BFGS (strong Wolfe) in torch.float64 on `device`. noise = fixed_noise + noise_floor + learned. A kernel
     matrix that is not numerically positive definite raises ModelFittingError. Returns a GPHyper (noise: the learned scalar plus the
-    floor; the caller adds its fixed noise)."""
+    floor; the caller adds its fixed noise). backend "device": likelihood and gradient come from DeviceGP.mll_grad (gp: the handle
+    to use; created and closed here otherwise), the optimiser is the same and runs on the host; `device` is not used."""
     import torch
     Xn = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    if backend == "device":
+        return _fit_gp_device(Xn, y, fixed_noise, learn_noise, noise_floor, init, max_iter, return_trace, gp)
+    if backend != "torch":
+        raise ValueError(f"fit_gp: backend {backend!r} is neither 'torch' nor 'device'")
     X = torch.as_tensor(Xn, dtype=torch.float64, device=device)
     yt = torch.as_tensor(np.asarray(y, dtype=np.float64).reshape(-1), dtype=torch.float64, device=device)
     d = X.shape[1]
@@ -580,17 +755,17 @@ def standardize(Y):
 class ObjectiveModel:
     """One exact GP per objective on the feasible trials, Y standardised."""
 
-    def __init__(self, X, Y, device="cpu", max_iter=100):
+    def __init__(self, X, Y, device="cpu", max_iter=100, backend="torch", gp=None):
         self.X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         self.Ys, self.mean, self.std = standardize(Y)
-        self.hyp = [fit_gp(self.X, self.Ys[:, o], device=device, max_iter=max_iter) for o in range(2)]
+        self.hyp = [fit_gp(self.X, self.Ys[:, o], device=device, max_iter=max_iter, backend=backend, gp=gp) for o in range(2)]
 
 
 class ConstraintModel:
     """The two-class Dirichlet classification GP on all trials (surrogate_models.py:66-160): one GP per class on the transformed
     targets with their fixed noise and a learned extra noise; constant mean initialised at 1."""
 
-    def __init__(self, X, feasible, device="cpu", max_iter=100, alpha_eps=0.001):
+    def __init__(self, X, feasible, device="cpu", max_iter=100, alpha_eps=0.001, backend="torch", gp=None):
         self.X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         self.feasible = np.asarray(feasible).astype(bool)
         targets, fixed = dirichlet_targets(self.feasible, alpha_eps)
@@ -598,7 +773,8 @@ class ConstraintModel:
         self.hyp = []
         for k in range(2):
             init = GPHyper(c=1.0, s=max(float(np.var(targets[:, k])), 1.0), ls=np.full(d, 0.5), noise=1e-2)
-            self.hyp.append(fit_gp(self.X, targets[:, k], fixed_noise=fixed[:, k], init=init, device=device, max_iter=max_iter))
+            self.hyp.append(fit_gp(self.X, targets[:, k], fixed_noise=fixed[:, k], init=init, device=device, max_iter=max_iter,
+                                   backend=backend, gp=gp))
 
 
 # ------------------------------------------------------------------------------------------------ trials
@@ -642,11 +818,14 @@ class BayesianOptimization:
     The reference standardises Y for the GP but hands the acquisition the reference point in raw units; that is kept as the default
     (config standardize_ref_point=False); True maps the reference point into the standardised units."""
 
-    def __init__(self, bounds, config, objective, acq="device", fit_device="cpu"):
+    def __init__(self, bounds, config, objective, acq="device", fit_device="cpu", fit_backend="torch"):
         self.bounds = np.asarray(bounds, dtype=np.float64)
         self.d = self.bounds.shape[1]
         self.config = dict(DEFAULT_CONFIG); self.config.update(config or {})
         self.objective, self.acq, self.fit_device = objective, acq, fit_device
+        if fit_backend not in ("torch", "device"):
+            raise ValueError(f"BayesianOptimization: fit_backend {fit_backend!r} is neither 'torch' nor 'device'")
+        self.fit_backend, self._gp = fit_backend, None          # (one DeviceGP for every fit and factor of the campaign)
         self.ref = np.array([self.config["reference_point_0"], self.config["reference_point_1"]], dtype=np.float64)
         self.trials, self.active_group = [], 0
         self.hypervolumes, self.hv_traces, self.pareto_trials = [0.0, 0.0], [], [[], []]
@@ -705,15 +884,18 @@ class BayesianOptimization:
         cfg = self.config
         Xn, feas, obj = self._arrays()
         Xt, Y = Xn[feas], obj[feas][:, group, :]
-        om = ObjectiveModel(Xt, Y, device=self.fit_device, max_iter=cfg["fit_max_iter"])
-        cm = ConstraintModel(Xn, feas, device=self.fit_device, max_iter=cfg["fit_max_iter"])
+        if self.fit_backend == "device" and self._gp is None:
+            self._gp = DeviceGP()
+        om = ObjectiveModel(Xt, Y, device=self.fit_device, max_iter=cfg["fit_max_iter"], backend=self.fit_backend, gp=self._gp)
+        cm = ConstraintModel(Xn, feas, device=self.fit_device, max_iter=cfg["fit_max_iter"], backend=self.fit_backend, gp=self._gp)
         ref = (self.ref[group] - om.mean) / om.std if cfg["standardize_ref_point"] else self.ref[group]
         S, q = int(cfg["n_sobol_samples"]), int(cfg["batch_size"])
         keep = prune_baseline(Xt, om.Ys, om.hyp, S=S, seed=[int(cfg["seed"]), 11, len(self.trials)], jitter=cfg["jitter"]) \
             if cfg["prune_baseline"] else np.arange(len(Xt))
         keep = keep[:NB_MAX - q - 1]
         Z = sobol_normal(S, 2 * (len(keep) + q + 1), [int(cfg["seed"]), 13, len(self.trials)]).reshape(S, 2, -1).transpose(0, 2, 1)
-        return pack_model(Xt, om.Ys, om.hyp, Xn, feas, cm.hyp, Xt[keep], Z, ref, eps=cfg["epsilon"], jitter=cfg["jitter"], K=cfg["gh_nodes"])
+        return pack_model(Xt, om.Ys, om.hyp, Xn, feas, cm.hyp, Xt[keep], Z, ref, eps=cfg["epsilon"], jitter=cfg["jitter"], K=cfg["gh_nodes"],
+                          factor=self._gp.gp_factor if self._gp is not None else None)
 
     def perform_bayesian_optimization_step(self):
         """One iteration: fit, select batch_size candidates, evaluate them. Returns (t_fit, t_select, t_evaluate), or None where the

@@ -27,6 +27,7 @@
 #include "sqp_kernels.hpp"
 #include "rti_kernels.hpp"
 #include "bo_kernels.hpp"
+#include "gp_kernels.hpp"
 
 using namespace tum;
 
@@ -2201,3 +2202,4 @@ extern "C" int tum_ocp_constraints_get(tum_ocp *c, int stage, const char *field,
 #include "sim_loop.hpp"          // K8 / K9: tum_sim, the control step, segment scoring, the getters
 #include "sim_rl.hpp"            // K11 to K14: the RL environment, the agent, collection, the trainer
 #include "bo.hpp"                // K15: tum_bo, the acquisition value of the Bayesian-optimisation step
+#include "gp.hpp"                // K16: tum_gp, the marginal log-likelihood of a surrogate and its factor

@@ -83,6 +83,8 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
 # the entry points of the Bayesian-optimisation step (bo.py), declared in the same header; a list of their own because
 # tests/test_host_logic.py::test_cabi_exports_every_declared_symbol holds C_SYMBOLS to the tum_ocp / tum_pce / tum_sim / tum_planner names
 BO_SYMBOLS = ["tum_bo_create", "tum_bo_free", "tum_bo_model", "tum_bo_evaluate", "tum_bo_profile"]
+# the entry points of the surrogate fit (bo.DeviceGP), a list of their own for the same reason
+GP_SYMBOLS = ["tum_gp_create", "tum_gp_free", "tum_gp_data", "tum_gp_mll", "tum_gp_factor", "tum_gp_profile"]
 
 
 def load_library(path=None):
@@ -188,6 +190,13 @@ def load_library(path=None):
         L.tum_bo_model.argtypes = [vp, vp]
         L.tum_bo_evaluate.argtypes = [vp, dp, ci, dp, dp]
         L.tum_bo_profile.argtypes = [vp, ci, dp]
+    if hasattr(L, "tum_gp_create"):
+        L.tum_gp_create.restype = vp; L.tum_gp_create.argtypes = [ci]
+        L.tum_gp_free.restype = None; L.tum_gp_free.argtypes = [vp]
+        L.tum_gp_data.argtypes = [vp, dp, dp, dp, ci, ci]
+        L.tum_gp_mll.argtypes = [vp, dp, ci, ctypes.c_double, dp, dp, ip]
+        L.tum_gp_factor.argtypes = [vp, dp, ci, ctypes.c_double, dp, dp, ip]
+        L.tum_gp_profile.argtypes = [vp, ci, dp]
     _libs[p] = L
     if p == LIB_PATH:
         _lib = L
