@@ -84,6 +84,62 @@ def test_host_statement_reports_a_singular_matrix():
     assert not bo.gp_mll_grad_host(X, y, th, None, False, 0.0)[2]
 
 
+def test_block_wise_reference_equals_the_whole_matrix_reference():
+    """Clustered data (gp_reference.clustered_data): the sums and concatenations of the clusters' long-double results against the
+    long-double results of the whole matrix, within 1 u x scale (both are long double: 2^-11 u per operation; measured 0.001 u for
+    the MLL and 0.04 u for the gradient). V is exactly 0 outside the clusters' blocks in both."""
+    sizes, d = (37, 70, 23), 3
+    LDT = np.longdouble
+    for noise, learn in ((False, True), (True, True), (True, False)):
+        X, y, fixed = gref.clustered_data(sizes, d, seed=11, noise=noise)
+        th = np.concatenate([np.log([0.5, 0.9, 1.2]), [np.log(1.3), 0.1, np.log(0.02)]])
+        whole = gref.mll_grad(X, y, th, fixed, learn, 1e-6)
+        block = gref.block_mll_grad(sizes, X, y, th, fixed, learn, 1e-6)
+        e = gref.errors(block[0], block[1], whole)
+        print(f"gp_bounds block-wise against whole noise={noise} learn={learn}: mll {e[0]:.4f} grad {e[1]:.4f} (u x scale)")
+        assert e[0] <= 1.0 and e[1] <= 1.0
+        assert abs(block[2] - whole[2]) <= 1e-12 * whole[2] and abs(block[3] - whole[3]) <= 1e-12 * whole[3]
+        hyp = bo.GPHyper(c=0.1, s=1.3, ls=np.exp(th[:d]), noise=0.05 if fixed is None else fixed + 0.05)
+        Vw, aw = gref.factor(X, y, hyp)
+        Vb, ab = gref.block_factor(sizes, X, y, hyp)
+        assert Vb.dtype == LDT and ab.dtype == LDT
+        assert float(np.abs(Vw - Vb).max()) <= U * float(np.abs(Vw).max()) and float(np.abs(aw - ab).max()) <= U * float(np.abs(aw).max())
+        inside = np.zeros((len(X), len(X)), dtype=bool)
+        for b in gref._blocks(sizes):
+            inside[b, b] = True
+        assert (Vb[~inside] == 0).all() and (Vw[~inside] == 0).all() and (np.tril(Vb)[inside] != 0).sum() == sum(s * (s + 1) // 2 for s in sizes)
+    with pytest.raises(AssertionError):
+        gref.clustered_data((64, 70), d, seed=0)          # (a cluster that ends on a tile edge)
+    for n in (1409, 4033, 4096):
+        assert sum(gref.cluster_sizes(n)) == n
+        gref.clustered_data(gref.cluster_sizes(n), 1, seed=0)
+
+
+def test_campaign_fixture_reloads_and_belongs_to_the_data(golden_dir):
+    """tests/golden/gp_campaign.npz (make_gp_golden.py): the split long doubles join exactly, and the stored MLL of every (class,
+    theta) is the MLL bo.gp_mll_grad_host gives on the 2050 trials within 1e-9 relative -- a check that the fixture belongs to the
+    data, not a bound on the host statement."""
+    z = np.load(os.path.join(golden_dir, "gp_campaign.npz"))
+    t = np.load(os.path.join(golden_dir, "bo_trials_F.npz"))
+    Xn = t["params_nor"]
+    targets, fixed = bo.dirichlet_targets(t["feasible"])
+    assert Xn.shape == (2050, 7) and list(z["rows"]) == [63, 64, 1023, 1024, 2047, 2048, 2049]
+    for k in range(2):
+        for e in range(2):
+            tag = f"{k}_{e}"
+            th = z["theta_" + tag]
+            mll = gref.join(z[f"mll_{tag}_hi"], z[f"mll_{tag}_lo"])
+            grad, a, V = (gref.join(z[f"{q}_{tag}_hi"], z[f"{q}_{tag}_lo"]) for q in ("grad", "a", "V"))
+            assert th.shape == (10,) and grad.shape == (10,) and a.shape == (2050,) and V.shape == (7, 2050) and z["scale_" + tag].shape == (2,)
+            assert mll.dtype == np.longdouble and float(mll) == float(z[f"mll_{tag}_hi"]) and np.isfinite(V.astype(np.float64)).all()
+            for i, r in enumerate(z["rows"]):
+                assert (V[i, r + 1:] == 0).all() and V[i, r] > 0
+            assert float(np.abs(grad).max()) == z["scale_" + tag][1] and float(np.abs(V).max()) <= float(z["vmax_" + tag])
+            hm, _, ok = bo.gp_mll_grad_host(Xn, targets[:, k], th, fixed[:, k], True, float(z["noise_floor"]))
+            assert ok and abs(hm - float(mll)) <= 1e-9 * abs(float(mll)), (tag, hm, float(mll))
+        assert not (z[f"theta_{k}_0"] == z[f"theta_{k}_1"]).all()
+
+
 def test_defaults_return_what_the_explicit_keywords_return():
     """fit_gp without the keyword against backend="torch", pack_model without it against factor=bo.gp_factor: equal to the bit."""
     X, y = _fit_data()

@@ -126,6 +126,55 @@ def test_real_shape_first_300_trials(acq, golden_dir):
     _gate(acq, m, X, "fixture[:300] n_t=%d S=128 C=%d" % (len(Xt), len(X)))
 
 
+_CAMPAIGN = []
+S_CAMPAIGN = 1000
+
+
+def _campaign_model(golden_dir):
+    """The model of test_real_shape_first_300_trials from all 2050 trials: n_c = 2050, n_t = n_b = 194, packed once per module."""
+    if not _CAMPAIGN:
+        z = np.load(os.path.join(golden_dir, "bo_trials_F.npz"))
+        Xn, feas, obj = z["params_nor"], z["feasible"], z["objectives"]
+        Xt = Xn[feas]
+        assert len(Xn) == 2050 and len(Xt) == 194
+        Ys = bo.standardize(obj[feas][:, 0, :])[0]
+        o_h, c_h = ref.hypers(7)
+        S = S_CAMPAIGN
+        Z = bo.sobol_normal(S, 2 * (len(Xt) + 2), 4).reshape(S, 2, -1).transpose(0, 2, 1)
+        _CAMPAIGN.append((bo.pack_model(Xt, Ys, o_h, Xn, feas, c_h, Xt, Z, np.array([-0.5, -0.75]), eps=0.8, jitter=1e-6, K=64), Xt))
+    return _CAMPAIGN[0]
+
+
+def test_real_shape_all_2050_trials(acq, golden_dir):
+    """The shape every step of the logged campaign has: n_c = 2050 (row-tile chains of 129 tiles over the class factors, offsets into
+    them past 2^22 doubles), n_t = n_b = 194, K = 64. S = 1000 samples: no multiple of 16, so the sample mask is live (the
+    long-double reference takes about 5 s of the CPU at this S). 17 Sobol candidates and 3 trial points: two column tiles, one
+    partial."""
+    m, Xt = _campaign_model(golden_dir)
+    X = np.vstack([bo.sobol_points(17, 7, 5), Xt[:3]])
+    _gate(acq, m, X, "fixture[:2050] n_t=%d S=%d C=%d" % (len(Xt), m.S, len(X)))
+
+
+def test_alone_and_inside_a_batch_same_bits_at_the_campaign_shape(acq, golden_dir):
+    m, _ = _campaign_model(golden_dir)
+    acq.set_model(m)
+    X = np.random.default_rng(14).random((600, 7))
+    a600, d600 = acq.evaluate(X, detail=True)          # (two passes of the chain: 512 + 88)
+    assert np.isfinite(a600).all() and np.isfinite(d600).all() and a600.max() > 0
+    for i in (0, 15, 16, 511, 512, 599):
+        a1, d1 = acq.evaluate(X[i:i + 1], detail=True)
+        assert a1[0] == a600[i] and (d1[0] == d600[i]).all(), i
+
+
+def test_acquisition_at_the_size_limits(acq):
+    """n_b = 512 (BO_MAXB) and S = 4096 (BO_MAXS) at once; the baseline repeats draws behind the 40 trials."""
+    shape = (7, 40, 512, 130, 4096, 20, 8)
+    d, n_t, n_b, n_c, S, C, K = shape
+    m = ref.generate(d, n_t, n_b, n_c, S, K, seed=sum(shape))
+    X = np.random.default_rng(1 + sum(shape)).random((C, d))
+    _gate(acq, m, X, "d=%d n_t=%d n_b=%d n_c=%d S=%d C=%d K=%d" % shape)
+
+
 def test_alone_and_inside_a_batch_same_bits(acq):
     m = ref.generate(7, 37, 33, 130, 100, 8, seed=9)
     acq.set_model(m)

@@ -49,8 +49,9 @@ def _case(n, d, kind, seed=None):
     return X, y, None, np.concatenate([np.log(ls), [np.log(1.3), 0.1, np.log(0.02)]]), kind == "obj"
 
 
-def _gate(gp, X, y, fixed, th, learn, floor, label):
-    want = gref.mll_grad(X, y, th, fixed, learn, floor)
+def _gate(gp, X, y, fixed, th, learn, floor, label, want=None):
+    """want: the long-double (mll, grad, scale_mll, scale_grad) where it does not come from the whole matrix here."""
+    want = gref.mll_grad(X, y, th, fixed, learn, floor) if want is None else want
     gp.set_data(X, y, fixed)
     mll, grad, ok = gp.mll_grad(th, learn, floor)
     e_dev = gref.errors(mll, grad, want)
@@ -101,9 +102,21 @@ def test_real_shape_first_300_trials(gp, golden_dir):
         _gate(gp, Xn, targets[:, k], fixed[:, k], th, True, 1e-6, "fixture[:300] class %d n=300" % k)
 
 
-def _factor_errors(V, a, Vl, al):
-    return (float(np.abs(np.asarray(V, dtype=LD) - Vl).max() / (U * float(np.abs(Vl).max()))),
-            float(np.abs(np.asarray(a, dtype=LD) - al).max() / (U * float(np.abs(al).max()))))
+def _factor_gate(V, a, X, y, hyp, Vl, al, label, rows=None, vmax=None):
+    """The gate of the factor: (V, a) of the device against the long-double (Vl, al); rows: Vl holds these rows of L^-1 only, vmax
+    is then the largest |entry| of the whole of it."""
+    def errors(V, a):
+        V = V if rows is None else V[list(rows)]
+        return (float(np.abs(np.asarray(V, dtype=LD) - Vl).max() / (U * (float(np.abs(Vl).max()) if vmax is None else vmax))),
+                float(np.abs(np.asarray(a, dtype=LD) - al).max() / (U * float(np.abs(al).max()))))
+    e_dev = errors(V, a)
+    e_host = errors(*bo.gp_factor(X, y, hyp))
+    e_torch = errors(*gref.torch_factor(X, y, hyp))
+    for i, name in enumerate(("V", "a")):
+        gate = max(32.0, 4.0 * max(e_host[i], e_torch[i]))
+        print(f"gp_bounds factor {label} {name}: device {e_dev[i]:.2f} host {e_host[i]:.2f} torch {e_torch[i]:.2f} gate {gate:.2f} "
+              f"share {e_dev[i] / gate:.3f} (u x scale)")
+        assert e_dev[i] <= gate, (name, e_dev[i], gate)
 
 
 @pytest.mark.parametrize("n,d,kind", [(5, 7, "obj"), (NB + 1, 7, "cls"), (3 * NB + 8, 7, "obj"), (3 * NB + 8, 2, "cls")])
@@ -114,14 +127,7 @@ def test_factor_against_long_double(gp, n, d, kind):
     Vl, al = gref.factor(X, y, hyp)
     V, a = gp.gp_factor(X, y, hyp)
     assert V.shape == (n, n) and (np.triu(V, 1) == 0.0).all() and (np.diag(V) > 0).all()
-    e_dev = _factor_errors(V, a, Vl, al)
-    e_host = _factor_errors(*bo.gp_factor(X, y, hyp), Vl, al)
-    e_torch = _factor_errors(*gref.torch_factor(X, y, hyp), Vl, al)
-    for i, name in enumerate(("V", "a")):
-        gate = max(32.0, 4.0 * max(e_host[i], e_torch[i]))
-        print(f"gp_bounds factor n={n} d={d} {kind} {name}: device {e_dev[i]:.2f} host {e_host[i]:.2f} torch {e_torch[i]:.2f} gate {gate:.2f} "
-              f"share {e_dev[i] / gate:.3f} (u x scale)")
-        assert e_dev[i] <= gate, (name, e_dev[i], gate)
+    _factor_gate(V, a, X, y, hyp, Vl, al, f"n={n} d={d} {kind}")
     # factor(hyp) on data with a fixed noise adds the scalar of hyp to it: the same matrix, the same bits
     if kind == "cls":
         gp.set_data(X, y, fixed)
@@ -324,3 +330,185 @@ def test_handle_lifetime():
         assert ms.shape == (7,) and (ms >= 0).all() and ms.sum() > 0
     finally:
         a.close(); b.close()
+
+
+# ------------------------------------------------------------------------------------------------ at the sizes a campaign runs at
+# gp_reduce_kernel's threads take a second element from n = 257 and a second tile from nb = 23 (n >= 1409); the logged campaign has
+# n = 2050 (33 block columns), the entry points take n = 4096 (64 block columns, no padded row). The whole-matrix long-double
+# reference is cubic (minutes at these sizes), so the truth is either block-wise (gp_reference.clustered_data: A is block diagonal,
+# exactly) or recorded (tests/golden/gp_campaign.npz).
+def _same(a, b):
+    return a[2] and b[2] and a[0] == b[0] and (a[1] == b[1]).all()
+
+
+def _fresh(X, y, fixed, th, learn, floor=1e-6):
+    g = bo.DeviceGP()
+    try:
+        g.set_data(X, y, fixed)
+        return g.mll_grad(th, learn, floor)
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("case", [(257, 7, "obj"), (257, 1, "cls"), (449, 16, "cls"), (449, 2, "fix")], ids=lambda c: "n%d_d%d_%s" % c)
+def test_second_trip_of_the_n_loop_against_long_double(gp, case):
+    """257: the first n at which a thread of gp_reduce_kernel sums two elements; 449 = 7 x 64 + 1."""
+    n, d, kind = case
+    X, y, fixed, th, learn = _case(n, d, kind)
+    _gate(gp, X, y, fixed, th, learn, 1e-6, "n=%d d=%d %s" % case)
+
+
+_CLUSTERED = {}
+
+
+def _clustered(n, d, kind):
+    """(sizes, X, y, fixed, theta, learn) of clustered data; "cls": the class-1 targets of a 10 % feasible flag vector, their fixed
+    noise plus a per-point one. Length scales 0.4 .. 1.2 as in _case."""
+    if (n, d, kind) not in _CLUSTERED:
+        sizes = gref.cluster_sizes(n)
+        X, y, noise = gref.clustered_data(sizes, d, seed=n + d, noise=kind == "cls")
+        ls = 0.4 + 0.8 * np.random.default_rng(1000 + n + d).random(d)
+        if kind == "cls":
+            flags = np.zeros(n, dtype=bool); flags[::10] = True
+            t, f = bo.dirichlet_targets(flags)
+            y, fixed, tail = t[:, 1], f[:, 1] + noise, [np.log(12.0), -3.0, np.log(0.1)]
+        else:
+            fixed, tail = None, [np.log(1.3), 0.1, np.log(0.02)]
+        _CLUSTERED[n, d, kind] = (sizes, X, y, fixed, np.concatenate([np.log(ls), tail]), True)
+    return _CLUSTERED[n, d, kind]
+
+
+@pytest.mark.parametrize("case", [(1409, 7, "obj"), (4033, 2, "cls"), (4096, 7, "obj")], ids=lambda c: "n%d_d%d_%s" % c)
+def test_clustered_data_against_block_wise_long_double(gp, case):
+    """1409: 23 block columns, 276 tiles, the first size with a second trip of gp_reduce_kernel's tile loop. 4033 = 63 x 64 + 1: one
+    live row in the last block row, a per-point fixed noise. 4096: the limit, no padded row, 2080 tiles (the slowest case of the
+    module: the two FP64 statements of the gate take about 10 s of it)."""
+    n, d, kind = case
+    sizes, X, y, fixed, th, learn = _clustered(n, d, kind)
+    want = gref.block_mll_grad(sizes, X, y, th, fixed, learn, 1e-6)
+    _gate(gp, X, y, fixed, th, learn, 1e-6, "clustered n=%d d=%d %s" % case, want=want)
+
+
+@pytest.mark.parametrize("n", [1409, 4096])
+def test_factor_at_size_against_block_wise_long_double(gp, n):
+    sizes, X, y, _, _, _ = _clustered(n, 7, "obj")
+    hyp = ref.hypers(7)[0][0]
+    Vl, al = gref.block_factor(sizes, X, y, hyp)
+    V, a = gp.gp_factor(X, y, hyp)
+    assert V.shape == (n, n) and (np.triu(V, 1) == 0.0).all() and (np.diag(V) > 0).all()
+    assert (V[Vl == 0] == 0.0).all()          # (a tile index off by one brings live numbers between the clusters)
+    _factor_gate(V, a, X, y, hyp, Vl, al, f"clustered n={n} d=7 obj")
+
+
+@pytest.fixture(scope="module")
+def campaign(golden_dir):
+    """The logged campaign's class GPs on all 2050 trials and their recorded long-double truth (tests/golden/make_gp_golden.py)."""
+    t = np.load(os.path.join(golden_dir, "bo_trials_F.npz"))
+    targets, fixed = bo.dirichlet_targets(t["feasible"])
+    return t["params_nor"], targets, fixed, np.load(os.path.join(golden_dir, "gp_campaign.npz"))
+
+
+def _entry(z, k, e):
+    tag = f"{k}_{e}"
+    j = lambda name: gref.join(z[f"{name}_{tag}_hi"], z[f"{name}_{tag}_lo"])          # noqa: E731
+    return z["theta_" + tag], (j("mll"), j("grad"), float(z["scale_" + tag][0]), float(z["scale_" + tag][1])), j("V"), j("a"), float(z["vmax_" + tag])
+
+
+@pytest.mark.parametrize("k,e", [(0, 0), (0, 1), (1, 0), (1, 1)], ids=lambda v: str(v))
+def test_campaign_class_gps_against_recorded_long_double(gp, campaign, k, e):
+    """Class k at theta e (0: where the fit starts, 1: where the CPU fit ends) on all 2050 trials: 33 block columns, 561 tiles. The
+    likelihood and its gradient, then the factor at the same theta: a and the recorded rows of V."""
+    Xn, targets, fixed, z = campaign
+    th, want, Vl, al, vmax = _entry(z, k, e)
+    floor = float(z["noise_floor"])
+    _gate(gp, Xn, targets[:, k], fixed[:, k], th, True, floor, f"campaign n=2050 class {k} theta {e}", want=want)
+    hyp = bo.GPHyper(c=float(th[8]), s=float(np.exp(th[7])), ls=np.exp(th[:7]), noise=floor + float(np.exp(th[9])))
+    V, a = gp.factor(hyp)          # (raises where ok is 0)
+    assert (np.triu(V, 1) == 0.0).all() and (np.diag(V) > 0).all()
+    _factor_gate(V, a, Xn, targets[:, k], bo.GPHyper(c=hyp.c, s=hyp.s, ls=hyp.ls, noise=fixed[:, k] + hyp.noise), Vl, al,
+                 f"campaign n=2050 class {k} theta {e}", rows=z["rows"], vmax=vmax)
+
+
+def test_a_pivot_that_fails_in_a_later_block_column_is_a_result(gp):
+    """A repeated trial at row 300 (block column 4) without any noise: the bad pivot appears after gp_trsm_kernel and gp_syrk_kernel
+    have run over four columns. The kernels' contract is finite numbers and ok = 0."""
+    n, d = 321, 3
+    X, y = gref.fit_data(n, d)
+    X[300] = X[70]
+    th = np.concatenate([np.log(np.full(d, 0.5)), [np.log(max(float(np.var(y, ddof=1)), 1e-3)), float(y.mean()), np.log(1e-2)]])
+    gp.set_data(X, y)
+    mll, grad, ok = gp.mll_grad(th, False, 0.0)
+    assert not ok and np.isfinite(mll) and np.isfinite(grad).all()
+    mll2, _, ok2 = gp.mll_grad(th, False, 0.0, grad=False)
+    assert not ok2 and np.isfinite(mll2)
+    with pytest.raises(bo.ModelFittingError):
+        gp.factor(bo.GPHyper(c=th[4], s=np.exp(th[3]), ls=np.exp(th[:3]), noise=0.0))
+    assert not bo.gp_mll_grad_host(X, y, th, None, False, 0.0)[2]
+    Xs, ys, fs, ths, ls_ = _case(449, 2, "fix")          # sound data on the same handle: the bits of a fresh handle
+    gp.set_data(Xs, ys, fs)
+    assert _same(gp.mll_grad(ths, ls_, 1e-6), _fresh(Xs, ys, fs, ths, ls_))
+
+
+def test_same_bits_and_nothing_stale_at_size(gp, campaign):
+    Xn, targets, fixed, z = campaign
+    th = z["theta_1_1"]
+    gp.set_data(Xn, targets[:, 1], fixed[:, 1])
+    first = gp.mll_grad(th, True, 1e-6)
+    assert _same(first, gp.mll_grad(th, True, 1e-6))
+    _, Xm, ym, fm, thm, lm = _clustered(1409, 7, "obj")
+    gp.set_data(Xm, ym, fm)
+    assert gp.mll_grad(thm, lm, 1e-6, grad=False)[0] == gp.mll_grad(thm, lm, 1e-6)[0]          # the value alone: the same bits
+    _, Xl, yl, fl, thl, ll = _clustered(4096, 7, "obj")
+    Xs, ys, fs, ths, ls_ = _case(257, 7, "obj")
+    X5, y5, f5, th5, l5 = _case(5, 7, "obj")
+    h5 = bo.GPHyper(c=0.1, s=1.3, ls=np.exp(th5[:7]), noise=0.05)
+    big_fresh, small_fresh, five_fresh = _fresh(Xl, yl, fl, thl, ll), _fresh(Xs, ys, fs, ths, ls_), _fresh(X5, y5, f5, th5, l5)
+    g = bo.DeviceGP()
+    try:
+        g.set_data(X5, y5, f5)
+        v5 = g.factor(h5)
+    finally:
+        g.close()
+    # after n = 4096 on a handle, n = 257 gives what a fresh handle gives
+    gp.set_data(Xl, yl, fl)
+    assert _same(gp.mll_grad(thl, ll, 1e-6), big_fresh)
+    gp.set_data(Xs, ys, fs)
+    assert _same(gp.mll_grad(ths, ls_, 1e-6), small_fresh)
+    # 5, 4096, 5, 2050 on one handle: its buffers grow from one tile to 2080 and never shrink
+    g = bo.DeviceGP()
+    try:
+        for step in ("five", "big", "five", "campaign"):
+            if step == "five":
+                g.set_data(X5, y5, f5)
+                v = g.factor(h5)
+                assert _same(g.mll_grad(th5, l5, 1e-6), five_fresh) and (v[0] == v5[0]).all() and (v[1] == v5[1]).all()
+            elif step == "big":
+                g.set_data(Xl, yl, fl)
+                assert _same(g.mll_grad(thl, ll, 1e-6), big_fresh)
+            else:
+                g.set_data(Xn, targets[:, 1], fixed[:, 1])
+                assert _same(g.mll_grad(th, True, 1e-6), first)
+    finally:
+        g.close()
+
+
+def test_fit_on_the_device_at_the_campaign_objective_shape(gp, golden_dir):
+    """bo.fit_gp(backend="device") on the campaign's 194 feasible trials (d = 7), both objectives, by the criteria of
+    test_fit_on_the_device."""
+    z = np.load(os.path.join(golden_dir, "bo_trials_F.npz"))
+    feas = z["feasible"]
+    Xt = z["params_nor"][feas]
+    Ys = bo.standardize(z["objectives"][feas][:, 0, :])[0]
+    assert Xt.shape == (194, 7)
+    for o in range(2):
+        y = Ys[:, o]
+        h1, start, end = bo.fit_gp(Xt, y, return_trace=True, backend="device", gp=gp)
+        h2 = bo.fit_gp(Xt, y, backend="device", gp=gp)
+        _, _, end_cpu = bo.fit_gp(Xt, y, return_trace=True)
+        _, _, end_gpu = bo.fit_gp(Xt, y, return_trace=True, device="cuda")
+        g = max(4.0 * abs(end_gpu - end_cpu), 1e-9 * abs(end_cpu))
+        print(f"gp_bounds fit campaign objective {o} n=194 d=7: start {start!r} end device {end!r} torch cpu {end_cpu!r} torch gpu {end_gpu!r} g {g:.3e}")
+        assert end >= start
+        assert h1.c == h2.c and h1.s == h2.s and h1.noise == h2.noise and (h1.ls == h2.ls).all()
+        assert abs(bo.gp_mll(Xt, y, bo.GPHyper(h1.c, h1.s, h1.ls, h1.noise - 1e-6), noise_floor=1e-6) - end) <= 1e-9 * abs(end)
+        assert end >= end_cpu - g
