@@ -628,6 +628,81 @@ int tum_bo_evaluate(tum_bo *b, const double *X, int C, double *alpha_out, double
  * milliseconds of the last evaluation -- kernel values, V products, moments, H product, R product, samples and HVI, final. */
 int tum_bo_profile(tum_bo *b, int on, double *ms_out);
 
+/* --- K17: parts of the acquisition model built on the device (bo.prune_baseline, the baseline part of bo.pack_model, bo.append_pick,
+ * bo.build_fronts). All work on a tum_bo handle. tum_bom_prune and tum_bom_fronts need no model and leave the handle's model alone;
+ * tum_bom_build installs a model (it replaces the one there), tum_bom_append extends it, tum_bom_model_read downloads it.
+ * tum_bom_prune: which of the n feasible trials are non-dominated in at least one of S joint posterior samples at the trials
+ * themselves. Per objective o, from the fitted GP (Xt, ils_o, s_o, c_o, V_o = L_A^-1 lower, a_o) and base samples Z_o (S x n):
+ *   K = k_o(Xt, Xt); H = K V_o^T; Sig = K - H H^T (symmetrised) + max(jitter, 1e-6 s_o) I = L_p L_p^T; m = c_o + K a_o
+ *   F[s][i][o] = m_i + sum_k Z_o[s][k] L_p[i][k]
+ * then keep_out[i] = 1 where in some sample s no j has F[s][j] >= F[s][i] in both objectives and > in one (equal rows keep each
+ * other), 0 otherwise. With desc->F (S x n x 2) set, the GP inputs are not read and only this step runs on the given draws.
+ * ok_out: 1 where both factorisations met positive finite pivots only (always 1 with given draws); otherwise 0, and keep_out and
+ * F_out hold the result of the chain with each failed pivot replaced by 1 -- a result, not an error. The Cholesky is gp_kernels'
+ * blocked chain; products run on the matrix cores and skip the zero tiles of V and L_p. No floating-point atomics: the order of
+ * every sum depends on n, d and S alone. struct_size: sizeof(tum_bom_prune_desc) as the caller compiled it (tum_bom_prune_desc_init
+ * sets it and zeroes the rest). Limits: n 1..4096, S 1..4096, d 1..16. Refused: a null argument, a struct_size that is not this
+ * library's, sizes out of range, a NaN or an infinity in any input, a V with a nonzero above its diagonal (the products stop at the
+ * diagonal tile; tum_bom_build refuses the same of the two objective V). */
+typedef struct tum_bom_prune_desc {
+    int struct_size;
+    int n, d, S;
+    double jitter;
+    const double *F;                    /* NULL, or S x n x 2 given draws */
+    const double *Xt;                   /* n x d */
+    double s[2], c[2];
+    const double *ils[2];               /* d */
+    const double *V[2], *a[2];          /* n x n, zero above the diagonal (as tum_gp_factor returns it); n */
+    const double *Z[2];                 /* S x n */
+} tum_bom_prune_desc;
+void tum_bom_prune_desc_init(tum_bom_prune_desc *desc);
+/* keep_out: n ints; F_out: NULL or S x n x 2, the draws the mask was formed from. */
+int tum_bom_prune(tum_bo *b, const tum_bom_prune_desc *desc, int *keep_out, double *F_out, int *ok_out);
+/* The fronts of given baseline draws F_b (S x n_b x 2): per sample the points strictly above ref in both objectives, sorted by
+ * objective 0 descending, then objective 1 descending, kept where objective 1 exceeds the running maximum, stored ascending in
+ * objective 0 into fronts_out (S x n_b x 2, zero rows behind the count) with count_out (S) -- what tum_bo_model takes as fronts
+ * (P_max = n_b) and front_count. Limits: S 1..4096, n_b 1..512. Refused: a null argument, sizes out of range, a NaN or an infinity. */
+int tum_bom_fronts(tum_bo *b, const double *F_b, int S, int n_b, const double *ref, double *fronts_out, int *count_out);
+/* tum_bom_build: tum_bo_model with the baseline part built on the device. The four GPs are installed as tum_bo_model installs them;
+ * then per objective o, with Z_o = Zfull_o[:, 0 .. n_b) and zeta_o = Zfull_o[:, n_b] (Zfull_o: S x ncol, ncol >= n_b + 1):
+ *   H_o = K_o(Xb,Xt) V_o^T; L_b = chol(sym(K_o(Xb,Xb) - H_o H_o^T) + jitter_o I); R_o = L_b^-1; mu_b = c_o + K_o(Xb,Xt) a_o
+ *   F_b[s][i][o] = mu_b,i + sum_k Z_o[s][k] L_b[i][k]
+ * and per sample the front of F_b[s] above ref as tum_bom_fronts states it (P_max = n_b). It takes no H, R, fronts or counts. ok_out: 1
+ * where both factorisations met positive finite pivots only; otherwise 0 and the handle holds NO model. Limits and refusals as
+ * tum_bo_model's, and a struct_size that is not this library's. tum_bom_model_read downloads what the build left on the device: per
+ * objective H (n_b x n_t), R and L_b (n_b x n_b, zero above the diagonal), mu_b (n_b); F_b and fronts (S x n_b x 2), counts (S),
+ * n_b. Any pointer (or entry of a pointer pair) may be NULL. Refused where the resident model was not built by tum_bom_build. */
+typedef struct tum_bom_build_desc {
+    int struct_size;
+    int d, n_t, n_b, n_c, S, ncol, K;
+    double eps, ref[2], jitter[2];
+    double s[4], c[4];                  /* objective 0, 1, class 0, 1 */
+    const double *Xt, *Xb, *Xc;         /* n_t x d, n_b x d, n_c x d */
+    const double *ils[4];               /* d inverse length scales each */
+    const double *a[4];                 /* n_t, n_t, n_c, n_c */
+    const double *V[4];                 /* n x n, zero above the diagonal */
+    const double *Zfull[2];             /* S x ncol */
+    const double *gh_x, *gh_w;          /* K */
+} tum_bom_build_desc;
+void tum_bom_build_desc_init(tum_bom_build_desc *desc);
+int tum_bom_build(tum_bo *b, const tum_bom_build_desc *desc, int *ok_out);
+int tum_bom_model_read(tum_bo *b, double *const *H_out, double *const *R_out, double *const *L_out, double *const *mu_out,
+                       double *F_b_out, double *fronts_out, int *count_out, int *n_b_out);
+/* tum_bom_append: the point x (d doubles) joins the baseline of the model tum_bom_build left, without refactoring, as bo.append_pick
+ * states it: with mu, q, l, d2 of x from the evaluation chain and lam = sqrt(d2), q is the new row of H_o, (l, lam) of L_b,
+ * (-(l R_o) / lam, 1 / lam) of R_o, the new baseline draw is mu + Z_o l + lam zeta_o, the next column of Zfull_o becomes zeta_o and the
+ * fronts are rebuilt -- all on the device; nothing is uploaded but x. tum_bom_build keeps room for one append per column of Zfull behind
+ * zeta's, up to n_b = 512. ok_out: 0 where a lam is not positive and finite (jitter 0 on a baseline point). Refused: a null argument, a
+ * model not built by tum_bom_build, no free column of Zfull (n_b + 2 > ncol), n_b = 512 already, a NaN or an infinity in x. */
+int tum_bom_append(tum_bo *b, const double *x, int *ok_out);
+/* Measurement aid: on != 0 times the kernels of the following tum_bom_build calls with events; ms_out (NULL or 9 doubles): the
+ * milliseconds of the last call, both objectives together -- kernel matrices, H, covariance, Cholesky, R = L_b^-1, mean, draws, packing
+ * of H and R, fronts. */
+int tum_bom_build_profile(tum_bo *b, int on, double *ms_out);
+/* Measurement aid: on != 0 times the kernels of the following tum_bom_prune calls with events; ms_out (NULL or 7 doubles): the
+ * milliseconds of the last call, both objectives together -- kernel matrix, H, covariance, Cholesky, mean, draws, dominance. */
+int tum_bom_prune_profile(tum_bo *b, int on, double *ms_out);
+
 /* --- K16: fitting the surrogates of the Bayesian-optimisation step: the exact marginal log-likelihood of one GP and its gradient.
  * Data X (n x d), y (n) and a fixed noise per point (NULL: none); hyperparameters theta = [log ls (d), log s, c, log noise]:
  *   A = s exp(-1/2 sum_j ((x_ij - x_kj) / ls_j)^2) + diag(fixed + noise_floor + [learn_noise] e^theta_noise) = L L^T

@@ -11,7 +11,8 @@ of the same mathematics (INTEGRATION.md lists the differences).
   host_acquisition, HostAcquisition             numpy statement of the acquisition value (the CPU path)
   DeviceAcquisition                             the device path
   select                                        sequential greedy picks: Sobol raw samples, restarts, batched compass search
-  pareto_mask, hypervolume_2d, prune_baseline   front utilities
+  pareto_mask, hypervolume_2d, prune_baseline   front utilities; prune_draws / dominance_keep are prune_baseline's two halves, which
+                                                DeviceAcquisition.prune runs on the device (csrc/bo_model_kernels.hpp)
   load_trials, store_trials                     the reference's CSV line format
   BayesianOptimization                          the driver
 """
@@ -190,6 +191,7 @@ class PackedModel:
     F_b: np.ndarray = None          # S x n_b x 2
     fronts: np.ndarray = None
     front_count: np.ndarray = None
+    device_baseline: bool = False          # H, R, L_b, mu_b, F_b and the fronts are not here: DeviceAcquisition.set_model builds them
 
     @property
     def n_b(self):
@@ -206,11 +208,15 @@ class PackedModel:
         return np.ascontiguousarray(self.Zfull[:, self.n_b, o])
 
 
-def pack_model(Xt, Y, obj_hyp, Xc, feasible, cls_hyp, Xb, Z, ref, eps=0.8, jitter=1e-8, K=64, alpha_eps=0.001, factor=None):
+def pack_model(Xt, Y, obj_hyp, Xc, feasible, cls_hyp, Xb, Z, ref, eps=0.8, jitter=1e-8, K=64, alpha_eps=0.001, factor=None, baseline="host"):
     """Xt (n_t x d) feasible trials with Y (n_t x 2, the units the GPs model); obj_hyp two GPHyper; Xc (n_c x d) all trials with their
     feasibility flags; cls_hyp two GPHyper whose noise is the LEARNED extra noise (the fixed Dirichlet noise is added here); Xb the
     baseline; Z (S x ncol x 2, ncol >= n_b + 1) base samples; ref the reference point in the units of Y. factor: what forms the four
-    (V, a), gp_factor by default or a callable of its signature such as DeviceGP.gp_factor."""
+    (V, a), gp_factor by default or a callable of its signature such as DeviceGP.gp_factor. baseline "device": the model carries the
+    inputs and the flag device_baseline, and no H, R, L_b, mu_b, F_b or fronts: DeviceAcquisition.set_model builds those on the device
+    (tum_bom_build) and model_arrays() reads them back; complete_model joins the two."""
+    if baseline not in ("host", "device"):
+        raise ValueError(f"pack_model: baseline {baseline!r} is neither 'host' nor 'device'")
     Xt, Xb, Xc = (np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64))) for a in (Xt, Xb, Xc))
     Y = np.asarray(Y, dtype=np.float64).reshape(len(Xt), 2)
     d = Xt.shape[1]
@@ -228,6 +234,9 @@ def pack_model(Xt, Y, obj_hyp, Xc, feasible, cls_hyp, Xb, Z, ref, eps=0.8, jitte
     m = PackedModel(d=d, Xt=Xt, Xb=Xb, Xc=Xc, ils=[np.ascontiguousarray(h.ils) for h in hyps], s=np.array([h.s for h in hyps], dtype=np.float64),
                     c=np.array([h.c for h in hyps], dtype=np.float64), a=a, V=V, jitter=jit, H=[], R=[], Zfull=np.ascontiguousarray(Z, dtype=np.float64),
                     ref=np.asarray(ref, dtype=np.float64).copy(), eps=float(eps), gh_x=gh_x, gh_w=gh_w)
+    if baseline == "device":
+        m.device_baseline = True
+        return m
     nb = len(Xb)
     m.F_b = np.zeros((m.S, nb, 2))
     for o in range(2):
@@ -240,6 +249,12 @@ def pack_model(Xt, Y, obj_hyp, Xc, feasible, cls_hyp, Xb, Z, ref, eps=0.8, jitte
         m.F_b[:, :, o] = m.mu_b[o] + m.Z(o) @ L.T
     m.fronts, m.front_count = build_fronts(m.F_b, m.ref)
     return m
+
+
+def complete_model(m, arrays):
+    """A model packed with baseline="device" and the arrays DeviceAcquisition.model_arrays() read back: the model pack_model's host
+    path returns, with the device's numbers."""
+    return replace(m, device_baseline=False, **arrays)
 
 
 def _candidate_terms(m, X):
@@ -328,26 +343,53 @@ def append_pick(m, x):
     return new
 
 
-def prune_baseline(Xt, Y, obj_hyp, S=1024, seed=0, jitter=1e-8):
-    """Indices of the feasible trials that are non-dominated in at least one of S joint posterior samples at the trials themselves."""
-    Xt = np.atleast_2d(np.asarray(Xt, dtype=np.float64))
-    n = len(Xt)
-    Zs = sobol_normal(S, 2 * n, seed).reshape(S, 2, n)
-    F = np.zeros((S, n, 2))
-    for o in range(2):
-        V, a = gp_factor(Xt, Y[:, o], obj_hyp[o])
-        K = rbf(Xt, Xt, obj_hyp[o].ils, obj_hyp[o].s)
-        Hm = K @ V.T
-        Sig = K - Hm @ Hm.T
-        L = _chol(0.5 * (Sig + Sig.T) + max(jitter, 1e-6 * obj_hyp[o].s) * np.eye(n), "posterior covariance at the trials")
-        F[:, :, o] = obj_hyp[o].c + K @ a + Zs[:, o] @ L.T
-    # i is dominated in sample s if some j is >= in both and > in one
-    keep = np.zeros(n, dtype=bool)
-    for s in range(S):
+def dominance_keep(F):
+    """F: S x n x 2 draws -> the boolean mask of the rows that are non-dominated in at least one sample: i is dominated in sample s
+    if some j is >= in both objectives and > in one. Equal rows keep each other."""
+    keep = np.zeros(F.shape[1], dtype=bool)
+    for s in range(F.shape[0]):
         ge = (F[s, None, :, :] >= F[s, :, None, :]).all(-1)
         gt = (F[s, None, :, :] > F[s, :, None, :]).any(-1)
         keep |= ~(ge & gt).any(1)
-    return np.flatnonzero(keep)
+    return keep
+
+
+def prune_draws(Xt, V, a, obj_hyp, Zs, jitter=1e-8):
+    """The joint posterior draws prune_baseline judges: F (S x n x 2) from the factors (V, a) of the two objective GPs and the base
+    samples Zs (S x 2 x n) -- the numpy statement of tum_bom_prune's chain."""
+    n, S = len(Xt), len(Zs)
+    F = np.zeros((S, n, 2))
+    for o in range(2):
+        K = rbf(Xt, Xt, obj_hyp[o].ils, obj_hyp[o].s)
+        Hm = K @ V[o].T
+        Sig = K - Hm @ Hm.T
+        L = _chol(0.5 * (Sig + Sig.T) + max(jitter, 1e-6 * obj_hyp[o].s) * np.eye(n), "posterior covariance at the trials")
+        F[:, :, o] = obj_hyp[o].c + K @ a[o] + Zs[:, o] @ L.T
+    return F
+
+
+def prune_baseline(Xt, Y, obj_hyp, S=1024, seed=0, jitter=1e-8, backend="host", acq=None, factor=None):
+    """Indices of the feasible trials that are non-dominated in at least one of S joint posterior samples at the trials themselves.
+    backend "device": the draws and the dominance step run on the device (DeviceAcquisition.prune; acq: the handle to use, created
+    and closed here otherwise); the base samples and the two factors (factor: gp_factor or a callable of its signature) stay on the
+    host. The host path is the default and returns what it returned."""
+    if backend not in ("host", "device"):
+        raise ValueError(f"prune_baseline: backend {backend!r} is neither 'host' nor 'device'")
+    Xt = np.atleast_2d(np.asarray(Xt, dtype=np.float64))
+    n = len(Xt)
+    Zs = sobol_normal(S, 2 * n, seed).reshape(S, 2, n)
+    factor = gp_factor if factor is None else factor
+    V, a = zip(*(factor(Xt, Y[:, o], obj_hyp[o]) for o in range(2)))
+    if backend == "host":
+        return np.flatnonzero(dominance_keep(prune_draws(Xt, V, a, obj_hyp, Zs, jitter)))
+    own = acq is None
+    if own:
+        acq = DeviceAcquisition()
+    try:
+        return np.flatnonzero(acq.prune(Xt, V, a, obj_hyp, Zs, jitter)[0])
+    finally:
+        if own:
+            acq.close()
 
 
 # ------------------------------------------------------------------------------------------------ evaluators
@@ -374,8 +416,26 @@ class _ModelDesc(ctypes.Structure):
                 ("fronts", _dp), ("front_count", _ip), ("gh_x", _dp), ("gh_w", _dp)]
 
 
+class _BuildDesc(ctypes.Structure):
+    _dp = ctypes.POINTER(ctypes.c_double)
+    _fields_ = [(n, ctypes.c_int) for n in ("struct_size", "d", "n_t", "n_b", "n_c", "S", "ncol", "K")] + \
+               [("eps", ctypes.c_double), ("ref", ctypes.c_double * 2), ("jitter", ctypes.c_double * 2),
+                ("s", ctypes.c_double * 4), ("c", ctypes.c_double * 4),
+                ("Xt", _dp), ("Xb", _dp), ("Xc", _dp), ("ils", _dp * 4), ("a", _dp * 4), ("V", _dp * 4),
+                ("Zfull", _dp * 2), ("gh_x", _dp), ("gh_w", _dp)]
+
+
+class _PruneDesc(ctypes.Structure):
+    _dp = ctypes.POINTER(ctypes.c_double)
+    _fields_ = [(n, ctypes.c_int) for n in ("struct_size", "n", "d", "S")] + \
+               [("jitter", ctypes.c_double), ("F", _dp), ("Xt", _dp), ("s", ctypes.c_double * 2), ("c", ctypes.c_double * 2),
+                ("ils", _dp * 2), ("V", _dp * 2), ("a", _dp * 2), ("Z", _dp * 2)]
+
+
 class DeviceAcquisition:
-    """The acquisition value on the device: tum_bo_create / tum_bo_model / tum_bo_evaluate. There is no CPU fallback behind it."""
+    """The acquisition value on the device: tum_bo_create / tum_bo_model / tum_bo_evaluate, and the parts of its model the device
+    builds: tum_bom_prune (prune, prune_given), tum_bom_fronts (fronts), tum_bom_build (set_model of a model packed with
+    baseline="device"), tum_bom_append (append_pick) and tum_bom_model_read (model_arrays). There is no CPU fallback behind it."""
 
     def __init__(self, device=0):
         from . import solver
@@ -384,6 +444,7 @@ class DeviceAcquisition:
         if not self._h:
             raise Exception("tum_bo_create: " + self._L.tum_ocp_last_error().decode())
         self.d = None
+        self._built = None          # (S, n_b, n_t) of the resident model where tum_bom_build built it
 
     def _check(self, rc, what):
         if rc != 0:
@@ -397,6 +458,10 @@ class DeviceAcquisition:
             a = np.ascontiguousarray(a, dtype=np.float64)
             hold.append(a)
             return a.ctypes.data_as(dp)
+        if m.device_baseline:
+            if keep_gp:
+                raise Exception("tum_bom_build: a model whose baseline the device builds installs its GPs too (keep_gp is not for it)")
+            return self._build(m, ptr)
         desc = _ModelDesc()
         desc.d, desc.n_t, desc.n_b, desc.n_c, desc.S = m.d, len(m.Xt), m.n_b, len(m.Xc), m.S
         desc.P_max, desc.K, desc.keep_gp, desc.eps = m.fronts.shape[1], len(m.gh_x), int(bool(keep_gp)), m.eps
@@ -412,8 +477,61 @@ class DeviceAcquisition:
         desc.fronts, desc.gh_x, desc.gh_w = ptr(m.fronts), ptr(m.gh_x), ptr(m.gh_w)
         cnt = np.ascontiguousarray(m.front_count, dtype=np.int32)
         desc.front_count = cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        self._built = None
         self._check(self._L.tum_bo_model(self._h, ctypes.addressof(desc)), "tum_bo_model")
         self.d = m.d
+
+    def _build(self, m, ptr):
+        desc = _BuildDesc()
+        self._L.tum_bom_build_desc_init(ctypes.addressof(desc))
+        if desc.struct_size != ctypes.sizeof(_BuildDesc):
+            raise Exception("tum_bom_build_desc: the library's descriptor is not the one bo.py declares")
+        desc.d, desc.n_t, desc.n_b, desc.n_c, desc.S = m.d, len(m.Xt), m.n_b, len(m.Xc), m.S
+        desc.ncol, desc.K, desc.eps = m.Zfull.shape[1], len(m.gh_x), m.eps
+        desc.Xt, desc.Xb, desc.Xc, desc.gh_x, desc.gh_w = ptr(m.Xt), ptr(m.Xb), ptr(m.Xc), ptr(m.gh_x), ptr(m.gh_w)
+        for o in range(2):
+            desc.ref[o], desc.jitter[o], desc.Zfull[o] = m.ref[o], m.jitter[o], ptr(m.Zfull[:, :, o])
+        for g in range(4):
+            desc.s[g], desc.c[g] = m.s[g], m.c[g]
+            desc.ils[g], desc.a[g], desc.V[g] = ptr(m.ils[g]), ptr(m.a[g]), ptr(m.V[g])
+        ok = ctypes.c_int()
+        self.d = self._built = None
+        self._check(self._L.tum_bom_build(self._h, ctypes.addressof(desc), ctypes.byref(ok)), "tum_bom_build")
+        if not ok.value:
+            raise ModelFittingError("baseline posterior covariance: not positive definite on the device")
+        self.d = m.d
+        self._built = (m.S, m.n_b, len(m.Xt))
+
+    def append_pick(self, x):
+        """bo.append_pick on the device (tum_bom_append): x joins the baseline of the model set_model built there; nothing but x is
+        uploaded. model_arrays() reads the appended model."""
+        if self.d is None or self._built is None:
+            raise Exception("tum_bom_append: no model built on the device (tum_bom_build first)")
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+        if len(x) != self.d:
+            raise Exception(f"tum_bom_append: x has {len(x)} entries, the model has d = {self.d}")
+        ok = ctypes.c_int()
+        self._check(self._L.tum_bom_append(self._h, x.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(ok)), "tum_bom_append")
+        S, nb, nt = self._built
+        self._built = (S, nb + 1, nt)
+        if not ok.value:
+            raise ModelFittingError("append_pick: the appended point has no positive posterior variance on the device")
+
+    def model_arrays(self):
+        """What tum_bom_build left on the device, as the fields of PackedModel: H, R, L_b, mu_b (one per objective), F_b, fronts,
+        front_count."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        if self.d is None or self._built is None:
+            raise Exception("tum_bom_model_read: no model built on the device (tum_bom_build first)")
+        S, nb, nt = self._built
+        H, R, L, mu = ([np.zeros(sh) for _ in range(2)] for sh in ((nb, nt), (nb, nb), (nb, nb), (nb,)))
+        F_b, fronts, count, n_b = np.zeros((S, nb, 2)), np.zeros((S, nb, 2)), np.zeros(S, dtype=np.int32), ctypes.c_int()
+        pair = lambda arrs: (dp * 2)(*(x.ctypes.data_as(dp) for x in arrs))          # noqa: E731
+        pairs = [pair(x) for x in (H, R, L, mu)]
+        self._check(self._L.tum_bom_model_read(self._h, *(ctypes.addressof(x) for x in pairs), F_b.ctypes.data_as(dp), fronts.ctypes.data_as(dp),
+                                               count.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(n_b)), "tum_bom_model_read")
+        assert n_b.value == nb
+        return dict(H=H, R=R, L_b=L, mu_b=mu, F_b=F_b, fronts=fronts, front_count=count)
 
     def evaluate(self, X, detail=False):
         X = np.ascontiguousarray(np.atleast_2d(np.asarray(X, dtype=np.float64)))
@@ -425,6 +543,85 @@ class DeviceAcquisition:
         self._check(self._L.tum_bo_evaluate(self._h, X.ctypes.data_as(dp), len(X), alpha.ctypes.data_as(dp),
                                             det.ctypes.data_as(dp) if detail else None), "tum_bo_evaluate")
         return (alpha, det) if detail else alpha
+
+    def _prune(self, desc, n, S, want_draws, hold):
+        desc.n, desc.S = n, S
+        keep, ok = np.zeros(n, dtype=np.int32), ctypes.c_int()
+        F = np.zeros((S, n, 2)) if want_draws else None
+        self._check(self._L.tum_bom_prune(self._h, ctypes.addressof(desc), keep.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                          F.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if want_draws else None, ctypes.byref(ok)),
+                    "tum_bom_prune")
+        if not ok.value:
+            raise ModelFittingError("posterior covariance at the trials: not positive definite on the device")
+        return keep.astype(bool), F
+
+    def _prune_desc(self):
+        desc = _PruneDesc()
+        self._L.tum_bom_prune_desc_init(ctypes.addressof(desc))
+        if desc.struct_size != ctypes.sizeof(_PruneDesc):
+            raise Exception("tum_bom_prune_desc: the library's descriptor is not the one bo.py declares")
+        return desc
+
+    def prune(self, Xt, V, a, obj_hyp, Zs, jitter=1e-8, draws=False):
+        """prune_draws and dominance_keep on the device: (keep mask (n), F (S x n x 2) or None). Zs: S x 2 x n base samples. V: the two
+        L^-1 as gp_factor returns them, zero above the diagonal -- the device's products stop at the diagonal tile, so anything else is
+        refused, not multiplied."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        hold = []
+
+        def ptr(x):
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            hold.append(x)
+            return x.ctypes.data_as(dp)
+        Xt = np.ascontiguousarray(np.atleast_2d(np.asarray(Xt, dtype=np.float64)))
+        n, d = Xt.shape
+        Zs = np.asarray(Zs, dtype=np.float64)
+        if Zs.ndim != 3 or Zs.shape[1:] != (2, n):
+            raise Exception(f"tum_bom_prune: the base samples have the shape {Zs.shape}, not S x 2 x {n}")
+        desc = self._prune_desc()
+        desc.d, desc.jitter, desc.Xt = d, float(jitter), ptr(Xt)
+        for o in range(2):
+            if np.shape(V[o]) != (n, n) or np.shape(a[o]) != (n,) or len(obj_hyp[o].ls) != d:
+                raise Exception(f"tum_bom_prune: V, a or the length scales of objective {o} do not have the sizes of Xt ({n} x {d})")
+            desc.s[o], desc.c[o] = obj_hyp[o].s, obj_hyp[o].c
+            desc.ils[o], desc.V[o], desc.a[o], desc.Z[o] = ptr(obj_hyp[o].ils), ptr(V[o]), ptr(a[o]), ptr(Zs[:, o])
+        return self._prune(desc, n, len(Zs), draws, hold)
+
+    def prune_given(self, F):
+        """dominance_keep of given draws F (S x n x 2) on the device: the keep mask (n)."""
+        F = np.ascontiguousarray(np.asarray(F, dtype=np.float64))
+        if F.ndim != 3 or F.shape[2] != 2:
+            raise Exception(f"tum_bom_prune: the draws have the shape {F.shape}, not S x n x 2")
+        desc = self._prune_desc()
+        desc.F = F.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        return self._prune(desc, F.shape[1], F.shape[0], False, [F])[0]
+
+    def fronts(self, F_b, ref):
+        """build_fronts (P_max = n_b) of the baseline draws F_b (S x n_b x 2) on the device: fronts (S x n_b x 2) and counts (S)."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        F_b = np.ascontiguousarray(np.asarray(F_b, dtype=np.float64))
+        if F_b.ndim != 3 or F_b.shape[2] != 2:
+            raise Exception(f"tum_bom_fronts: the draws have the shape {F_b.shape}, not S x n_b x 2")
+        ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(2))
+        S, nb = F_b.shape[:2]
+        fronts, count = np.zeros((S, nb, 2)), np.zeros(S, dtype=np.int32)
+        self._check(self._L.tum_bom_fronts(self._h, F_b.ctypes.data_as(dp), S, nb, ref.ctypes.data_as(dp), fronts.ctypes.data_as(dp),
+                                           count.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "tum_bom_fronts")
+        return fronts, count
+
+    def prune_profile(self, on=True):
+        """Time the kernels of the following prune calls; returns the seven times (ms) of the last one, both objectives together:
+        kernel matrix, H, covariance, Cholesky, mean, draws, dominance."""
+        ms = np.zeros(7)
+        self._check(self._L.tum_bom_prune_profile(self._h, int(on), ms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "tum_bom_prune_profile")
+        return ms
+
+    def build_profile(self, on=True):
+        """Time the kernels of the following device builds (set_model of a baseline="device" model); returns the nine times (ms) of the
+        last one, both objectives together: kernel matrices, H, covariance, Cholesky, R = L_b^-1, mean, draws, packing, fronts."""
+        ms = np.zeros(9)
+        self._check(self._L.tum_bom_build_profile(self._h, int(on), ms.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "tum_bom_build_profile")
+        return ms
 
     def profile(self, on=True):
         """Time the launches of the following evaluations; returns the seven times (ms) of the last one."""
@@ -469,17 +666,28 @@ def compass_search(evaluate, X0, h0=0.1, h_min=1e-3, max_iter=400):
     return X, val, launches
 
 
-def select(model, q=1, n_raw=512, n_restarts=20, max_iter=400, seed=0, acq=None, h0=0.1, h_min=1e-3, stats=None):
+def select(model, q=1, n_raw=512, n_restarts=20, max_iter=400, seed=0, acq=None, h0=0.1, h_min=1e-3, stats=None, device_append=True):
     """q sequential greedy picks (optimize_acqf(..., sequential=True)). Per pick: n_raw scrambled Sobol points in one launch, the best
     n_restarts refined by compass_search, the best restart is the pick and is appended to the baseline. acq: DeviceAcquisition (the
-    default, created and closed here) or any object with set_model / evaluate. Returns picks (q x d), their values, the final model."""
+    default, created and closed here) or any object with set_model / evaluate. Returns picks (q x d), their values, the final model.
+    A model packed with baseline="device" is built by the evaluator's set_model; where the evaluator has append_pick (and device_append
+    is left on) the picks are appended there too and the final model is completed from model_arrays(); otherwise the built model is
+    read back once and the picks are appended on the host."""
     own = acq is None
     if own:
         acq = DeviceAcquisition()
     try:
         picks, values = [], []
+        on_device = False          # the model was built on the device and the evaluator appends there: nothing is uploaded after the build
         for i in range(int(q)):
-            acq.set_model(model, keep_gp=i > 0)
+            if not on_device:
+                acq.set_model(model, keep_gp=i > 0)
+            if model.device_baseline:          # (built on the device just now)
+                if not hasattr(acq, "model_arrays"):
+                    raise ValueError("select: a model packed with baseline='device' needs an evaluator with model_arrays (DeviceAcquisition)")
+                on_device = hasattr(acq, "append_pick") and device_append
+                if not on_device:          # (the picks are appended on the host to what the device built)
+                    model = complete_model(model, acq.model_arrays())
             raw = sobol_points(n_raw, model.d, list(np.atleast_1d(seed)) + [i])
             t0 = time.perf_counter()
             v = np.asarray(acq.evaluate(raw))
@@ -489,7 +697,13 @@ def select(model, q=1, n_raw=512, n_restarts=20, max_iter=400, seed=0, acq=None,
                 stats.append({"launches": launches + 1, "seconds": time.perf_counter() - t0})
             b = int(np.argmax(val))
             picks.append(X[b].copy()); values.append(float(val[b]))
-            model = append_pick(model, X[b])
+            if on_device:
+                acq.append_pick(X[b])
+                model = replace(model, Xb=np.vstack([model.Xb, X[b][None, :]]))
+            else:
+                model = append_pick(model, X[b])
+        if on_device:
+            model = complete_model(model, acq.model_arrays())
         return np.array(picks), np.array(values), model
     finally:
         if own:
@@ -816,9 +1030,11 @@ class BayesianOptimization:
         objective(params_nat (P x d)) -> (objectives (P x 2 x 2), feasible (P,))      -- closed_loop.evaluate_segments
     bounds: 2 x d natural lower / upper bounds. acq: "device" (DeviceAcquisition), "host" (host_acquisition) or an evaluator.
     The reference standardises Y for the GP but hands the acquisition the reference point in raw units; that is kept as the default
-    (config standardize_ref_point=False); True maps the reference point into the standardised units."""
+    (config standardize_ref_point=False); True maps the reference point into the standardised units. model_backend "device": the
+    baseline is pruned on the device (prune_baseline(backend="device")) and its posterior, draws and fronts are built there
+    (pack_model(baseline="device")); it needs the device acquisition. "host", the default, is the numpy path."""
 
-    def __init__(self, bounds, config, objective, acq="device", fit_device="cpu", fit_backend="torch"):
+    def __init__(self, bounds, config, objective, acq="device", fit_device="cpu", fit_backend="torch", model_backend="host"):
         self.bounds = np.asarray(bounds, dtype=np.float64)
         self.d = self.bounds.shape[1]
         self.config = dict(DEFAULT_CONFIG); self.config.update(config or {})
@@ -826,11 +1042,25 @@ class BayesianOptimization:
         if fit_backend not in ("torch", "device"):
             raise ValueError(f"BayesianOptimization: fit_backend {fit_backend!r} is neither 'torch' nor 'device'")
         self.fit_backend, self._gp = fit_backend, None          # (one DeviceGP for every fit and factor of the campaign)
+        if model_backend not in ("host", "device"):
+            raise ValueError(f"BayesianOptimization: model_backend {model_backend!r} is neither 'host' nor 'device'")
+        if model_backend == "device" and not (acq == "device" or isinstance(acq, DeviceAcquisition)):
+            raise ValueError("BayesianOptimization: model_backend 'device' needs acq 'device' or a DeviceAcquisition")
+        self.model_backend, self._model_acq = model_backend, None          # (one handle for every pruning of the campaign)
         self.ref = np.array([self.config["reference_point_0"], self.config["reference_point_1"]], dtype=np.float64)
         self.trials, self.active_group = [], 0
         self.hypervolumes, self.hv_traces, self.pareto_trials = [0.0, 0.0], [], [[], []]
         self.times, self.fallbacks, self.groups_used = [], 0, []
         self._draws = 0
+
+    def close(self):
+        """Free the device handles the driver created (the surrogate fit's and the model's); one that was handed in stays open."""
+        if self._gp is not None:
+            self._gp.close()
+            self._gp = None
+        if self._model_acq is not None and self._model_acq is not self.acq:
+            self._model_acq.close()
+        self._model_acq = None
 
     # -- data
     def unnormalize(self, X):
@@ -890,12 +1120,17 @@ class BayesianOptimization:
         cm = ConstraintModel(Xn, feas, device=self.fit_device, max_iter=cfg["fit_max_iter"], backend=self.fit_backend, gp=self._gp)
         ref = (self.ref[group] - om.mean) / om.std if cfg["standardize_ref_point"] else self.ref[group]
         S, q = int(cfg["n_sobol_samples"]), int(cfg["batch_size"])
-        keep = prune_baseline(Xt, om.Ys, om.hyp, S=S, seed=[int(cfg["seed"]), 11, len(self.trials)], jitter=cfg["jitter"]) \
+        dev = {}
+        if self.model_backend == "device" and cfg["prune_baseline"]:
+            if self._model_acq is None:
+                self._model_acq = self.acq if isinstance(self.acq, DeviceAcquisition) else DeviceAcquisition()
+            dev = dict(backend="device", acq=self._model_acq, factor=self._gp.gp_factor if self._gp is not None else None)
+        keep = prune_baseline(Xt, om.Ys, om.hyp, S=S, seed=[int(cfg["seed"]), 11, len(self.trials)], jitter=cfg["jitter"], **dev) \
             if cfg["prune_baseline"] else np.arange(len(Xt))
         keep = keep[:NB_MAX - q - 1]
         Z = sobol_normal(S, 2 * (len(keep) + q + 1), [int(cfg["seed"]), 13, len(self.trials)]).reshape(S, 2, -1).transpose(0, 2, 1)
         return pack_model(Xt, om.Ys, om.hyp, Xn, feas, cm.hyp, Xt[keep], Z, ref, eps=cfg["epsilon"], jitter=cfg["jitter"], K=cfg["gh_nodes"],
-                          factor=self._gp.gp_factor if self._gp is not None else None)
+                          factor=self._gp.gp_factor if self._gp is not None else None, baseline=self.model_backend)
 
     def perform_bayesian_optimization_step(self):
         """One iteration: fit, select batch_size candidates, evaluate them. Returns (t_fit, t_select, t_evaluate), or None where the
@@ -911,8 +1146,13 @@ class BayesianOptimization:
             return self._fallback()
         t1 = time.perf_counter()
         acq = {"device": None, "host": HostAcquisition()}.get(self.acq, self.acq) if isinstance(self.acq, str) else self.acq
-        picks, _, _ = select(model, q=cfg["batch_size"], n_raw=cfg["n_raw_samples"], n_restarts=cfg["n_restarts"], max_iter=cfg["max_iter"],
-                             seed=[int(cfg["seed"]), 17, len(self.trials)], acq=acq)
+        try:
+            picks, _, _ = select(model, q=cfg["batch_size"], n_raw=cfg["n_raw_samples"], n_restarts=cfg["n_restarts"], max_iter=cfg["max_iter"],
+                                 seed=[int(cfg["seed"]), 17, len(self.trials)], acq=acq)
+        except ModelFittingError:          # (a baseline the device builds is factored inside select's first set_model)
+            if not model.device_baseline:
+                raise
+            return self._fallback()
         t2 = time.perf_counter()
         self._evaluate(np.clip(picks, 0.0, 1.0))
         t3 = time.perf_counter()

@@ -6,7 +6,29 @@ constexpr int BO_CHUNK = 512;          // candidates per pass of the kernel chai
 constexpr int BO_MAXN = 4096, BO_MAXB = 512, BO_MAXS = 4096;
 enum { BO_T_KERN, BO_T_TRI, BO_T_MOM, BO_T_CROSS, BO_T_TRI2, BO_T_HVI, BO_T_FINAL, BO_TIMERS };
 
+// what tum_bom_prune, tum_bom_fronts, tum_bom_build and tum_bom_append (bo_model.hpp) keep on the device: grown on demand, never read before the call wrote it
+enum { BOM_T_KERN, BOM_T_H, BOM_T_SIG, BOM_T_CHOL, BOM_T_MEAN, BOM_T_DRAW, BOM_T_DOM, BOM_TIMERS };
+constexpr int BOM_EVENTS = 2 * (BOM_T_DOM + 1) + 2;
+enum { BOMB_T_KERN, BOMB_T_H, BOMB_T_SIG, BOMB_T_CHOL, BOMB_T_TRINV, BOMB_T_MEAN, BOMB_T_DRAW, BOMB_T_PACK, BOMB_T_FRONT, BOMB_TIMERS };
+constexpr int BOMB_EVENTS = 2 * (BOMB_T_FRONT + 1) + 2;
+struct BomWork {
+    DevBuf<double> X, K, W, H, A, Z, a, m, F, minpiv, Fb, fronts;
+    DevBuf<int> keep, bad, count;
+    // tum_bom_build: the dense baseline posterior of the resident model, per objective, for tum_bom_model_read
+    bool built = false;
+    DevBuf<double> Kbb, Mt, Hd[2], Ld[2], Rd[2], mub[2], Fbm, Zf[2];
+    DevBuf<int> okapp;
+    int cap = 0, ldb = 0, ncol = 0;          // baseline points the resident arrays hold room for; their leading dimension; columns of Zfull
+    hipEvent_t ev[BOM_EVENTS] = {};
+    double ms[BOM_TIMERS] = {};
+    bool profile = false;
+    hipEvent_t evb[BOMB_EVENTS] = {};          // tum_bom_build's timers
+    double msb[BOMB_TIMERS] = {};
+    bool profile_build = false;
+};
+
 struct tum_bo {
+    BomWork work;
     int device = 0;
     hipStream_t stream = nullptr;
     bool have_model = false, profile = false;
@@ -92,6 +114,10 @@ extern "C" void tum_bo_free(tum_bo *b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (int i = 0; i <= BO_TIMERS; i++)
         if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
+    for (int i = 0; i < BOM_EVENTS; i++)
+        if (b->work.ev[i]) (void)hipEventDestroy(b->work.ev[i]);
+    for (int i = 0; i < BOMB_EVENTS; i++)
+        if (b->work.evb[i]) (void)hipEventDestroy(b->work.evb[i]);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;          // (the buffers free under the guard)
 }
@@ -109,6 +135,38 @@ static int bo_model_gp(tum_bo *b, const tum_bo_model_desc *m)
         BOCHK(bo_upload(b->V[g], V.data(), V.size()));
         b->s[g] = m->s[g]; b->c[g] = m->c[g];
     }
+    return 0;
+}
+
+// the sizes of a model, as tum_bo_model and tum_bom_build (bo_model.hpp) set them
+static void bo_model_sizes(tum_bo *b, int d, int n_t, int n_c, int n_b, int S, int P_max, int K, double eps)
+{
+    b->d = d;
+    const int ns[BO_SETS] = {n_t, n_t, n_c, n_c, n_b, n_b};
+    for (int g = 0; g < BO_SETS; g++) { b->n[g] = ns[g]; b->np[g] = bo_pad16(ns[g]); }
+    b->S = S; b->nts = bo_pad16(S) >> 4; b->P_max = P_max; b->K = K; b->eps = eps;
+}
+
+// the quadrature rule and the chunk's buffers of a model whose sizes are set
+static int bo_model_chunk(tum_bo *b, const double *gh_x, const double *gh_w)
+{
+    std::vector<double> gh(2 * BO_MAXK, 0.0);
+    for (int i = 0; i < b->K; i++) { gh[i] = gh_x[i]; gh[BO_MAXK + i] = gh_w[i]; }
+    BOCHK(bo_upload(b->gh, gh.data(), gh.size()));
+    // the chunk's buffers: every element of them is written by the chain before it is read
+    const size_t nct = BO_CHUNK / 16;
+    HIPCHK(b->x.reserve((size_t)BO_CHUNK * BO_MAXD));
+    for (int g = 0; g < BO_SETS; g++) HIPCHK(b->k[g].alloc(nct * b->np[g] * 16, false));
+    for (int g = 0; g < BO_GP; g++) { HIPCHK(b->part[g].alloc(nct * b->np[g], false)); HIPCHK(b->dot[g].alloc(nct * b->np[g], false)); }
+    for (int o = 0; o < 2; o++) {
+        HIPCHK(b->q[o].alloc(nct * b->np[0] * 16, false));
+        HIPCHK(b->sig[o].alloc(nct * b->np[4] * 16, false));
+        HIPCHK(b->l[o].alloc(nct * b->np[4] * 16, false));
+        HIPCHK(b->llpart[o].alloc(nct * b->np[4], false));
+    }
+    HIPCHK(b->mom.reserve((size_t)BO_GP * BO_CHUNK * 2));
+    HIPCHK(b->hvpart.alloc(nct * b->nts * 16, false));
+    HIPCHK(b->alpha.reserve(BO_CHUNK)); HIPCHK(b->detail.reserve((size_t)BO_CHUNK * BO_DETAIL));
     return 0;
 }
 
@@ -137,12 +195,9 @@ extern "C" int tum_bo_model(tum_bo *b, const tum_bo_model_desc *m)
         if (m->front_count[s] < 0 || m->front_count[s] > m->P_max) return fail("tum_bo_model: front_count outside 0..P_max");
     DevGuard guard(b->device); GUARD_OK(guard);
     HIPCHK(hipStreamSynchronize(b->stream));
-    b->have_model = false;
+    b->have_model = false; b->work.built = false;
     if (!m->keep_gp) BOCHK(bo_model_gp(b, m));
-    b->d = m->d;
-    const int ns[BO_SETS] = {m->n_t, m->n_t, m->n_c, m->n_c, m->n_b, m->n_b};
-    for (int g = 0; g < BO_SETS; g++) { b->n[g] = ns[g]; b->np[g] = bo_pad16(ns[g]); }
-    b->S = m->S; b->nts = bo_pad16(m->S) >> 4; b->P_max = m->P_max; b->K = m->K; b->eps = m->eps;
+    bo_model_sizes(b, m->d, m->n_t, m->n_c, m->n_b, m->S, m->P_max, m->K, m->eps);
     BOCHK(bo_upload(b->X[1], m->Xb, (size_t)m->n_b * m->d));
     for (int o = 0; o < 2; o++) {
         b->jitter[o] = m->jitter[o]; b->ref[o] = m->ref[o];
@@ -156,23 +211,7 @@ extern "C" int tum_bo_model(tum_bo *b, const tum_bo_model_desc *m)
     BOCHK(bo_upload(b->fronts, m->fronts, (size_t)m->S * m->P_max * 2));
     HIPCHK(b->count.alloc(m->S));
     HIPCHK(hipMemcpy(b->count.get(), m->front_count, sizeof(int) * m->S, hipMemcpyHostToDevice));
-    std::vector<double> gh(2 * BO_MAXK, 0.0);
-    for (int i = 0; i < m->K; i++) { gh[i] = m->gh_x[i]; gh[BO_MAXK + i] = m->gh_w[i]; }
-    BOCHK(bo_upload(b->gh, gh.data(), gh.size()));
-    // the chunk's buffers: every element of them is written by the chain before it is read
-    const size_t nct = BO_CHUNK / 16;
-    HIPCHK(b->x.reserve((size_t)BO_CHUNK * BO_MAXD));
-    for (int g = 0; g < BO_SETS; g++) HIPCHK(b->k[g].alloc(nct * b->np[g] * 16, false));
-    for (int g = 0; g < BO_GP; g++) { HIPCHK(b->part[g].alloc(nct * b->np[g], false)); HIPCHK(b->dot[g].alloc(nct * b->np[g], false)); }
-    for (int o = 0; o < 2; o++) {
-        HIPCHK(b->q[o].alloc(nct * b->np[0] * 16, false));
-        HIPCHK(b->sig[o].alloc(nct * b->np[4] * 16, false));
-        HIPCHK(b->l[o].alloc(nct * b->np[4] * 16, false));
-        HIPCHK(b->llpart[o].alloc(nct * b->np[4], false));
-    }
-    HIPCHK(b->mom.reserve((size_t)BO_GP * BO_CHUNK * 2));
-    HIPCHK(b->hvpart.alloc(nct * b->nts * 16, false));
-    HIPCHK(b->alpha.reserve(BO_CHUNK)); HIPCHK(b->detail.reserve((size_t)BO_CHUNK * BO_DETAIL));
+    BOCHK(bo_model_chunk(b, m->gh_x, m->gh_w));
     HIPCHK(hipDeviceSynchronize());
     b->have_model = true;
     return 0;

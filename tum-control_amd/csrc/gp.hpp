@@ -73,6 +73,11 @@ extern "C" int tum_gp_data(tum_gp *g, const double *X, const double *y, const do
     return 0;
 }
 
+// the blocked right-looking Cholesky of the lower tiles of f.A, in place: per block column the diagonal block (with its inverse into the
+// diagonal tile of f.V), the panel below it and the trailing update. Shared with the posterior covariance of bo_model.hpp. (Defined
+// behind gp_chain: the kernels keep the order of first use they had.)
+static int gp_cholesky(GpFacArgs f, int nb, hipStream_t st);
+
 // the chain on the handle's stream. grad: A^-1 and the gradient; alpha: a = V^T w (implied by grad).
 static int gp_chain(tum_gp *g, const double *theta, int learn, double floor_, bool want_alpha, bool want_grad)
 {
@@ -92,15 +97,7 @@ static int gp_chain(tum_gp *g, const double *theta, int learn, double floor_, bo
     mark();
     GpFacArgs f{};
     f.n = n; f.np = np; f.A = g->A.get(); f.V = g->V.get(); f.M = g->M.get(); f.minpiv = g->minpiv.get(); f.bad = g->bad.get();
-    for (int k = 0; k < nb; k++) {
-        f.k = k;
-        LAUNCH(gp_potrf_kernel<>, dim3(1), dim3(256), 0, st, f);
-        const int m = nb - k - 1;
-        if (m > 0) {
-            LAUNCH(gp_trsm_kernel<>, dim3(m), dim3(256), 0, st, f);
-            LAUNCH(gp_syrk_kernel<>, dim3(m, m), dim3(256), 0, st, f);
-        }
-    }
+    BOCHK(gp_cholesky(f, nb, st));
     mark();
     if (nb > 1) LAUNCH(gp_lhat_kernel<>, dim3(nb, nb, 4), dim3(64), 0, st, f);
     for (int sdiag = 1; sdiag < nb; sdiag++) {
@@ -127,6 +124,22 @@ static int gp_chain(tum_gp *g, const double *theta, int learn, double floor_, bo
     mark();
     LAUNCH(gp_reduce_kernel<>, dim3(1), dim3(256), 0, st, v);
     mark();
+    return 0;
+}
+
+// (Keep this definition BEHIND gp_chain: a template kernel's code is emitted where it is first used, and gp_chain's first uses fix
+// the order the K16 kernels have in the code object. Moving it in front would put potrf / trsm / syrk before gp_kern_kernel.)
+static int gp_cholesky(GpFacArgs f, int nb, hipStream_t st)
+{
+    for (int k = 0; k < nb; k++) {
+        f.k = k;
+        LAUNCH(gp_potrf_kernel<>, dim3(1), dim3(256), 0, st, f);
+        const int m = nb - k - 1;
+        if (m > 0) {
+            LAUNCH(gp_trsm_kernel<>, dim3(m), dim3(256), 0, st, f);
+            LAUNCH(gp_syrk_kernel<>, dim3(m, m), dim3(256), 0, st, f);
+        }
+    }
     return 0;
 }
 

@@ -28,6 +28,7 @@
 #include "rti_kernels.hpp"
 #include "bo_kernels.hpp"
 #include "gp_kernels.hpp"
+#include "bo_model_kernels.hpp"
 
 using namespace tum;
 
@@ -2203,3 +2204,4 @@ extern "C" int tum_ocp_constraints_get(tum_ocp *c, int stage, const char *field,
 #include "sim_rl.hpp"            // K11 to K14: the RL environment, the agent, collection, the trainer
 #include "bo.hpp"                // K15: tum_bo, the acquisition value of the Bayesian-optimisation step
 #include "gp.hpp"                // K16: tum_gp, the marginal log-likelihood of a surrogate and its factor
+#include "bo_model.hpp"          // K17: tum_bom_prune / fronts / build / append / model_read: the acquisition model built on the device

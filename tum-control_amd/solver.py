@@ -85,6 +85,10 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
 BO_SYMBOLS = ["tum_bo_create", "tum_bo_free", "tum_bo_model", "tum_bo_evaluate", "tum_bo_profile"]
 # the entry points of the surrogate fit (bo.DeviceGP), a list of their own for the same reason
 GP_SYMBOLS = ["tum_gp_create", "tum_gp_free", "tum_gp_data", "tum_gp_mll", "tum_gp_factor", "tum_gp_profile"]
+# the entry points that build parts of the acquisition model on the device (bo.prune_baseline, bo.build_fronts): they work on a tum_bo
+# handle; their prefix is their own because tests/test_bo_host.py holds the tum_bo_ names of the header to BO_SYMBOLS
+BOM_SYMBOLS = ["tum_bom_prune_desc_init", "tum_bom_prune", "tum_bom_fronts", "tum_bom_prune_profile",
+               "tum_bom_build_desc_init", "tum_bom_build", "tum_bom_model_read", "tum_bom_build_profile", "tum_bom_append"]
 
 
 def load_library(path=None):
@@ -190,6 +194,16 @@ def load_library(path=None):
         L.tum_bo_model.argtypes = [vp, vp]
         L.tum_bo_evaluate.argtypes = [vp, dp, ci, dp, dp]
         L.tum_bo_profile.argtypes = [vp, ci, dp]
+    if hasattr(L, "tum_bom_prune"):
+        L.tum_bom_prune_desc_init.restype = None; L.tum_bom_prune_desc_init.argtypes = [vp]
+        L.tum_bom_prune.argtypes = [vp, vp, ip, dp, ip]
+        L.tum_bom_fronts.argtypes = [vp, dp, ci, ci, dp, dp, ip]
+        L.tum_bom_prune_profile.argtypes = [vp, ci, dp]
+        L.tum_bom_build_desc_init.restype = None; L.tum_bom_build_desc_init.argtypes = [vp]
+        L.tum_bom_build.argtypes = [vp, vp, ip]
+        L.tum_bom_build_profile.argtypes = [vp, ci, dp]
+        L.tum_bom_append.argtypes = [vp, dp, ip]
+        L.tum_bom_model_read.argtypes = [vp, vp, vp, vp, vp, dp, dp, ip, ip]
     if hasattr(L, "tum_gp_create"):
         L.tum_gp_create.restype = vp; L.tum_gp_create.argtypes = [ci]
         L.tum_gp_free.restype = None; L.tum_gp_free.argtypes = [vp]
