@@ -329,6 +329,16 @@ double tum_ocp_last_kernel_ms(tum_ocp *c);
  * (N <= 40): out = [H 80x80 | q 80 | steering-angle row and gg row of every stage, 2N x 80 | their constants 2N]; see
  * csrc/tum_nmpc.hip */
 int tum_ocp_debug_dump(tum_ocp *c, int b, double *out, int len);
+/* read-only: the condensed QP of the instances b0 .. b0 + nb - 1 as the LAST preparation or solve left it in the hand-over buffers of the
+ * pipeline -- every horizon (NVP = 80 | 96 | 112 condensed variables incl. the padding for N <= 40 | 48 | 56), whichever condensing
+ * kernel ran. Launches nothing, changes nothing.
+ *   info[3]: NVP, 2 N, and 1 where dv is the step of this QP (0: the expansion ran as the tail of the interior point kernel, which
+ *            hands no step over -- batches of at most 1024 instances below seven tiles)
+ *   H nb x NVP x NVP (diagonal tiles as stored, both triangles) | q, d, dv nb x NVP | C nb x 2 N x NVP
+ *   rows: 2 (s - 1) the steering-angle row of stage s (synthesised: dt on the odd columns below 2 s), 2 (s - 1) + 1 its gg row
+ * Null array pointers are skipped (all null: info only). Refused before the first pipeline preparation / solve, on the development
+ * kernel 'fused' (no hand-over buffers) and for an instance range out of bounds. */
+int tum_ocp_get_condensed_qp(tum_ocp *c, int b0, int nb, double *H, double *q, double *C, double *d, double *dv, int *info);
 
 /* ---- the small kernels either side of the solve ---------------------------------
  * Scenario fan-out of the initial state (Stochastic_NMPC/stochastic_mpc_utils.py:78-91 compute_x0dist as a

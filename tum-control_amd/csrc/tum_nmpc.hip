@@ -147,6 +147,9 @@ struct tum_ocp {
     // uniform_powers: options_set "uniform_powers", 1 by default -- the record-free condensing forms the sequences A^m B and g_s once per
     // instance (cond_uniform_kernel); 0: every lane carries its column through every stage (cond_uniform_columns_kernel). Same results, to the bit.
     int uniform_powers = 1;
+    // tum_ocp_get_condensed_qp: the hand-over buffers hold a condensed QP (a pipeline preparation or solve has run); PV_DV holds the
+    // step of that QP (the interior point kernel wrote it for an expansion kernel behind it: its own tail keeps the step in LDS)
+    bool qp_handed = false, dv_handed = false;
 };
 
 // cold_start() / reset() re-initialise the iterate: a capsule the safety net has failed works again from there. The word may only be
@@ -1108,6 +1111,8 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, Part part)
     const long long items = (long long)c->batch * (c->N + 1);
     const dim3 g_cols((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), g_lane((unsigned)((items + 63) / 64)), g_ocp(c->batch), wave(64);
     if (part != Part::FEEDBACK) c->lin_ahead = false;
+    if (plan.cond != Cond::NONE) { c->qp_handed = true; c->dv_handed = false; }
+    if (plan.ipm != Ipm::NONE) c->dv_handed = plan.ipm != Ipm::FUSED_TAIL;
     if (plan.lin_ahead_flag) pa.ka.flags |= KF_LIN_AHEAD;          // (launch_lin_ahead ran it on another stream; the caller has joined that stream)
     if (plan.lin == Lin::SN_LANE || plan.lin == Lin::SN_COLS) {   // coupled SNMPC OCP: sample fan-out and prologue first, the QP solution goes to the epilogue through the workspace
         if (c->fanout && sn_fanout(c)) return 1;
@@ -2019,6 +2024,70 @@ extern "C" int tum_ocp_debug_dump(tum_ocp *c, int b, double *out, int len)
         // (development aid: the tail of the dump area carries the phase cycle counters of the SNMPC prologue kernels, SnArgs::dbg)
         HIPCHK(hipMemcpy(o.data() + 20000, c->ddbg + (size_t)b * DBG_STRIDE + 20000, sizeof(double) * (DBG_STRIDE - 20000), hipMemcpyDeviceToHost));
         memcpy(out, o.data(), sizeof(double) * len);
+        return 0;
+    });
+}
+
+// The condensed QP of the instances b0 .. b0 + nb - 1 as the LAST preparation or solve left it in the hand-over buffers of the
+// pipeline, at every tile count and whichever condensing kernel ran. Launches nothing and writes nothing on the device.
+//   info[0] = NVP (16 x tiles: condensed variables incl. the padding), info[1] = 2 N (rows), info[2] = 1 where dv is the step of
+//   this QP (see below), 0 where the buffer does not hold it
+//   H  nb x NVP x NVP, symmetric, unpacked from the accumulator-layout tiles (PD<NT>::tidx)
+//   q  nb x NVP | d  nb x NVP: d[2 (s - 1)] the steering-angle row of stage s, d[2 (s - 1) + 1] its gg row
+//   C  nb x 2 N x NVP: the same rows; the gg rows from the operand layout (PD<NT>::cidx), the steering-angle rows synthesised (dt on
+//      the odd columns below 2 s) as the debug dump does -- no kernel stores them
+//   dv nb x NVP: what PV_DV holds. The interior point kernel writes it for an expansion KERNEL behind it (batches beyond 1024, seven
+//      tiles, the record-free chain, the coupled SNMPC OCP); where the expansion is its own tail the step stays in LDS: info[2] = 0
+// Any of the array pointers may be null (skipped); with all of them null the call only answers info.
+extern "C" int tum_ocp_get_condensed_qp(tum_ocp *c, int b0, int nb, double *H, double *q, double *C, double *d, double *dv, int *info)
+{
+    if (!c) return fail("null capsule");
+#ifdef TUM_DEV_KERNELS
+    if (c->kmode == KMode::FUSED) return fail("get_condensed_qp: the development kernel 'fused' condenses in registers and LDS and has no hand-over buffers (use 'auto' or 'pipeline')");
+#endif
+    if (!c->qp_handed || !c->dhws || !c->dcws || !c->dvec) return fail("get_condensed_qp: no preparation or solve has run on the pipeline yet: there is no condensed QP to read");
+    if (b0 < 0 || nb < 0 || (long long)b0 + nb > c->batch) return fail("get_condensed_qp: instance range out of bounds");
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (lin_uniform_check(c)) return 1;
+    return with_tiles(c, [&](auto ntc) {
+        using D = PD<decltype(ntc)::value>;
+        constexpr int NT = D::NT, NVP = D::NVP;
+        const int N = c->N, m = 2 * N;
+        if (info) { info[0] = NVP; info[1] = m; info[2] = c->dv_handed ? 1 : 0; }
+        std::vector<double> hw((size_t)D::NTT * 256), cw((size_t)D::NCH * 64), vv(D::PVEC);
+        for (int i = 0; i < nb; i++) {
+            const size_t b = (size_t)b0 + i;
+            if (H) {
+                HIPCHK(hipMemcpy(hw.data(), c->dhws + b * D::NTT * 256, sizeof(double) * hw.size(), hipMemcpyDeviceToHost));
+                double *o = H + (size_t)i * NVP * NVP;
+                for (int K = 0; K < NT; K++)
+                    for (int I = K; I < NT; I++)
+                        for (int l = 0; l < 64; l++)
+                            for (int jj = 0; jj < 4; jj++) {         // accumulator layout: row (l >> 4) + 4 jj, column l & 15
+                                const int row = 16 * K + (l >> 4) + 4 * jj, col = 16 * I + (l & 15);
+                                const double v = hw[((size_t)D::tidx(K, I) * 64 + l) * 4 + jj];
+                                o[(size_t)row * NVP + col] = v;
+                                if (K != I) o[(size_t)col * NVP + row] = v;          // (a diagonal tile holds both triangles: they go out as stored, so that an asymmetry shows)
+                            }
+            }
+            if (q || d || dv) {
+                HIPCHK(hipMemcpy(vv.data(), c->dvec + b * D::PVEC, sizeof(double) * vv.size(), hipMemcpyDeviceToHost));
+                if (q) memcpy(q + (size_t)i * NVP, vv.data() + D::PV_Q, sizeof(double) * NVP);
+                if (d) memcpy(d + (size_t)i * NVP, vv.data() + D::PV_D, sizeof(double) * NVP);
+                if (dv) memcpy(dv + (size_t)i * NVP, vv.data() + D::PV_DV, sizeof(double) * NVP);
+            }
+            if (C) {
+                HIPCHK(hipMemcpy(cw.data(), c->dcws + b * D::NCH * 64, sizeof(double) * cw.size(), hipMemcpyDeviceToHost));
+                double *o = C + (size_t)i * m * NVP;
+                for (int s = 1; s <= N; s++)
+                    for (int col = 0; col < NVP; col++) {
+                        o[(size_t)(2 * (s - 1)) * NVP + col] = ((col & 1) && col < 2 * s) ? c->ka.dt : 0.0;
+                        const int cc = (s - 1) >> 2, lq = (s - 1) & 3, T = col >> 4;       // operand layout: chunk cc, DPP row lq, tile column T
+                        o[(size_t)(2 * (s - 1) + 1) * NVP + col] = (cc >= 2 * T) ? cw[(size_t)D::cidx(cc, T) * 64 + 16 * lq + (col & 15)] : 0.0;
+                    }
+            }
+        }
         return 0;
     });
 }

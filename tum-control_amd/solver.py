@@ -70,7 +70,7 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_ocp_solve", "tum_ocp_solve_async", "tum_ocp_synchronize", "tum_ocp_options_set",
              "tum_ocp_get_cost", "tum_ocp_get_stats", "tum_ocp_reset", "tum_ocp_get_from_qp_in",
              "tum_ocp_set_stream", "tum_ocp_get_device", "tum_ocp_put_device", "tum_ocp_bind_device", "tum_ocp_results_async", "tum_ocp_results_wait", "tum_ocp_results_outstanding", "tum_ocp_step_async", "tum_ocp_cold_start", "tum_ocp_last_kernel_ms",
-             "tum_ocp_debug_dump", "tum_ocp_profile_phases", "tum_ocp_set_schedule", "tum_ocp_set_kernel",
+             "tum_ocp_debug_dump", "tum_ocp_get_condensed_qp", "tum_ocp_profile_phases", "tum_ocp_set_schedule", "tum_ocp_set_kernel",
              "tum_ocp_set_x0_fanout", "tum_pce_moments", "tum_pce_attach", "tum_pce_moments_device",
              "tum_ocp_bounds_snapshot", "tum_ocp_bounds_restore", "tum_ocp_r2_backoff", "tum_ocp_r2_attach", "tum_ocp_constraints_get",
              "tum_ocp_snmpc_attach", "tum_ocp_snmpc_samples", "tum_ocp_snmpc_set_offsets",
@@ -141,6 +141,8 @@ def load_library(path=None):
         L.tum_ocp_step_async.argtypes = [vp, vp, vp, ci]
     L.tum_ocp_last_kernel_ms.restype = ctypes.c_double; L.tum_ocp_last_kernel_ms.argtypes = [vp]
     L.tum_ocp_debug_dump.argtypes = [vp, ci, dp, ci]
+    if hasattr(L, "tum_ocp_get_condensed_qp"):
+        L.tum_ocp_get_condensed_qp.argtypes = [vp, ci, ci, dp, dp, dp, dp, dp, ctypes.POINTER(ci)]
     L.tum_ocp_profile_phases.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     L.tum_ocp_set_x0_fanout.argtypes = [vp, dp, dp, ci, ci]
     L.tum_pce_moments.argtypes = [vp, cs, ci, dp, ci, ci, dp, dp]
@@ -678,6 +680,21 @@ class BatchedOcpSolver:
         out = np.zeros(n)
         self._chk(self._L.tum_ocp_debug_dump(self._h, b, _dp(out), n), "debug_dump")
         return out
+
+    def get_condensed_qp(self, b0=0, nb=None):
+        """The condensed QP of the instances b0 .. b0 + nb - 1 as the last preparation or solve handed it to the interior point kernel
+        (read-only, launches nothing; every horizon, whichever condensing kernel ran): dict with H (nb, NVP, NVP), q (nb, NVP),
+        C (nb, 2 N, NVP), d (nb, 2 N), dv (nb, NVP) and dv_valid. NVP = 16 x tiles: the 2 N condensed inputs and the padding. Row
+        2 (s - 1) is the steering-angle row of stage s, row 2 (s - 1) + 1 its gg row. dv_valid False: the expansion ran as the tail of
+        the interior point kernel (at most 1024 instances, N <= 48), which hands no step over -- dv is not that of this QP."""
+        nb = self.batch - b0 if nb is None else int(nb)
+        info = (ctypes.c_int * 3)()
+        null = ctypes.POINTER(ctypes.c_double)()
+        self._chk(self._L.tum_ocp_get_condensed_qp(self._h, int(b0), nb, null, null, null, null, null, info), "get_condensed_qp")
+        nvp, m = int(info[0]), int(info[1])
+        H = np.zeros((nb, nvp, nvp)); q = np.zeros((nb, nvp)); C = np.zeros((nb, m, nvp)); d = np.zeros((nb, nvp)); dv = np.zeros((nb, nvp))
+        self._chk(self._L.tum_ocp_get_condensed_qp(self._h, int(b0), nb, _dp(H), _dp(q), _dp(C), _dp(d), _dp(dv), info), "get_condensed_qp")
+        return dict(H=H, q=q, C=C, d=d[:, :m].copy(), dv=dv, dv_valid=bool(info[2]))
 
     # ------------------------------------------------------------------ reference defaults
     def install_reference_ocp(self, Q=None, R=None, Qe=None, L1=None, L2=None, w_scale=0.01):
