@@ -212,7 +212,12 @@ int tum_ocp_solve_async(tum_ocp *c);
  * "uniform_powers"         1 (default): the condensing of that record-free path computes what is the same on every lane once per
  *                          instance -- the sequences A^m B and g_{s+1} = A g_s + defect -- and its stages read them from tables
  *                          (cond_uniform_kernel). 0: every lane carries its column of G through every stage
- *                          (cond_uniform_columns_kernel; A/B runs, tests). Results are bit-identical either way. */
+ *                          (cond_uniform_columns_kernel; A/B runs, tests). Results are bit-identical either way.
+ * "uniform_shift"          1 (default): cond_uniform_kernel at N <= 40 decides per instance whether the four cost weights of W are the
+ *                          same doubles (bit patterns; no NaN) at the stages 1 .. N - 1. Where they are, tile (j, I + j) of the
+ *                          condensed Hessian is tile (0, I) as it stood 8 j stages earlier plus the terminal stage's product, and
+ *                          only block row 0 is accumulated: 130 matrix products at N = 40, not 280. Every other instance runs the
+ *                          stage loop with all its products, as does 0 (A/B runs, tests). Results are bit-identical either way. */
 int tum_ocp_options_set(tum_ocp *c, const char *field, double value);
 int tum_ocp_synchronize(tum_ocp *c);
 
@@ -233,6 +238,8 @@ int tum_ocp_get_cost(tum_ocp *c, double *out, int b0, int nb);
  * "merit_weights" -> nb x 2 doubles: mu_eq, mu_in
  * "lin_uniform" -> 1 int: linearisations of this capsule that took the uniform path (options_set "lin_dedup") since it was created.
  * "records_skipped" -> 1 int: solves of this capsule that ran without stage records (options_set "uniform_records") since it was created.
+ * "cond_shifted" -> 1 int: instances of the LAST solve whose condensing took the shift form (options_set "uniform_shift"); 0 where the
+ *   last condensing was not cond_uniform_kernel.
  * "lpt_order" -> nb ints: entries b0 .. b0 + nb - 1 of the longest-first order the NEXT solve dispatches in (tum_ocp_set_schedule): the
  *   last solve's iteration counts, clipped to 0..63, descending; instances of one count by ascending index. The identity map while no
  *   order is kept (a batch of at most 1024, before the first solve). */

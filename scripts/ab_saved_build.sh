@@ -1,8 +1,8 @@
 #!/bin/bash
 # A/B of a SAVED build of the parent commit against the library of the working tree, run from the same tree on one box
 # (the protocol of profiles/lin_uniform_ab.txt and profiles/uniform_records_ab.txt):
-#   scripts/ab_saved_build.sh <parent libtumnmpc.so> [headline] [trace] [full] | [ktrace] [ktrace3] [onestream] [dump] [fullbench]
-#     headline  python bench.py, six fresh processes each, interleaved parent / change
+#   scripts/ab_saved_build.sh <parent libtumnmpc.so> [headline] [trace] [full] | [headline1] [ktrace] [ktrace3] [onestream] [dump] [fullbench]
+#     headline  python bench.py, six fresh processes each, interleaved parent / change (headline1: the same with --streams 1)
 #     trace     rocprofv3 --kernel-trace --stats -- python bench.py --streams 1 (kernel trace only, no counters) for each build: average and
 #               standard deviation per kernel; then bench.py --full --no-other-configs --no-cpu-baseline for each (value_single_stream)
 #     full      bench.py --dump-outputs (--steps 20 --warmup 3) for each build and the bitwise comparison of every .npy, then bench.py --full
@@ -22,12 +22,14 @@ EXP=""
 for leg in $LEGS; do case $leg in trace) EXP="$EXP ktrace onestream" ;; full) EXP="$EXP dump fullbench" ;; *) EXP="$EXP $leg" ;; esac; done
 for leg in $EXP; do
 case $leg in
-headline)
+headline|headline1)
+  # headline1: the same six pairs on ONE stream (bench.py --streams 1)
+  if [ $leg = headline1 ]; then HL_ARGS="--streams 1"; HL=s1_; else HL_ARGS=""; HL=""; fi
   for i in 1 2 3 4 5 6; do for w in parent change; do
     use $w
-    timeout -k 10 240 python bench.py > $OUT/${w}_$i.out 2> $OUT/${w}_$i.err < /dev/null || die "headline $w $i" $?
-    grep metric $OUT/${w}_$i.out > $OUT/${w}_$i.json
-    python -c "import json; d = json.load(open('$OUT/${w}_$i.json')); print('$w', $i, 'value', round(d['value']), 'ms/step', round(d['ms_per_step'], 4))"
+    timeout -k 10 240 python bench.py $HL_ARGS > $OUT/${HL}${w}_$i.out 2> $OUT/${HL}${w}_$i.err < /dev/null || die "$leg $w $i" $?
+    grep metric $OUT/${HL}${w}_$i.out > $OUT/${HL}${w}_$i.json
+    python -c "import json; d = json.load(open('$OUT/${HL}${w}_$i.json')); print('$leg', '$w', $i, 'value', round(d['value']), 'ms/step', round(d['ms_per_step'], 4))"
   done; done ;;
 ktrace|ktrace3)
   # ktrace: one stream; ktrace3: the default run's three streams (what a kernel waits for beside the other capsules' kernels shows here only)

@@ -946,6 +946,10 @@ __global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_columns_k
 //            five-tile build keeps the reference rows in LDS, so that no stage waits on the vector-memory counter (which would also
 //            wait for the stage's own gg-row store), and requests a stage's matrix operands one stage ahead (stage_body_pf;
 //            tests/test_gpu_cond_uniform_edges.py).
+//   shift    (profiles/cond_uniform_shift_ab.txt) five tiles, where the instance's cost weights are the same at the stages 1 .. N - 1:
+//            the stages accumulate block row 0 of H only, the tiles below it are snapshots of block row 0 plus the terminal stage's
+//            product and leave inside the loop (stage_body_pf with SH, emit_shifted; tests/test_gpu_cond_uniform_shift.py). Every
+//            other instance runs the stage loop with all its tiles, in the same kernel.
 template <int NT_> struct CondPow {
     static constexpr int NVP = 16 * NT_, NMAX = 8 * NT_;
     static constexpr int PAD = 2;               // in front of a row: the one step the P rows run beyond m = N - 1 lands here at N = NMAX
@@ -979,8 +983,9 @@ struct CondAhead {
     }
     template <int I> __device__ __forceinline__ double bop() const { return const_cast<CondAhead *>(this)->template bop<I>(); }
 };
+// use_shift: options_set "uniform_shift"; shifted[b]: 1 where the instance took the shift form of phase 2 (below), 0 where it did not
 template <int NT_>
-__device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const double *lin1)
+__device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const double *lin1, const int use_shift, int *shifted)
 {
     PD_LOCALS
     using T = CondPow<NT_>;
@@ -1091,6 +1096,22 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
         }
     }
     wsync();
+    // the verdict on the shift form of phase 2 (five tiles): the four cost weights, as the sums take them, are the same doubles at
+    // the stages 1 .. N - 1 -- bit patterns, not values (0.0 and -0.0 round products differently), and no NaN among them. Lane l
+    // looks at stage l + 1; stage N (W_e) and the rows 4 / 5 (R) do not enter. Read beside g_s below: no wait of its own.
+    bool shift = false;
+    if constexpr (PF) {
+        const bool chk = lane + 1 < N;
+        const int sv = chk ? lane + 1 : 1;
+        bool bad = false;
+#pragma unroll
+        for (int cr = 0; cr < 4; cr++) {          // (cost row)
+            const long long ws = __double_as_longlong(sWt[sv * 6 + cr]), w1 = __double_as_longlong(sWt[6 + cr]);
+            bad |= ws != w1 || (ws & 0x7fffffffffffffffLL) > 0x7ff0000000000000LL;
+        }
+        shift = use_shift != 0 && __ballot(chk && bad) == 0ull;
+    }
+    if (lane == 0) shifted[b] = shift ? 1 : 0;
     // d of the two rows of every stage: X_0[6] + g_s[6] and h + the gg-row sum of g_s
     if (lane < N) {
         gvec[PV_D + 2 * lane] = sG[(lane + 1) * 8 + 6] + gx6;
@@ -1181,9 +1202,48 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
     };
     // ENDS: the call site of the odd k, the stages that may close a segment -- the stage behind such a one has one tile more, and
     // stage 33 the operands of bank 1
-    auto stage_body_pf = [&](const int k, auto tsc, auto endsc, const Ahead &cur, Ahead &nxt, double &uyq) __attribute__((always_inline)) {
+    // ---- the SHIFT form of the five-tile build (SH; options_set "uniform_shift" 1, the default, and the verdict above).
+    // The table is one sequence: the operand of tile K + 1 at stage s is the operand of tile K at stage s - 8, the very same doubles.
+    // Where the weight of the stage is the same too, the product stage s adds to tile (K + 1, I + 1) is, bit for bit, the product
+    // stage s - 8 added to tile (K, I); both accumulators start from zero, so with equal weights at the stages 1 .. N - 1 tile
+    // (j, I + j) behind stage s <= N - 1 IS tile (0, I) behind stage s - 8 j. Only stage N differs (W_e, not dt W). Hence
+    //   Ht(j, I + j) = mfma(bop_{N - 8 j}[0] W_e, bop_{N - 8 j}[I], [Ht(0, I) behind stage N - 8 j - 1])
+    // -- the accumulator zero where N - 8 j - 1 < 1, the product left out where stage N - 8 j has no tile I (or does not exist) -- and
+    // a stage issues the products of block row 0 only: 130 of them at N = 40, not 280. The tiles (j, .) are formed behind stage
+    // N - 8 j - 1 from the accumulators and the operands that stage has requested for the next one, take their diagonal terms and
+    // leave for the workspace there and then (stores nobody waits for, as the gg row's). Same operations on the same operands in
+    // the same order: tests/test_gpu_cond_uniform_shift.py holds it to the column form and to the stage loop below with SH = false.
+    const double we = sWt[N * 6 + lq];          // the weight of the terminal products
+    // TN: the most tiles stage N - 8 j can have where this is called, tn: the tiles it has; o: its operands
+    auto emit_shifted = [&](const int j, auto tnc, const int tn, const Ahead &o) __attribute__((always_inline)) {
+        constexpr int TN = decltype(tnc)::value;
+        d4 *gh = reinterpret_cast<d4 *>(pa.hws) + (size_t)b * NTT * 64 + lane;
+        double aw = 0.0;
+        if constexpr (TN > 0) aw = o.b0 * we;
+        static_for<0, NT - 2>([&](auto ic) {
+            constexpr int I = decltype(ic)::value;
+            if (I + j < NT) {
+                d4 acc = Ht[I];
+                if constexpr (I < TN) { if (I < tn) acc = mfma(aw, o.template bop<I>(), acc); }
+                if constexpr (I == 0) {          // input cost (R) and padding on the diagonal, as behind the loop
+#pragma unroll
+                    for (int jj = 0; jj < 4; jj++) {
+                        const int row = lq + 4 * jj;
+                        if (row == lc) {
+                            const int idx = 16 * j + row;
+                            acc[jj] += (idx < nv) ? sWt[(idx >> 1) * 6 + 4 + (idx & 1)] : 1.0;
+                        }
+                    }
+                }
+                gh[(j * NT - j * (j - 1) / 2 + I) * 64] = acc;          // tidx(j, I + j)
+            }
+        });
+    };
+    auto stage_body_pf = [&](const int k, auto tsc, auto endsc, auto shc, const Ahead &cur, Ahead &nxt, double &uyq) __attribute__((always_inline)) {
         constexpr int Ts = decltype(tsc)::value;
         constexpr bool ENDS = decltype(endsc)::value;
+        constexpr bool SH = decltype(shc)::value;
+        constexpr int TA = SH ? 1 : Ts;              // block rows whose products the stage issues
         constexpr bool B1 = Ts >= 5;                 // columns 64.. exist from stage 33 on
         const int s = k + 1;
         const double *tb = sTab + PAD + 2 * (NMAX - s);
@@ -1200,8 +1260,8 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
             }
         }
         // the weighted operands of the stage: all of them AHEAD of the matrix instructions (as the column form)
-        double aopv[Ts];
-        static_for<0, Ts - 1>([&](auto kc) { constexpr int K = decltype(kc)::value; aopv[K] = cur.template bop<K>() * cur.wl; });
+        double aopv[TA];
+        static_for<0, TA - 1>([&](auto kc) { constexpr int K = decltype(kc)::value; aopv[K] = cur.template bop<K>() * cur.wl; });
         double wr[4], gsr[4], gt[4], gt1[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) wr[r] = sWt[s * 6 + r];          // (the stage's own weights, scaled; stage N: W_e)
@@ -1223,12 +1283,12 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
             }
         }
         static_assert(Ts <= 5, "the asm below lists five products");
-        if constexpr (Ts == 1) asm volatile("" : "+v"(aopv[0]));
-        if constexpr (Ts == 2) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]));
-        if constexpr (Ts == 3) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]));
-        if constexpr (Ts == 4) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]), "+v"(aopv[3]));
-        if constexpr (Ts == 5) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]), "+v"(aopv[3]), "+v"(aopv[4]));
-        static_for<0, Ts - 1>([&](auto kc) {
+        if constexpr (TA == 1) asm volatile("" : "+v"(aopv[0]));
+        if constexpr (TA == 2) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]));
+        if constexpr (TA == 3) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]));
+        if constexpr (TA == 4) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]), "+v"(aopv[3]));
+        if constexpr (TA == 5) asm volatile("" : "+v"(aopv[0]), "+v"(aopv[1]), "+v"(aopv[2]), "+v"(aopv[3]), "+v"(aopv[4]));
+        static_for<0, TA - 1>([&](auto kc) {
             constexpr int K = decltype(kc)::value;
             static_for<K, Ts - 1>([&](auto ic) { constexpr int I = decltype(ic)::value; Ht[tidx(K, I)] = mfma(aopv[K], cur.template bop<I>(), Ht[tidx(K, I)]); });
         });
@@ -1250,18 +1310,77 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
         // a DPP operand -- settle_dpp at the top of the next stage stands between it and the first read
         if (k + 1 < N) res = ures ? uxr - uyq : res;
         if (k + 3 < N) uyq = sYr[(k + 4) * 6];
+        // shift form: behind stage N - 8 j - 1 the tiles (j, .) are final but for the terminal product of stage s + 1 = N - 8 j, whose
+        // operands nxt holds (a stage that closes a segment has requested the next segment's tile with them)
+        if constexpr (SH) {
+            if (s < N - 1 && ((N - 1 - s) & 7) == 0) {
+                constexpr bool OPENS = ENDS && Ts < NT;
+                emit_shifted((N - 1 - s) >> 3, std::integral_constant<int, OPENS ? Ts + 1 : Ts>(), (OPENS && k + 1 == 8 * Ts) ? Ts + 1 : Ts, nxt);
+            }
+        }
+    };
+    // what stands behind the stage loop (SH, the shift form: of block row 0 only -- the other tiles have left with their diagonal terms)
+    auto finish = [&](auto shc) __attribute__((always_inline)) {
+        constexpr bool SH = decltype(shc)::value;
+        for (int s = N + 1; s <= NMAX; s++) {          // rows beyond the horizon: zeros
+            const int c_ = (s - 1) >> 2;
+            double *gcs = pa.cws + (size_t)b * NCH * 64 + 16 * ((s - 1) & 3) + lc;
+            if (2 * lq <= c_) gcs[cidx(c_, lq) * 64] = 0.0;
+            const int T1 = 4 + lq;
+            if (lane < NB1 && 2 * T1 <= c_) gcs[cidx(c_, T1) * 64] = 0.0;
+        }
+        // input cost (R) and padding on the diagonal, gradient of the input cost
+#pragma unroll
+        for (int K = 0; K < (SH ? 1 : NT); K++)
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) {
+                const int row = lq + 4 * jj;
+                if (row == lc) {
+                    const int idx = 16 * K + row;
+                    Ht[tidx(K, K)][jj] += (idx < nv) ? sWt[(idx >> 1) * 6 + 4 + (idx & 1)] : 1.0;
+                }
+            }
+        // (the inputs' reference: from the copy in LDS where there is one)
+        auto yref_at = [&](const int idx) __attribute__((always_inline)) { if constexpr (PF) return lds[T::YR + idx]; else return gyref[idx]; };
+        if (lane < nv) q0 += sWt[j0 * 6 + 4 + r0] * (sU0[lane] - yref_at(j0 * 6 + 4 + r0));
+        {
+            const int j1 = 32 + j0;
+            if (lane < NB1 && 64 + lane < nv) q1 += sWt[j1 * 6 + 4 + r0] * (sU0[64 + lane] - yref_at(j1 * 6 + 4 + r0));
+        }
+        // ---- hand-over: H tiles, q (the gg rows went out stage by stage)
+        {
+            d4 *gh = reinterpret_cast<d4 *>(pa.hws) + (size_t)b * NTT * 64 + lane;
+#pragma unroll
+            for (int t = 0; t < (SH ? NT : NTT); t++) gh[t * 64] = Ht[t];
+            gvec[PV_Q + lane] = q0;
+            if (lane < NB1) gvec[PV_Q + 64 + lane] = q1;
+        }
     };
     // stage s = k+1 touches columns < 2s, i.e. ceil(s/8) tiles: one instantiation of the stage per segment of 8 stages
     if constexpr (PF) {
         Ahead oa, ob;
         fetch_ahead(1, std::integral_constant<int, 1>(), oa);          // (N >= 1)
-        static_for<1, NT>([&](auto tsc) {
-            constexpr int Ts = decltype(tsc)::value;
-            for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k += 2) {
-                stage_body_pf(k, tsc, std::false_type(), oa, ob, uy[0]);
-                if (k + 1 < N) stage_body_pf(k + 1, tsc, std::true_type(), ob, oa, uy[1]);
+        auto stages = [&](auto shc) __attribute__((always_inline)) {
+            static_for<1, NT>([&](auto tsc) {
+                constexpr int Ts = decltype(tsc)::value;
+                for (int k = 8 * (Ts - 1); k < N && k < 8 * Ts; k += 2) {
+                    stage_body_pf(k, tsc, std::false_type(), shc, oa, ob, uy[0]);
+                    if (k + 1 < N) stage_body_pf(k + 1, tsc, std::true_type(), shc, ob, oa, uy[1]);
+                }
+            });
+        };
+        if (shift) {          // (wave-uniform)
+            // the tiles (j, .) whose accumulator is zero: N - 8 j - 1 < 1 -- with the terminal product of stage 1 where N - 8 j = 1
+            for (int j = (N > 1) ? (N + 6) >> 3 : 1; j < NT; j++) {
+                if (N - 8 * j == 1) emit_shifted(j, std::integral_constant<int, 1>(), 1, oa);
+                else emit_shifted(j, std::integral_constant<int, 0>(), 0, oa);
             }
-        });
+            stages(std::true_type());
+            finish(std::true_type());
+        } else {
+            stages(std::false_type());
+            finish(std::false_type());
+        }
     } else {
         static_for<1, NT>([&](auto tsc) {
             constexpr int Ts = decltype(tsc)::value;
@@ -1270,46 +1389,14 @@ __device__ __forceinline__ void cond_powers_instance(const PArgs &pa, const doub
                 if (k + 1 < N) stage_body(k + 1, tsc, uy[1]);
             }
         });
-    }
-    for (int s = N + 1; s <= NMAX; s++) {          // rows beyond the horizon: zeros
-        const int c_ = (s - 1) >> 2;
-        double *gcs = pa.cws + (size_t)b * NCH * 64 + 16 * ((s - 1) & 3) + lc;
-        if (2 * lq <= c_) gcs[cidx(c_, lq) * 64] = 0.0;
-        const int T1 = 4 + lq;
-        if (lane < NB1 && 2 * T1 <= c_) gcs[cidx(c_, T1) * 64] = 0.0;
-    }
-    // input cost (R) and padding on the diagonal, gradient of the input cost
-#pragma unroll
-    for (int K = 0; K < NT; K++)
-#pragma unroll
-        for (int jj = 0; jj < 4; jj++) {
-            const int row = lq + 4 * jj;
-            if (row == lc) {
-                const int idx = 16 * K + row;
-                Ht[tidx(K, K)][jj] += (idx < nv) ? sWt[(idx >> 1) * 6 + 4 + (idx & 1)] : 1.0;
-            }
-        }
-    // (the inputs' reference: from the copy in LDS where there is one)
-    auto yref_at = [&](const int idx) __attribute__((always_inline)) { if constexpr (PF) return lds[T::YR + idx]; else return gyref[idx]; };
-    if (lane < nv) q0 += sWt[j0 * 6 + 4 + r0] * (sU0[lane] - yref_at(j0 * 6 + 4 + r0));
-    {
-        const int j1 = 32 + j0;
-        if (lane < NB1 && 64 + lane < nv) q1 += sWt[j1 * 6 + 4 + r0] * (sU0[64 + lane] - yref_at(j1 * 6 + 4 + r0));
-    }
-    // ---- hand-over: H tiles, q (the gg rows went out stage by stage)
-    {
-        d4 *gh = reinterpret_cast<d4 *>(pa.hws) + (size_t)b * NTT * 64 + lane;
-#pragma unroll
-        for (int t = 0; t < NTT; t++) gh[t * 64] = Ht[t];
-        gvec[PV_Q + lane] = q0;
-        if (lane < NB1) gvec[PV_Q + 64 + lane] = q1;
+        finish(std::false_type());
     }
 }
 
 template <int NT_>
-__global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_kernel(const PArgs pa, const double *lin1)
+__global__ void __launch_bounds__(64, (NT_ == 5) ? 2 : 1) cond_uniform_kernel(const PArgs pa, const double *lin1, const int use_shift, int *shifted)
 {
-    cond_powers_instance<NT_>(pa, lin1);
+    cond_powers_instance<NT_>(pa, lin1, use_shift, shifted);
 }
 
 // ---- K2 for small batches: six (N <= 40) or seven wavefronts per OCP.

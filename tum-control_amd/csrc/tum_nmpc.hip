@@ -147,6 +147,11 @@ struct tum_ocp {
     // uniform_powers: options_set "uniform_powers", 1 by default -- the record-free condensing forms the sequences A^m B and g_s once per
     // instance (cond_uniform_kernel); 0: every lane carries its column through every stage (cond_uniform_columns_kernel). Same results, to the bit.
     int uniform_powers = 1;
+    // uniform_shift: options_set "uniform_shift", 1 by default -- cond_uniform_kernel<5> forms the Hessian tiles below block row 0 from those of
+    // block row 0 where the cost weights are the same at every stage (pipe_kernels.hpp: the SHIFT form); 0: every tile from its own products.
+    // Same results, to the bit. dshift: one int per instance, 1 where the last cond_uniform_kernel took the form (get_stats "cond_shifted",
+    // summed on the host when asked); shift_counted: the last condensing was that kernel
+    int uniform_shift = 1; int *dshift = nullptr; bool shift_counted = false;
     // tum_ocp_get_condensed_qp: the hand-over buffers hold a condensed QP (a pipeline preparation or solve has run); PV_DV holds the
     // step of that QP (the interior point kernel wrote it for an expansion kernel behind it: its own tail keeps the step in LDS)
     bool qp_handed = false, dv_handed = false;
@@ -294,6 +299,7 @@ extern "C" tum_ocp *tum_ocp_create(const tum_ocp_desc *desc)
     ok &= dalloc(&c->dX, B * (N + 1) * NX) == hipSuccess;
     ok &= dalloc(&c->dU, B * N * NU) == hipSuccess;
     ok &= dalloc(&c->dlin1, B * LIN1) == hipSuccess;
+    ok &= hipMalloc((void **)&c->dshift, sizeof(int) * B) == hipSuccess;
     ok &= hipHostMalloc((void **)&c->hlin_bad, sizeof(int), hipHostMallocDefault) == hipSuccess;
     if (c->hlin_bad) *c->hlin_bad = 0;
     ok &= dalloc(&c->dx0, B * NX) == hipSuccess;
@@ -393,7 +399,7 @@ extern "C" void tum_ocp_free(tum_ocp *c)
     if (c->evi1) (void)hipEventDestroy(c->evi1);
     (void)hipFree(c->dXS); (void)hipFree(c->dxs0); (void)hipFree(c->dApce); (void)hipFree(c->dws2); (void)hipFree(c->dpro); (void)hipFree(c->ddv); (void)hipFree(c->doffs); (void)hipFree(c->dxs_dirty);
     (void)hipFree(c->dr2S); (void)hipFree(c->dr2B); (void)hipFree(c->dpceA); (void)hipFree(c->dbnd_snap);
-    (void)hipFree(c->dsum); (void)hipFree(c->dx0prep); (void)hipFree(c->dlin1);
+    (void)hipFree(c->dsum); (void)hipFree(c->dx0prep); (void)hipFree(c->dlin1); (void)hipFree(c->dshift);
     if (c->hlin_bad) (void)hipHostFree(c->hlin_bad);
     (void)hipFree(c->dnlpres); (void)hipFree(c->dsnap); (void)hipFree(c->dsqpstate); (void)hipFree(c->dsqpiter); (void)hipFree(c->dsnapi); (void)hipFree(c->dactive);
     if (c->hactive) (void)hipHostFree(c->hactive);
@@ -1111,7 +1117,7 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, Part part)
     const long long items = (long long)c->batch * (c->N + 1);
     const dim3 g_cols((unsigned)((items + LC_ITEMS - 1) / LC_ITEMS)), g_lane((unsigned)((items + 63) / 64)), g_ocp(c->batch), wave(64);
     if (part != Part::FEEDBACK) c->lin_ahead = false;
-    if (plan.cond != Cond::NONE) { c->qp_handed = true; c->dv_handed = false; }
+    if (plan.cond != Cond::NONE) { c->qp_handed = true; c->dv_handed = false; c->shift_counted = plan.cond == Cond::ONE_WAVE_UNIFORM && plan.cond_powers; }
     if (plan.ipm != Ipm::NONE) c->dv_handed = plan.ipm != Ipm::FUSED_TAIL;
     if (plan.lin_ahead_flag) pa.ka.flags |= KF_LIN_AHEAD;          // (launch_lin_ahead ran it on another stream; the caller has joined that stream)
     if (plan.lin == Lin::SN_LANE || plan.lin == Lin::SN_COLS) {   // coupled SNMPC OCP: sample fan-out and prologue first, the QP solution goes to the epilogue through the workspace
@@ -1140,7 +1146,7 @@ static int launch_pipeline(tum_ocp *c, bool ipm_events, Part part)
         case Cond::NONE: break;
         case Cond::ONE_WAVE: hipLaunchKernelGGL((cond_kernel<NTv, false>), g_ocp, wave, 0, c->stream, pa); break;
         case Cond::ONE_WAVE_UNIFORM:
-            if (plan.cond_powers) hipLaunchKernelGGL((cond_uniform_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1);
+            if (plan.cond_powers) hipLaunchKernelGGL((cond_uniform_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1, c->uniform_shift, c->dshift);
             else hipLaunchKernelGGL((cond_uniform_columns_kernel<NTv>), g_ocp, wave, 0, c->stream, pa, c->dlin1);
             break;
         case Cond::SN_REGISTER: hipLaunchKernelGGL((cond_kernel<NTv, true, true>), g_ocp, wave, 0, c->stream, pa); break;
@@ -1397,7 +1403,12 @@ extern "C" int tum_ocp_options_set(tum_ocp *c, const char *field, double value)
         c->uniform_powers = (int)value;
         return 0;
     }
-    return fail("options_set: unknown field '" + f + "' (lin_dedup | uniform_records | uniform_powers | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
+    if (f == "uniform_shift") {      // 1: cond_uniform_kernel<5> takes the shift form where an instance's cost weights are the same at every stage (default); 0: never (A/B runs, tests)
+        if (value != 0.0 && value != 1.0) return fail("options_set uniform_shift: 0 or 1");
+        c->uniform_shift = (int)value;
+        return 0;
+    }
+    return fail("options_set: unknown field '" + f + "' (lin_dedup | uniform_records | uniform_powers | uniform_shift | nlp_solver_type | nlp_solver_max_iter | nlp_solver_tol_stat | nlp_solver_tol_eq | "
                 "nlp_solver_tol_ineq | nlp_solver_tol_comp | nlp_solver_step_length | rti_phase), of the SQP globalization (globalization | "
                 "alpha_min | alpha_reduction | merit_weight_eq)");
 }
@@ -1650,6 +1661,18 @@ extern "C" int tum_ocp_get_stats(tum_ocp *c, const char *field, void *out, int b
     }
     if (f == "records_skipped") { *(int *)out = c->n_records_skipped; return 0; }      // solves that ran without stage records (one int)
     if (f == "lin_uniform") { *(int *)out = c->n_lin_uniform; return 0; }      // linearisations that took the uniform path (one int)
+    if (f == "cond_shifted") {      // instances of the last solve whose condensing took the shift form (one int): the kernel's per-instance flags, summed here
+        *(int *)out = 0;
+        if (!c->shift_counted) return 0;
+        DevGuard guard(c->d.device); GUARD_OK(guard);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<int> h((size_t)c->batch);
+        HIPCHK(hipMemcpy(h.data(), c->dshift, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
+        int n = 0;
+        for (int v : h) n += v;
+        *(int *)out = n;
+        return 0;
+    }
     if (chk_range(c, b0, nb)) return 1;
     if (f == "sqp_iter" && !c->solved_sqp) { int *o = (int *)out; for (int i = 0; i < nb; i++) o[i] = 1; return 0; }      // (SQP-RTI: one QP per solve)
     if (f == "residuals" && !c->solved_sqp) return fail("get_stats residuals: computed by a full SQP solve only (options_set nlp_solver_type 1)");

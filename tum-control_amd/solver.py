@@ -406,7 +406,9 @@ class BatchedOcpSolver:
         'rti_phase' 0 | 1 | 2: the following solve() calls are whole SQP-RTI steps (default), preparations or feedbacks;
         'lin_dedup' 1 | 0: linearise a stage-uniform iterate (after cold_start() / reset()) once per instance (default) or per stage;
         'uniform_records' 0 | 1: such a solve writes no stage records where nothing reads them (default), or always fills them;
-        'uniform_powers' 1 | 0: its condensing computes the sequences A^m B once per instance (default) or carries every column through every stage"""
+        'uniform_powers' 1 | 0: its condensing computes the sequences A^m B once per instance (default) or carries every column through every stage;
+        'uniform_shift' 1 | 0: that condensing (N <= 40) forms the Hessian tiles below block row 0 from those of block row 0 where an instance's
+        cost weights are the same at every stage (default), or every tile from its own products; get_stats('cond_shifted') counts the instances"""
         if field == "rti_phase":
             value = _rti_phase_value(value)
         if field == "globalization":
@@ -468,7 +470,9 @@ class BatchedOcpSolver:
             if field == "sqp_iter" and self.batch == 1:
                 return int(out[0])
             return out            # acados returns an array for qp_iter; callers take np.max
-        if field in ("lin_uniform", "records_skipped"):      # linearisations that took the uniform path (options_set('lin_dedup', 0 | 1)); solves without stage records ('uniform_records')
+        # linearisations that took the uniform path (options_set('lin_dedup', 0 | 1)); solves without stage records ('uniform_records');
+        # instances of the last solve whose condensing took the shift form ('uniform_shift')
+        if field in ("lin_uniform", "records_skipped", "cond_shifted"):
             o = ctypes.c_int(0)
             self._chk(self._L.tum_ocp_get_stats(self._h, field.encode(), ctypes.byref(o), 0, 1), "get_stats")
             return o.value
