@@ -346,6 +346,18 @@ int tum_ocp_debug_dump(tum_ocp *c, int b, double *out, int len);
  * Null array pointers are skipped (all null: info only). Refused before the first pipeline preparation / solve, on the development
  * kernel 'fused' (no hand-over buffers) and for an instance range out of bounds. */
 int tum_ocp_get_condensed_qp(tum_ocp *c, int b0, int nb, double *H, double *q, double *C, double *d, double *dv, int *info);
+/* read-only: the linearisation of the coupled SNMPC OCP of the instances b0 .. b0 + nb - 1 as the LAST pipeline solve left it. Launches
+ * nothing, changes nothing.
+ *   info[3]: n_samples, uph, N
+ *   stages k < uph, every sample:  As nb x uph x ns x 64, Bs nb x uph x ns x 16 (column-major, expanded like tum_ocp_get_from_qp_in's),
+ *                                  bs nb x uph x ns x 8 | gg value hs nb x uph x ns and gradient ghs nb x uph x ns x 8 (entries 3, 4, 5, 7;
+ *                                  zeros at stage 0)
+ *   nominal copy, every stage:     hn nb x (N + 1), ghn nb x (N + 1) x 8 (entries 3, 4, 5, 7), cv nb x (N + 1) x 2 ((vl, vt) / |v|)
+ *   nominal copy, stages k >= uph: An nb x (N - uph) x 64, Bn nb x (N - uph) x 16, bn nb x (N - uph) x 8
+ * Null array pointers are skipped (all null: info only). Refused on a capsule that is not the coupled SNMPC one, before the first
+ * pipeline solve, on the development kernel 'fused' and for an instance range out of bounds. */
+int tum_ocp_get_snmpc_linearisation(tum_ocp *c, int b0, int nb, double *As, double *Bs, double *bs, double *hs, double *ghs,
+                                    double *hn, double *ghn, double *cv, double *An, double *Bn, double *bn, int *info);
 
 /* ---- the small kernels either side of the solve ---------------------------------
  * Scenario fan-out of the initial state (Stochastic_NMPC/stochastic_mpc_utils.py:78-91 compute_x0dist as a

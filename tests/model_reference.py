@@ -7,6 +7,8 @@ What is restated, from the formulas the header cites:
   f(x, u)              the single-track / Pacejka right-hand side, pred_model_dynamic_stm_pacejka.py:118-175
   Phi(x, u; dt, nsub)  one shooting interval, classic RK4 with nsub steps of dt / nsub
   h(x)                 the gg circle (a / ax)^2 + (vl r / ay)^2, NMPC_STM_acados_settings.py:70-74, 108-119
+  h_vabs(x)            the same circle with the limits looked up at |v| = sqrt(vl^2 + vt^2) (the coupled SNMPC OCP,
+                       SNMPC_acados_settings.py:60-67, 100-113), gradient w.r.t. (vl, vt, r, a); points of its own (h_vabs_points)
   wrap(yaw)            fmod(yaw, 2 pi) with the binary64 constant 2 pi, plus 2 pi where negative, NMPC_STM_acados_settings.py:41-42
 x = (px, py, psi, vl, vt, r, delta, a), u = (jerk, steering rate). The parameters are those of oracle.edgar_model() and the gg
 table of config, every one taken as the exact binary64 number it is; so are 3.6, 100, 0.001, 0.98, 0.5 and dt.
@@ -18,7 +20,7 @@ once, at the unperturbed point, on the exact quantities, and the perturbed evalu
 "derivative of the taken branch", also where an input sits exactly on a kink.
 
 Not covered here (they have restatements of their own): the sensitivity-free RK4 of sqp_kernels.hpp, the plant of
-loop_kernels.hpp and the SNMPC sample propagation.
+loop_kernels.hpp. (The SNMPC sample propagation is Phi with nsub = 1.)
 """
 import functools
 import math
@@ -155,6 +157,28 @@ def h_fun(P, x, tape):
     return (a / ax) ** 2 + (vl * r / ay) ** 2
 
 
+def h_vabs_fun(P, x, tape):
+    """the gg circle of the coupled SNMPC OCP (SNMPC_acados_settings.py:60-67, 100-113): the limits are looked up at |v| = sqrt(vl^2 + vt^2);
+    ax = -acc_min with zero slope for a < 0. At |v| = 0 the slope term is dropped: the perturbed evaluations keep the limits of |v| = 0."""
+    vl, vt, r, a = x[3], x[4], x[5], x[7]
+    vabs = mp.sqrt(vl * vl + vt * vt)
+    still = tape.take(bool(vabs == 0))
+    if still:
+        vabs = mp.mpf(0)
+    v = P["ggv_v"]
+    ax, _, seg = interp(v, P["ggv_ax"], vabs, tape)
+    ay, _, _ = interp(v, P["ggv_ay"], vabs, tape)
+    if tape.replay is None and not still:
+        for kv in v[1:-1]:
+            tape.computed.append(("|v|", vabs, kv))
+    brake = tape.take(bool(a < 0))
+    if brake:
+        ax = -P["acc_min"]
+    if tape.replay is None:
+        tape.info.append(dict(brake=brake, seg=seg, still=still))
+    return (a / ax) ** 2 + (vl * r / ay) ** 2
+
+
 def wrap(yaw):
     """float64 in, float64 out: fmod is exact in binary64 (math.fmod), the sum with 2 pi rounds once, as the expression does"""
     y = math.fmod(yaw, TWO_PI)
@@ -236,6 +260,52 @@ def eval_h(x, dps=H_DPS, rel="1e-20", raw=False):
         if raw:
             return h, g, t0
         return float(h), _f64(g), t0
+
+
+def eval_h_vabs(x, dps=H_DPS, rel="1e-20", raw=False):
+    """h at |v|, its gradient (8,) (entries vl, vt, r, a; the others are structurally 0), tape"""
+    with mp.workdps(dps):
+        P, z = params(), _mpv(list(x))
+        t0 = Tape()
+        h = h_vabs_fun(P, z, t0)
+        cols = _central(lambda zz, t: [h_vabs_fun(P, zz, t)], z, (3, 4, 5, 7), t0, mp.mpf(rel))
+        g = [mp.mpf(0)] * 8
+        for c, i in enumerate((3, 4, 5, 7)):
+            g[i] = cols[c][0]
+        if raw:
+            return h, g, t0
+        return float(h), _f64(g), t0
+
+
+@functools.lru_cache(maxsize=None)
+def h_vabs_points(seed=515):
+    """X (P, 8), labels: a < 0, a = 0 and a > 0, vt of both signs, every segment of the gg table (11.11 .. 12 is the only one with a slope of ax),
+    |v| below the first and above the last knot, one point at rest. |v| keeps KINK_MARGIN from the knots (the point is moved, never dropped)."""
+    rng = np.random.default_rng(seed)
+    v = ggv_table()[0]
+    X, L = [], []
+    edges = [(v[i], v[i + 1], f"seg{i}") for i in range(len(v) - 1)]
+    edges.append((v[-1], v[-1] + 4.0, "above_last_knot"))
+    for lo, hi, lab in edges:
+        for a, alab in ((-rng.uniform(0.5, 5.0), "a<0"), (0.0, "a=0"), (rng.uniform(0.3, 2.5), "a>0")):
+            for sg in (1.0, -1.0):
+                vabs = rng.uniform(lo + 0.05 * (hi - lo), hi - 0.05 * (hi - lo))
+                th = sg * rng.uniform(0.02, 0.25)
+                x = np.array([rng.normal(0, 50), rng.normal(0, 50), rng.uniform(-7, 7), vabs * math.cos(th), vabs * math.sin(th),
+                              rng.normal(0, 0.1), rng.normal(0, 0.05), a])
+                X.append(x); L.append(f"{lab} {alab} vt{'+' if sg > 0 else '-'}")
+    for a, alab in ((-2.0, "a<0"), (0.0, "a=0"), (1.5, "a>0")):
+        X.append(np.array([1.0, 2.0, 0.3, 0.0, 0.0, 0.05, 0.01, a])); L.append(f"rest {alab}")
+    X = np.array(X)
+    for p in range(len(L)):
+        for attempt in range(8):
+            if kink_margin(eval_h_vabs(X[p])[2]) > KINK_MARGIN:
+                break
+            X[p, 3] *= 1 + 1e-6
+        else:
+            raise AssertionError(f"point {p} ({L[p]}) stays on a knot")
+    X.setflags(write=False)
+    return X, tuple(L)
 
 
 def kink_margin(tape):

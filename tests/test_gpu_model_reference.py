@@ -17,8 +17,9 @@ The cold start of the uniform path cannot choose X_{k+1}: there X_{k+1} = x0, b 
 bound of Phi grows by u (|b| + |Phi|) (1 + 2u) for exactly these two roundings.
 
 The coupled-SNMPC capsule does not serve get_from_qp_in (CoupledSnmpcSolver.get_from_qp_in raises: "not available for the stacked
-state"), so lin_kernel<true> and snmpc_lin_cols_kernel are not driven here; what they inline -- rk4_sens, rk4_sens_col with one RK4
-step -- is held by the probe in (a).
+state"); its linearisation kernels -- snmpc_lin_kernel, snmpc_lin_cols_kernel, lin_kernel<true>, lin_cols_kernel<true> -- are driven in
+the same layout by tests/test_gpu_snmpc_reference.py through CoupledSnmpcSolver.get_snmpc_linearisation, with h at |v| (h_con_vabs)
+against model_reference.eval_h_vabs; what they inline -- rk4_sens, rk4_sens_col with one RK4 step -- is also held by the probe in (a).
 
 h through qp_vec. The condensing kernel writes, for stage s >= 1, d[2 (s - 1) + 1] = h(x_s) + g3 w3 + g5 w5 + g7 w7 with
 (g3, g5, g7) = grad h(x_s) and w = g_s, the constant part of dx_s (g_0 = x0 - X_0, g_{k+1} = A_k g_k + b_k). After a cold start
@@ -37,8 +38,7 @@ qf enters through atan, as an argument), h_con has none (it divides). So the dev
     allowance + n eps_f |entry|,   n = 5 for J, A, B, 1 for f, Phi, 0 for h, grad h,
 structural entries still exact. (Measured before this term existed: everything inside the allowance alone except d psi / d vl of one
 point with nsub = 1, an entry of -2.5e-5 with an error of 11.5 ulp against a floor of 10.) Not covered here (they
-have restatements of their own): the sensitivity-free RK4 of sqp_kernels.hpp, the plant of loop_kernels.hpp, the SNMPC sample
-propagation.
+have restatements of their own): the sensitivity-free RK4 of sqp_kernels.hpp, the plant of loop_kernels.hpp.
 
 Every test prints its largest error / bound ("MRB ..." lines): the GPU half of profiles/model_reference_bounds.txt.
 """

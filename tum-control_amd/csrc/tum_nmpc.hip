@@ -1748,6 +1748,24 @@ extern "C" int tum_ocp_cold_start(tum_ocp *c)
     return 0;
 }
 
+// A_k (column-major 8 x 8), B_k (column-major 8 x 2) and b_k (8) of one compact linearisation record ([0,1] Sp | [2..43] S[6][7] |
+// [44..51] defect: the first 52 doubles of a stage record and of a sample record of the coupled SNMPC OCP alike); null pointers are skipped
+static void expand_record(const double *q, double dt, double *A, double *B, double *b)
+{
+    if (A) {
+        for (int e = 0; e < 64; e++) A[e] = 0.0;
+        for (int d : {0, 1, 2, 6, 7}) A[d * 8 + d] = 1.0;
+        A[2 * 8 + 0] = q[0]; A[2 * 8 + 1] = q[1];
+        for (int ri = 0; ri < 6; ri++) for (int cc = 0; cc < 5; cc++) A[(3 + cc) * 8 + ri] = q[2 + ri * 7 + cc];
+    }
+    if (B) {
+        for (int e = 0; e < 16; e++) B[e] = 0.0;
+        for (int ri = 0; ri < 6; ri++) { B[0 * 8 + ri] = q[2 + ri * 7 + 5]; B[1 * 8 + ri] = q[2 + ri * 7 + 6]; }
+        B[1 * 8 + 6] = dt; B[0 * 8 + 7] = dt;
+    }
+    if (b) for (int ri = 0; ri < 8; ri++) b[ri] = q[44 + ri];
+}
+
 extern "C" int tum_ocp_get_from_qp_in(tum_ocp *c, int stage, const char *field, double *out, int len, int b0, int nb, int stride)
 {
     if (chk_range(c, b0, nb)) return 1;
@@ -1764,19 +1782,9 @@ extern "C" int tum_ocp_get_from_qp_in(tum_ocp *c, int stage, const char *field, 
     if (c->solved_pipe) {   // the pipeline keeps the linearisation as compact stage records (pipe_kernels.hpp): expand on the host
         std::vector<double> r((size_t)nb * PREC);
         if (fetch(c, c->drec, (size_t)(c->N + 1) * PREC, (size_t)stage * PREC, r.data(), PREC, b0, nb, PREC)) return 1;
-        const double dt = c->ka.dt;
         for (int i = 0; i < nb; i++) {
-            const double *q = &r[(size_t)i * PREC];
             double *o = out + (size_t)i * stride;
-            for (int e = 0; e < n; e++) o[e] = 0.0;
-            if (f == "A") {           // column-major 8 x 8
-                for (int d : {0, 1, 2, 6, 7}) o[d * 8 + d] = 1.0;
-                o[2 * 8 + 0] = q[0]; o[2 * 8 + 1] = q[1];
-                for (int ri = 0; ri < 6; ri++) for (int cc = 0; cc < 5; cc++) o[(3 + cc) * 8 + ri] = q[2 + ri * 7 + cc];
-            } else if (f == "B") {    // column-major 8 x 2
-                for (int ri = 0; ri < 6; ri++) { o[0 * 8 + ri] = q[2 + ri * 7 + 5]; o[1 * 8 + ri] = q[2 + ri * 7 + 6]; }
-                o[1 * 8 + 6] = dt; o[0 * 8 + 7] = dt;
-            } else for (int ri = 0; ri < 8; ri++) o[ri] = q[44 + ri];
+            expand_record(&r[(size_t)i * PREC], c->ka.dt, f == "A" ? o : nullptr, f == "B" ? o : nullptr, f == "b" ? o : nullptr);
         }
         return 0;
     }
@@ -2113,6 +2121,67 @@ extern "C" int tum_ocp_get_condensed_qp(tum_ocp *c, int b0, int nb, double *H, d
         }
         return 0;
     });
+}
+
+// The linearisation of the coupled SNMPC OCP of the instances b0 .. b0 + nb - 1 as the LAST pipeline solve left it: the sample records and
+// gg values of the stages below the uncertainty propagation horizon (ws2 / gh: snmpc_lin_kernel or snmpc_lin_cols_kernel), the nominal
+// stage records (lin_kernel<true> or lin_cols_kernel<true>). Launches nothing and writes nothing on the device.
+//   info[0] = n_samples, info[1] = uph, info[2] = N
+//   As nb x uph x ns x 64 | Bs nb x uph x ns x 16 (column-major, expand_record) | bs nb x uph x ns x 8
+//   hs nb x uph x ns | ghs nb x uph x ns x 8: entries 3, 4, 5, 7 (the device writes zeros at stage 0)
+//   hn nb x (N + 1) | ghn nb x (N + 1) x 8: entries 3, 4 (PR_G4), 5, 7 | cv nb x (N + 1) x 2 (PR_CV)
+//   An nb x (N - uph) x 64 | Bn nb x (N - uph) x 16 | bn nb x (N - uph) x 8: the nominal records of the stages uph .. N - 1
+// Any of the array pointers may be null (skipped); with all of them null the call only answers info.
+extern "C" int tum_ocp_get_snmpc_linearisation(tum_ocp *c, int b0, int nb, double *As, double *Bs, double *bs, double *hs, double *ghs,
+                                               double *hn, double *ghn, double *cv, double *An, double *Bn, double *bn, int *info)
+{
+    if (!c) return fail("null capsule");
+    if (!c->sn) return fail("get_snmpc_linearisation: not an SNMPC capsule (tum_ocp_snmpc_attach)");
+#ifdef TUM_DEV_KERNELS
+    if (c->kmode == KMode::FUSED) return fail("get_snmpc_linearisation: the development kernel 'fused' keeps no stage records (use 'auto' or 'pipeline')");
+#endif
+    if (!c->qp_handed || !c->solved_pipe || !c->drec || !c->dws2) return fail("get_snmpc_linearisation: no solve has run on the pipeline yet: there is no linearisation to read");
+    if (b0 < 0 || nb < 0 || (long long)b0 + nb > c->batch) return fail("get_snmpc_linearisation: instance range out of bounds");
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int N = c->N, ns = c->sa.ns, uph = c->sa.uph, nitem = uph * ns, nn = N - uph;
+    if (info) { info[0] = ns; info[1] = uph; info[2] = N; }
+    const double dt = c->ka.dt;
+    std::vector<double> w((size_t)nitem * ABS), g((size_t)nitem * 5), r((size_t)(N + 1) * PREC);
+    for (int i = 0; i < nb; i++) {
+        const size_t b = (size_t)b0 + i;
+        if (nitem > 0 && (As || Bs || bs)) {
+            HIPCHK(hipMemcpy(w.data(), c->sa.ws2 + b * nitem * ABS, sizeof(double) * w.size(), hipMemcpyDeviceToHost));
+            for (int it = 0; it < nitem; it++) {
+                const size_t o = (size_t)i * nitem + it;
+                expand_record(&w[(size_t)it * ABS], dt, As ? As + o * 64 : nullptr, Bs ? Bs + o * 16 : nullptr, bs ? bs + o * 8 : nullptr);
+            }
+        }
+        if (nitem > 0 && (hs || ghs)) {
+            HIPCHK(hipMemcpy(g.data(), c->sa.gh + b * nitem * 5, sizeof(double) * g.size(), hipMemcpyDeviceToHost));
+            for (int it = 0; it < nitem; it++) {
+                const size_t o = (size_t)i * nitem + it;
+                const double *q = &g[(size_t)it * 5];
+                if (hs) hs[o] = q[0];
+                if (ghs) { double *v = ghs + o * 8; for (int e = 0; e < 8; e++) v[e] = 0.0; v[3] = q[1]; v[4] = q[2]; v[5] = q[3]; v[7] = q[4]; }
+            }
+        }
+        if (hn || ghn || cv || An || Bn || bn) {
+            HIPCHK(hipMemcpy(r.data(), c->drec + b * (size_t)(N + 1) * PREC, sizeof(double) * r.size(), hipMemcpyDeviceToHost));
+            for (int k = 0; k <= N; k++) {
+                const double *q = &r[(size_t)k * PREC];
+                const size_t o = (size_t)i * (N + 1) + k;
+                if (hn) hn[o] = q[PR_GH + 3];
+                if (ghn) { double *v = ghn + o * 8; for (int e = 0; e < 8; e++) v[e] = 0.0; v[3] = q[PR_GH]; v[4] = q[PR_G4]; v[5] = q[PR_GH + 1]; v[7] = q[PR_GH + 2]; }
+                if (cv) { cv[o * 2] = q[PR_CV]; cv[o * 2 + 1] = q[PR_CV + 1]; }
+                if (k >= uph && k < N) {
+                    const size_t on = (size_t)i * nn + (k - uph);
+                    expand_record(q, dt, An ? An + on * 64 : nullptr, Bn ? Bn + on * 16 : nullptr, bn ? bn + on * 8 : nullptr);
+                }
+            }
+        }
+    }
+    return 0;
 }
 
 // development aid: one solve with the in-kernel phase timers on; out = batch x 12 cycle counters

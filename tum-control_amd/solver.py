@@ -70,7 +70,7 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_ocp_solve", "tum_ocp_solve_async", "tum_ocp_synchronize", "tum_ocp_options_set",
              "tum_ocp_get_cost", "tum_ocp_get_stats", "tum_ocp_reset", "tum_ocp_get_from_qp_in",
              "tum_ocp_set_stream", "tum_ocp_get_device", "tum_ocp_put_device", "tum_ocp_bind_device", "tum_ocp_results_async", "tum_ocp_results_wait", "tum_ocp_results_outstanding", "tum_ocp_step_async", "tum_ocp_cold_start", "tum_ocp_last_kernel_ms",
-             "tum_ocp_debug_dump", "tum_ocp_get_condensed_qp", "tum_ocp_profile_phases", "tum_ocp_set_schedule", "tum_ocp_set_kernel",
+             "tum_ocp_debug_dump", "tum_ocp_get_condensed_qp", "tum_ocp_get_snmpc_linearisation", "tum_ocp_profile_phases", "tum_ocp_set_schedule", "tum_ocp_set_kernel",
              "tum_ocp_set_x0_fanout", "tum_pce_moments", "tum_pce_attach", "tum_pce_moments_device",
              "tum_ocp_bounds_snapshot", "tum_ocp_bounds_restore", "tum_ocp_r2_backoff", "tum_ocp_r2_attach", "tum_ocp_constraints_get",
              "tum_ocp_snmpc_attach", "tum_ocp_snmpc_samples", "tum_ocp_snmpc_set_offsets",
@@ -143,6 +143,8 @@ def load_library(path=None):
     L.tum_ocp_debug_dump.argtypes = [vp, ci, dp, ci]
     if hasattr(L, "tum_ocp_get_condensed_qp"):
         L.tum_ocp_get_condensed_qp.argtypes = [vp, ci, ci, dp, dp, dp, dp, dp, ctypes.POINTER(ci)]
+    if hasattr(L, "tum_ocp_get_snmpc_linearisation"):
+        L.tum_ocp_get_snmpc_linearisation.argtypes = [vp, ci, ci] + [dp] * 11 + [ctypes.POINTER(ci)]
     L.tum_ocp_profile_phases.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     L.tum_ocp_set_x0_fanout.argtypes = [vp, dp, dp, ci, ci]
     L.tum_pce_moments.argtypes = [vp, cs, ci, dp, ci, ci, dp, dp]
@@ -793,6 +795,24 @@ class CoupledSnmpcSolver(BatchedOcpSolver):
 
     def get_from_qp_in(self, stage, field):
         raise Exception("CoupledSnmpcSolver.get_from_qp_in: not available for the stacked state")
+
+    def get_snmpc_linearisation(self, b0=0, nb=None):
+        """The linearisation of the instances b0 .. b0 + nb - 1 as the last pipeline solve left it (read-only, launches nothing): dict with
+        As (nb, uph, ns, 8, 8), Bs (nb, uph, ns, 8, 2), bs (nb, uph, ns, 8), the gg values hs (nb, uph, ns) and gradients ghs (nb, uph, ns, 8)
+        of the sample copies of the stages below the uncertainty propagation horizon (zeros at stage 0); hn (nb, N + 1), ghn (nb, N + 1, 8) and
+        the speed row's gradient cv (nb, N + 1, 2) of the nominal copy of every stage; An (nb, N - uph, 8, 8), Bn, bn of its stages >= uph."""
+        nb = self.batch - b0 if nb is None else int(nb)
+        info = (ctypes.c_int * 3)()
+        null = ctypes.POINTER(ctypes.c_double)()
+        self._chk(self._L.tum_ocp_get_snmpc_linearisation(self._h, int(b0), nb, *([null] * 11), info), "get_snmpc_linearisation")
+        ns, uph, N = int(info[0]), int(info[1]), int(info[2])
+        shapes = dict(As=(nb, uph, ns, 8, 8), Bs=(nb, uph, ns, 2, 8), bs=(nb, uph, ns, 8), hs=(nb, uph, ns), ghs=(nb, uph, ns, 8),
+                      hn=(nb, N + 1), ghn=(nb, N + 1, 8), cv=(nb, N + 1, 2), An=(nb, N - uph, 8, 8), Bn=(nb, N - uph, 2, 8), bn=(nb, N - uph, 8))
+        out = {k: np.zeros(v) for k, v in shapes.items()}
+        self._chk(self._L.tum_ocp_get_snmpc_linearisation(self._h, int(b0), nb, *[_dp(out[k]) for k in shapes], info), "get_snmpc_linearisation")
+        for k in ("As", "Bs", "An", "Bn"):      # the C-ABI hands matrices out column-major (acados convention)
+            out[k] = np.ascontiguousarray(np.swapaxes(out[k], -1, -2))
+        return out
 
 
 def planner_emulate(track, poses, n_points, Tp, loop_circuit=True, device=0):
