@@ -19,8 +19,9 @@ central differences in the same arithmetic with a step of 1e-20 of the variable'
 once, at the unperturbed point, on the exact quantities, and the perturbed evaluations replay that decision (`Tape`): CasADi's
 "derivative of the taken branch", also where an input sits exactly on a kink.
 
-Not covered here (they have restatements of their own): the sensitivity-free RK4 of sqp_kernels.hpp, the plant of
-loop_kernels.hpp. (The SNMPC sample propagation is Phi with nsub = 1.)
+Not covered here: the sensitivity-free RK4 of sqp_kernels.hpp (it has a restatement of its own). The plant of loop_kernels.hpp
+and its state estimator have their own exact statement, tests/plant_reference.py (tests/test_plant_reference.py,
+tests/test_gpu_plant_reference.py). (The SNMPC sample propagation is Phi with nsub = 1.)
 """
 import functools
 import math

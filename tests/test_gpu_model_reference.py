@@ -37,8 +37,9 @@ alf_vl = qf ivl cf2 with qf = (vt + lf r) ivl (ivl twice, cf2 once); a value (f,
 qf enters through atan, as an argument), h_con has none (it divides). So the device bound of an entry is
     allowance + n eps_f |entry|,   n = 5 for J, A, B, 1 for f, Phi, 0 for h, grad h,
 structural entries still exact. (Measured before this term existed: everything inside the allowance alone except d psi / d vl of one
-point with nsub = 1, an entry of -2.5e-5 with an error of 11.5 ulp against a floor of 10.) Not covered here (they
-have restatements of their own): the sensitivity-free RK4 of sqp_kernels.hpp, the plant of loop_kernels.hpp.
+point with nsub = 1, an entry of -2.5e-5 with an error of 11.5 ulp against a floor of 10.) Not covered here: the
+sensitivity-free RK4 of sqp_kernels.hpp (it has a restatement of its own). The plant of loop_kernels.hpp is held to its own exact
+statement by tests/test_gpu_plant_reference.py (tests/plant_reference.py).
 
 Every test prints its largest error / bound ("MRB ..." lines): the GPU half of profiles/model_reference_bounds.txt.
 """
