@@ -422,6 +422,11 @@ int tum_ocp_constraints_get(tum_ocp *c, int stage, const char *field, double *v,
  * [pos_x,pos_y,ref_yaw,ref_v]; pose: P x 2; ref_out: P x n_points x 4; closest_out (optional): P. All host pointers. */
 int tum_planner_emulate(const double *track, int n_track, const double *pose, int P, int n_points, double Tp,
                         int loop_circuit, double *ref_out, int *closest_out, int device);
+/* The same on a TRACK SET: tracks holds the tables of n_tracks race lines one behind the other ([sum n_t][4]), track_rows the
+ * n_tracks + 1 ascending row offsets (0 first, every track at least 2 rows), track_of[p] in 0..n_tracks-1 the track of pose p (any
+ * order). closest_out and every index behind it are local to the pose's own track; the arithmetic is the single-track call's. */
+int tum_planner_emulate_tracks(const double *tracks, const int *track_rows, int n_tracks, const int *track_of, const double *pose,
+                               int P, int n_points, double Tp, int loop_circuit, double *ref_out, int *closest_out, int device);
 
 /* A batch of closed loops kept in HBM: planner -> solve -> plant step + state estimation
  * (main.py:48-78; Utils/SimulationMode_main_class.py:106-156 sim_step simMode 0 / StateEstimation;
@@ -430,6 +435,14 @@ int tum_planner_emulate(const double *track, int n_track, const double *pose, in
 typedef struct tum_sim tum_sim;
 tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track, double Tp, int loop_circuit, double Ts, int n_elem,
                         const int *windows, int log_capacity);
+/* The same loop on a track set (tum_planner_emulate_tracks: tracks, track_rows, n_tracks), track_of[b] the track of instance b, batch
+ * ints in any order (need not be sorted or contiguous). Every index of an instance -- "closest", a segment's end, a start index of the
+ * environment, the full_lap waypoint n - 2 -- is local to that instance's own track, and the host checks hold it against that track:
+ * an index that exists on a longer track of the set but not on the instance's own is refused before anything is launched. Instance b
+ * computes what it computes in a single-track loop of the same batch on track_of[b], bit for bit. The set is fixed for the life of
+ * the loop (a captured chunk holds its pointers by value). */
+tum_sim *tum_sim_create_tracks(tum_ocp *c, const double *tracks, const int *track_rows, int n_tracks, const int *track_of, double Tp,
+                               int loop_circuit, double Ts, int n_elem, const int *windows, int log_capacity);
 void tum_sim_free(tum_sim *s);
 /* x_sim: batch x 7 plant states, x_mpc: batch x 8 controller states (host); resets the estimator and the step counter */
 int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *x_mpc, int cold_start);
@@ -449,7 +462,8 @@ int tum_sim_advance(tum_sim *s);
  * (tum_sim_get "graph_steps" tells whether the capture succeeded) */
 int tum_sim_run(tum_sim *s, int nsteps);
 int tum_sim_steps(const tum_sim *s);
-/* field: "x_sim" (B*7), "x_mpc" (B*8), "pose" (B*2), "ref0" (B*4), "closest" (B), "graph_steps" (1); logs with the npz schema of
+/* field: "x_sim" (B*7), "x_mpc" (B*8), "pose" (B*2), "ref0" (B*4), "closest" (B), "graph_steps" (1), "track_of" (B: all 0 on one
+ * track), "track_rows" (n_tracks + 1: the row offsets; {0, n_track} on one track); logs with the npz schema of
  * Utils/Logging_Plotting.py:357-372, step-major: "CiLX" ((steps+1)*B*7), "MPC_SimX" ((steps+1)*B*8), "simU" (steps*B*2),
  * "simREF" (steps*B*4), "simSolverDebug" (steps*B*5: cost, 0, sqp_iter, qp_iter, status). len must match. */
 int tum_sim_get(tum_sim *s, const char *field, double *out, long long len);

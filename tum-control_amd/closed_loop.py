@@ -194,9 +194,43 @@ class MovingAverageEstimator:
         return out
 
 
-def start_states(track, idx_start, batch):
+def resolve_tracks(track_name, batch, track_of=None):
+    """(names, tables, track_of) of a loop's tracks: track_name one name of planner.TRACKS -- track_of must be None then and every
+    instance drives on it -- or a sequence of names, instance i on names[track_of[i]] (None: i % T, as RL_WMPC/environment.py:283
+    deals trajectories to environments). An unknown name is a KeyError (load_track), a bad track_of a ValueError."""
+    if isinstance(track_name, str):
+        if track_of is not None:
+            raise ValueError("track_of goes with a sequence of track names")
+        return [track_name], [load_track(track_name)], np.zeros(int(batch), dtype=np.int64)
+    names = [str(n) for n in track_name]
+    if not names:
+        raise ValueError("track_name: a name or a non-empty sequence of names")
+    tables = [load_track(n) for n in names]
+    of = np.arange(int(batch)) % len(names) if track_of is None else np.asarray(track_of)
+    if of.shape != (int(batch),) or not np.issubdtype(of.dtype, np.integer):
+        raise ValueError(f"track_of: one integer track id per instance ({int(batch)})")
+    if ((of < 0) | (of >= len(names))).any():
+        raise ValueError(f"track_of holds ids outside 0..{len(names) - 1}")
+    return names, tables, of.astype(np.int64)
+
+
+def start_states(track, idx_start, batch, track_of=None):
     """X0_MPC (batch, 8) of loops that start on the race line at waypoint idx_start (SimulationMode_main_class.py:60-75 with
-    idx_ref_start): position, yaw in [0, 2 pi), reference speed, everything else 0. idx_start: one index or (batch,) indices."""
+    idx_ref_start): position, yaw in [0, 2 pi), reference speed, everything else 0. idx_start: one index or (batch,) indices.
+    With track_of (batch,): `track` is a sequence of tables and instance b starts at waypoint idx_start[b] of track[track_of[b]]; an
+    index outside that instance's own track is an IndexError, whatever the longer tracks of the set hold."""
+    if track_of is not None:
+        of = np.asarray(track_of)
+        idx = np.broadcast_to(np.asarray(idx_start), (batch,))
+        if of.shape != (batch,) or not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("idx_start: one index or an integer array of length batch; track_of: one track id per instance")
+        x = np.zeros((batch, 8))
+        for b in range(batch):
+            t = track[of[b]]
+            if not -len(t) <= idx[b] < len(t):
+                raise IndexError(f"idx_start[{b}] = {idx[b]} is outside the instance's own track ({len(t)} rows)")
+            x[b, :4] = t[idx[b], 0], t[idx[b], 1], np.mod(t[idx[b], 2], 2 * np.pi), t[idx[b], 3]
+        return x
     idx = np.asarray(idx_start)
     if idx.ndim == 0:
         i = idx_start
@@ -210,18 +244,22 @@ def start_states(track, idx_start, batch):
 
 
 class ClosedLoopBatch:
-    """B independent closed loops on one track, one OCP instance each; `params` (B,7) are per-instance
+    """B independent closed loops, one OCP instance each; `params` (B,7) are per-instance
     [q_xy, q_yaw, q_vel, r_jerk, r_steer, L1, L2] as in update_cost_function_weights (None: YAML defaults x0.01).
-    idx_start: the waypoint all loops start at, or one per instance."""
+    track_name: one track for all instances, or a sequence of names with instance i on track_name[track_of[i]] (None: i % T) -- on the
+    device and on the host path alike; .tracks / .track_of hold what was resolved, .track the one table of a single-track batch.
+    idx_start: the waypoint all loops start at, or one per instance -- a waypoint of the instance's own track."""
 
     def __init__(self, track_name, batch=1, params=None, N=38, Tp=3.04, Ts=0.02, idx_start=0, cfg=None, device=0,
                  on_device=False, log_capacity=0, controller="nominal", disturbances=None, disturbance_steps=0, seed=0,
-                 qp_warm_start=None, qp_tol=None):
+                 qp_warm_start=None, qp_tol=None, track_of=None):
         self.cfg = cfg or _config.default_config()
         kw = {} if qp_tol is None else dict(qp_tol=tuple(qp_tol))          # (termination tolerances of the interior point method; default: the solver's 1e-8)
-        self.track = load_track(track_name)
+        self.track_names, self.tracks, self.track_of = resolve_tracks(track_name, batch, track_of)
+        single = isinstance(track_name, str)
+        self.track = self.tracks[0] if single else None
         self.B, self.N, self.Tp, self.Ts = batch, N, Tp, Ts
-        self.x_mpc = start_states(self.track, idx_start, batch)  # X0_MPC
+        self.x_mpc = start_states(self.track, idx_start, batch) if single else start_states(self.tracks, idx_start, batch, self.track_of)  # X0_MPC
         self.x_sim = self.x_mpc[:, :7].copy()                    # X0_sim
         self.pose = self.x_mpc[:, :2].copy()
         self.controller = controller
@@ -255,7 +293,8 @@ class ClosedLoopBatch:
         # on_device: planner, plant and estimator run as kernels next to the solve (no host round trip per step)
         self.dev = None
         if on_device:
-            self.dev = DeviceClosedLoop(self.solver, self.track, Tp, Ts=Ts, n_elem=4, windows=WINDOWS, log_capacity=log_capacity)
+            set_kw = {} if single else dict(tracks=self.tracks, track_of=self.track_of)
+            self.dev = DeviceClosedLoop(self.solver, self.track, Tp, Ts=Ts, n_elem=4, windows=WINDOWS, log_capacity=log_capacity, **set_kw)
             self.dev.set_state(self.x_sim, self.x_mpc, cold_start=True)
         self.log = dict(CiLX=[self.x_sim.copy()], MPC_SimX=[self.x_mpc.copy()], simU=[], simREF=[], simSolverDebug=[])
         # disturbance realisation (sim_step's simulate_disturbances / simulate_state_estimation): a DisturbanceModel -- `disturbance_steps`
@@ -289,7 +328,7 @@ class ClosedLoopBatch:
         s, B, N = self.solver, self.B, self.N
         yref = np.zeros((B, N + 1, 6)); ref0 = np.zeros((B, 4))
         for b in range(B):
-            _, ref = planner_emulator(self.track, self.pose[b], N + 1, self.Tp, True)
+            _, ref = planner_emulator(self.tracks[self.track_of[b]], self.pose[b], N + 1, self.Tp, True)
             yref[b] = yref_from_ref(ref, N); ref0[b] = ref[0]
         s.set_yref_all(yref if B > 1 else yref[0])
         status = s.solve()
@@ -464,23 +503,77 @@ def segment_objectives(seg, n_candidates, group_sizes):
     return _objectives_from_groups(groups)
 
 
+def curvature_segments(track, name, curv_threshold_lo, curv_threshold_hi, overlap):
+    """BO_WMPC/track_segmentation.py:8-49 curvature_segmentation on one race line (n, 4): the curvature |diff(unwrap(yaw))| / v of
+    every waypoint but the last; a two-threshold switch over it -- on from a sample >= curv_threshold_hi, off from one
+    <= curv_threshold_lo, unchanged in between, off at first (helpers.py:41-50 hysteresis) --; a segment between consecutive switching
+    points, the last one closing on the FIRST again (so it wraps past the end of the line: its end is smaller than its start), widened
+    by `overlap` waypoints on both sides and dropped when shorter than 20. type 0 (curve) where the curvature behind the switching
+    point is above curv_threshold_lo, else 1 (straight). Returns (curves, straights), lists of dicts start, end, type, trajectory."""
+    track = np.asarray(track, dtype=float)
+    curv = np.abs(np.diff(np.unwrap(track[:, 2]))) / track[:-1, 3]
+    on = np.zeros(len(curv), dtype=bool)
+    state = False
+    for i, k in enumerate(curv):
+        if k >= curv_threshold_hi:
+            state = True
+        elif k <= curv_threshold_lo:
+            state = False
+        on[i] = state
+    switch = np.nonzero(on[1:] != on[:-1])[0]
+    groups = ([], [])
+    for j in range(len(switch)):
+        a, b = int(switch[j]), int(switch[(j + 1) % len(switch)])
+        start, end = a - int(overlap), b + int(overlap)
+        if abs(end - start) < 20:
+            continue
+        kind = 0 if curv[a + 1] > curv_threshold_lo else 1
+        groups[kind].append(dict(start=start, end=end, type=kind, trajectory=name))
+    return groups
+
+
+def train_segments(curv_threshold_lo=2e-5, curv_threshold_hi=1e-3, overlap=10, tracks=("modena", "monteblanco")):
+    """BO_WMPC/track_segmentation.py:52-83 get_train_segments: the two segment groups the reference's Bayesian optimisation drives --
+    [curves, straights], each the segments of every track of `tracks` in that order (curvature_segments) -- in the reference's
+    structure, which evaluate_segments takes as it is."""
+    groups = [[], []]
+    for name in tracks:
+        for g, segs in enumerate(curvature_segments(load_track(name), name, curv_threshold_lo, curv_threshold_hi, overlap)):
+            groups[g].extend(segs)
+    return groups
+
+
 def evaluate_segments(track_name, params, segment_groups, max_lat_dev, max_a_comb, max_steps, N=38, Tp=3.04, controller="nominal",
                       check_every=0, **loop_kw):
-    """objective_function (BO_WMPC/objective_function.py:57-175) for P candidate weight sets at once, on one track: params (P, 7) as in
-    update_cost_function_weights, segment_groups a list of groups of (start, end) waypoint index pairs. One device loop of
-    P x (number of segments) instances, candidate-major, every instance started at its segment's start and scored until the planner's
-    index equals its end, it crashes, or max_steps have run. Returns (objectives (P, n_groups, 2), feasible (P,), per-segment dict).
+    """objective_function (BO_WMPC/objective_function.py:57-175) for P candidate weight sets at once: params (P, 7) as in
+    update_cost_function_weights, segment_groups a list of groups of (start, end) waypoint index pairs on the one track track_name, or
+    -- the reference's structure, train_segments() -- of dicts with start, end and trajectory, every segment on its own track
+    (track_name: None, or the sequence of names that fixes the order of the loop's track set; None: first appearance). One device loop
+    of P x (number of segments) instances, candidate-major, then group, then the segments in the order given, every instance started at
+    its segment's start and scored until the planner's index equals its end, it crashes, or max_steps have run. Returns (objectives
+    (P, n_groups, 2), feasible (P,), per-segment dict).
     A candidate with a crashed or timed-out segment is infeasible and all its objectives are NaN. (The reference stops a candidate
     at its first crash; here all its segments run, the returned values are the same.)"""
     params = np.asarray(params, dtype=float).reshape(-1, 7)
     P = len(params)
-    pairs = np.array([p for grp in segment_groups for p in grp], dtype=np.int64).reshape(-1, 2)
+    flat = [p for grp in segment_groups for p in grp]
+    set_kw = {}
+    if flat and isinstance(flat[0], dict):
+        names = list(dict.fromkeys(p["trajectory"] for p in flat)) if track_name is None else \
+            ([track_name] if isinstance(track_name, str) else list(track_name))
+        missing = sorted({p["trajectory"] for p in flat} - set(names))
+        if missing:
+            raise ValueError(f"evaluate_segments: segments on {missing}, which track_name does not list")
+        set_kw = dict(track_of=np.tile([names.index(p["trajectory"]) for p in flat], P))
+        track_name = names
+        flat = [(p["start"], p["end"]) for p in flat]
+    pairs = np.array(flat, dtype=np.int64).reshape(-1, 2)
     sizes = [len(grp) for grp in segment_groups]
     S = len(pairs)
     off = np.concatenate([[0], np.cumsum(sizes)])
     offsets = np.concatenate([c * S + off[:-1] for c in range(P)] + [[P * S]])
     cl = ClosedLoopBatch(track_name, batch=P * S, params=np.repeat(params, S, axis=0), N=N, Tp=Tp, idx_start=np.tile(pairs[:, 0], P),
-                         on_device=True, controller=controller, **loop_kw)
+                         on_device=True, controller=controller, **set_kw, **loop_kw)
     cl.dev.attach_segments(np.tile(pairs[:, 1], P), max_lat_dev, max_a_comb, group_offsets=offsets)
     cl.dev.run_segments(max_steps, check_every)
     objectives, feasible = _objectives_from_groups(cl.dev.segment_groups().reshape(P, len(sizes), 4))
@@ -569,8 +662,35 @@ def rl_env_steps_from_logs(logs, track, actions_per_step, n_mpc_steps, max_lat_d
     return out
 
 
+def restart_lists(restart_indices, n_tracks):
+    """restart_indices of a WeightScheduleEnv as one int64 array per track: one list serves every track, a sequence of n_tracks
+    sequences gives each track its own"""
+    seq = list(restart_indices) if not np.isscalar(restart_indices) else [restart_indices]
+    if seq and all(np.ndim(r) == 1 for r in seq):
+        if len(seq) != int(n_tracks):
+            raise ValueError(f"restart_indices: one list, or one list per track ({int(n_tracks)})")
+        lists = [np.asarray(r, dtype=np.int64) for r in seq]
+    else:
+        lists = [np.atleast_1d(np.asarray(restart_indices, dtype=np.int64))] * int(n_tracks)
+    if any(r.ndim != 1 or len(r) < 1 for r in lists):
+        raise ValueError("restart_indices: every list holds at least one waypoint")
+    return lists
+
+
+def draw_restarts(rng, lists, tracks):
+    """environment.py:195-198 for the instances whose tracks are `tracks`, in that order: one rng.randint per instance into the list
+    of its own track. Where every list has the same length the draws are ONE randint call of that size -- the stream a single list
+    has always consumed -- and each instance indexes its own list with its draw."""
+    tracks = np.asarray(tracks, dtype=np.int64)
+    if len({len(r) for r in lists}) == 1:
+        k = rng.randint(0, len(lists[0]), size=len(tracks))
+    else:
+        k = np.array([rng.randint(0, len(lists[t])) for t in tracks], dtype=np.int64)
+    return np.array([lists[t][i] for t, i in zip(tracks, k)], dtype=np.int64)
+
+
 class WeightScheduleEnv:
-    """n_envs copies of the reference's RLEnvironment (RL_WMPC/environment.py) on one track as ONE batched environment whose state stays
+    """n_envs copies of the reference's RLEnvironment (RL_WMPC/environment.py) as ONE batched environment whose state stays
     on the device: reset() -> (obs, info), step(actions) -> (obs, reward, terminated, truncated, info), arrays over the n_envs axis.
     actions: the (A, 7) parameter table the integer actions index (rows as in update_cost_function_weights; the reference's
     actions_file). info: terminal_observation (the observation of the step itself, also where obs was replaced by a reset's zeros),
@@ -579,22 +699,34 @@ class WeightScheduleEnv:
     restart_indices with numpy.random.RandomState(seed) (environment.py:195-198; one randint per reset instance, in instance order,
     reset() draws n_envs first), and the observation step() returns for it is already the zeros of reset(). auto_reset=False never
     resets: an ended instance drives on and is scored on -- for scoring a run; restart instances with reset(mask) where wanted.
-    One object per track (the reference's trajectories[i % n_trajs] becomes one object each). No gymnasium / stable_baselines3 needed."""
+    track_name: one track, or a sequence of T names with instance i on track_name[i % T] -- the reference's
+    trajectories[i % n_trajs] (environment.py:283; rl_training.py:66 trains 16 environments on monteblanco and modena, 8 each) -- or on
+    track_name[track_of[i]]; ONE object, one rollout buffer and one update over all tracks. restart_indices: one list for all tracks or
+    one list per track (a sequence of T sequences); a reset instance draws from the list of its own track, still one randint per reset
+    instance in instance order (equal lists: the stream of the single list). A full_lap episode ends at the last-but-one waypoint of
+    the instance's own track. No gymnasium / stable_baselines3 needed."""
 
     def __init__(self, track_name, n_envs, actions, n_mpc_steps=20, max_lat_dev=2.0, episode_length=128, rew_sigmas=RL_SIGMAS,
                  rew_lims=RL_LIMS, obs_n_anticipation_points=10, full_lap=False, restart_indices=(0,), auto_reset=True, seed=0,
-                 obs_states="reference", **loop_kw):
+                 obs_states="reference", track_of=None, **loop_kw):
         self.table = np.ascontiguousarray(actions, dtype=float).reshape(-1, 7)
         self.n_envs, self.n_actions, self.n_mpc_steps = int(n_envs), len(self.table), int(n_mpc_steps)
         self.n_observations = 2 + 2 * int(obs_n_anticipation_points)
-        self.restart_indices = np.atleast_1d(np.asarray(restart_indices, dtype=np.int64))
+        n_tracks = 1 if isinstance(track_name, str) else len(track_name)
+        self.track_of = np.zeros(self.n_envs, dtype=np.int64) if isinstance(track_name, str) else \
+            (np.arange(self.n_envs) % n_tracks if track_of is None else np.asarray(track_of, dtype=np.int64))
+        self.restart_lists = restart_lists(restart_indices, n_tracks)
+        self.restart_indices = self.restart_lists[0]          # (the list of the first track: the only one of a single-track environment)
         self.auto_reset = bool(auto_reset)
         self._rng = np.random.RandomState(seed)
         for k in ("on_device", "controller", "batch", "params"):
             if k in loop_kw:
                 raise ValueError(f"WeightScheduleEnv: '{k}' is the environment's to set")
         # (idx_start among loop_kw: where the loops stand until the first reset() -- one waypoint or one per instance)
-        loop_kw.setdefault("idx_start", int(self.restart_indices[0]))
+        loop_kw.setdefault("idx_start", int(self.restart_indices[0]) if n_tracks == 1 else
+                           np.array([self.restart_lists[t][0] for t in self.track_of], dtype=np.int64))
+        if n_tracks > 1:
+            loop_kw["track_of"] = self.track_of
         self.loop = ClosedLoopBatch(track_name, batch=self.n_envs, on_device=True, controller="nominal", **loop_kw)
         self.dev = self.loop.dev
         self.dev.attach_env(self.table, n_mpc_steps, max_lat_dev, episode_length, rew_sigmas, rew_lims, obs_n_anticipation_points,
@@ -607,15 +739,16 @@ class WeightScheduleEnv:
         self._seed, self._t = int(seed), 0
         self._episode_starts = np.ones(self.n_envs)
 
-    def _draw(self, n):
-        return self.restart_indices[self._rng.randint(0, len(self.restart_indices), size=n)]
+    def _draw(self, instances):
+        """start waypoints of the instances listed (with repeats: a start table), one randint each in the order given"""
+        return draw_restarts(self._rng, self.restart_lists, self.track_of[np.asarray(instances, dtype=np.int64)])
 
     def reset(self, mask=None):
         """environment.py:191-237 for every instance (or those of the boolean mask): start waypoints drawn from restart_indices;
         the observation of a reset is all zeros (environment.py:230-233)."""
         m = np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
         start = np.zeros(self.n_envs, dtype=np.int64)
-        start[m] = self._draw(int(m.sum()))
+        start[m] = self._draw(np.nonzero(m)[0])
         self.dev.env_reset(start, m)
         self._ended[m] = False
         self.last_start = start
@@ -628,7 +761,7 @@ class WeightScheduleEnv:
         start = np.zeros(self.n_envs, dtype=np.int64)
         if self.auto_reset:
             mask[self._ended] = 1
-            start[self._ended] = self._draw(int(self._ended.sum()))
+            start[self._ended] = self._draw(np.nonzero(self._ended)[0])
         else:
             mask[self._ended] = 2
         r = self.dev.env_step(actions, mask, start)
@@ -661,7 +794,7 @@ class WeightScheduleEnv:
         if self._policy is not policy:
             self.dev.attach_policy(policy)
             self._policy = policy
-        table = self._draw(E * B).reshape(E, B) if self.auto_reset else None
+        table = self._draw(np.tile(np.arange(B), E)).reshape(E, B) if self.auto_reset else None
         r = self.dev.env_rollout(E, first_obs=self._next_obs, on_end=1 if self.auto_reset else 0, start_table=table,
                                  check_every=1 if stop_when_done else 0)
         live = r["live"]
@@ -708,7 +841,7 @@ class WeightScheduleEnv:
         if not isinstance(policy, PPOTrainer):
             self.dev.attach_policy(policy)
         self._policy = policy
-        table = self._draw(E * B).reshape(E, B)
+        table = self._draw(np.tile(np.arange(B), E)).reshape(E, B)
         r = self.dev.env_collect(E, table, self._seed if seed is None else int(seed), self._t, gamma, gae_lambda,
                                  first_obs=self._next_obs, first_episode_starts=self._episode_starts)
         self._t += E
@@ -1086,8 +1219,9 @@ def learn(env, trainer, n_updates, n_steps, batch_size, n_epochs, gamma, gae_lam
 
 
 def run_policy(track_name, policy, table, starts, max_steps=400, n_mpc_steps=20, check_every=1, n_obs_stack=1, **env_kw):
-    """RL_WMPC/evaluation.py:65-105 run_policy for MANY start waypoints at once: one vehicle per entry of `starts` on `track_name`,
-    full_lap=True and no restarts -- an episode ends at the last-but-one waypoint of the track or when the vehicle leaves it -- with
+    """RL_WMPC/evaluation.py:65-105 run_policy for MANY start waypoints at once: one vehicle per entry of `starts` on `track_name` -- or,
+    with a sequence of names and track_of (one track id per start; None: i % T) among env_kw, each on its own track --,
+    full_lap=True and no restarts -- an episode ends at the last-but-one waypoint of ITS track or when the vehicle leaves it -- with
     `policy` (a WeightPolicy) picking rows of `table` (A, 7) every n_mpc_steps control steps, on the device, until every instance has
     ended or max_steps environment steps have run. env_kw: further arguments of WeightScheduleEnv (N, Tp, max_lat_dev, log_capacity ...;
     by default the five logs of all control steps are kept).

@@ -25,6 +25,7 @@ struct EnvArgs {
     double max_lat_dev, Ts;
     double sig[2], lim[4];                            // reward.py: sigmas; lims[0][lat, vel], lims[1][lat, vel]
     const double *track, *table;                      // [n_track][4], [n_actions][7]
+    const int *track_of, *track_rows;                 // a track set (null: one track): [batch] track of an instance, [n_tracks + 1] first rows in `track`
     const int *in;                                    // [3][batch]: actions, reset mask, start index (one upload per environment step)
     const int *obs_idx;                               // [2][n_samples]: sample indices into ref_v and into the averaged yaw rate
     const double *obs_bounds;                         // [2][2 + 2 n_samples]: lower, upper
@@ -39,6 +40,16 @@ struct EnvArgs {
     double *out;                                      // [b][ENV_REC + 2 + 2 n_samples]
 };
 
+// the table and the length of the track instance b drives on (a.track / a.n_track where the loop holds one track)
+__device__ __forceinline__ const double *env_track(const EnvArgs &a, int b, int &n)
+{
+    n = a.n_track;
+    if (!a.track_of) return a.track;
+    const int t = a.track_of[b], r0 = a.track_rows[t];
+    n = a.track_rows[t + 1] - r0;
+    return a.track + (size_t)4 * r0;
+}
+
 // with_actions = 0: resets only (tum_sim_env_reset)
 __global__ void __launch_bounds__(64) env_begin_kernel(const EnvArgs a, int with_actions)
 {
@@ -47,11 +58,13 @@ __global__ void __launch_bounds__(64) env_begin_kernel(const EnvArgs a, int with
     if (b >= a.batch) return;
     const int N = a.N, B = a.batch;
     const int idx = a.in[2 * B + b];
-    if (a.in[B + b] != 0 && idx >= 0 && idx < a.n_track) {
+    int n_track;
+    const double *track = env_track(a, b, n_track);          // (start indices are local to the instance's own track)
+    if (a.in[B + b] != 0 && idx >= 0 && idx < n_track) {
         // environment.py:191-237: a fresh MPC_Sim at idx_ref_start (SimulationMode_main_class.py:60-75: position, yaw mod 2 pi, reference
         // speed, everything else 0), MPC.reset(X0_MPC) (NMPC_class.py:256-267: x_k = x0, u = 0), a fresh Logger. What tum_sim_set_state
         // and cold_start_kernel do, for this instance only
-        const double *t = a.track + (size_t)4 * idx;
+        const double *t = track + (size_t)4 * idx;
         const double xv[4] = {t[0], t[1], pymod_2pi(t[2]), t[3]};
         for (int i = lane; i < (N + 1) * NX; i += 64) {
             const int q = i & 7;
@@ -127,7 +140,9 @@ __global__ void __launch_bounds__(64) env_score_kernel(const EnvArgs a)
     if (a.status[b] != 0) a.qpf[b] += 1;
     int f = 0;
     if (lat > a.max_lat_dev) f |= ENV_TRUNCATED;
-    if (a.full_lap ? a.closest[b] == a.n_track - 2 : a.ep_steps[b] == a.episode_length) f |= ENV_TERMINATED;
+    int n_track = 0;
+    if (a.full_lap) (void)env_track(a, b, n_track);          // (the last-but-one waypoint of the instance's own track)
+    if (a.full_lap ? a.closest[b] == n_track - 2 : a.ep_steps[b] == a.episode_length) f |= ENV_TERMINATED;
     if (f) a.flags[b] = f;
 }
 

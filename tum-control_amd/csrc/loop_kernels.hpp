@@ -28,14 +28,21 @@ __device__ __forceinline__ double pymod_2pi(double x)
 // first minimum of (px-x)^2+(py-y)^2; walk forward while the accumulated travel time <= Tp; np.linspace / np.interp
 // resampling to npts samples; the yaw channel is interpolated on the unwrapped signal when the segment crosses the
 // 2*pi seam (any step > 250 degrees) and wrapped back into [0, 2*pi).
+// A track set (track_of non-null): track holds the tables of all tracks one behind the other, track_rows[t] .. track_rows[t + 1] - 1 are
+// the rows of track t and instance b drives on track_of[b]. The instance's table and length are selected before anything else: every
+// index below, closest[b] included, is local to that track. Two wave-uniform loads; a single track (track_of null) pays a scalar branch.
 __global__ void __launch_bounds__(64) planner_kernel(const double *track, int n, const double *pose, int pose_stride, int npts, double Tp,
                                                      int loop_circuit, double *out, int out_stride, double *ref0, int *closest,
-                                                     int *err, int batch, int *step_counter)
+                                                     int *err, int batch, int *step_counter, const int *track_of, const int *track_rows)
 {
 #pragma clang fp contract(off)
     __shared__ double sYaw[PLAN_MAXM];
     const int lane = threadIdx.x, b = blockIdx.x;
     if (b >= batch) return;
+    if (track_of) {
+        const int t = track_of[b], r0 = track_rows[t];
+        track += (size_t)4 * r0; n = track_rows[t + 1] - r0;
+    }
     const double x = pose[(size_t)b * pose_stride], y = pose[(size_t)b * pose_stride + 1];
     // ---- closest waypoint (np.argmin: first minimum)
     double best = INFINITY; int bi = 0x7fffffff;

@@ -52,6 +52,11 @@ struct SimCore {
     DevBuf<double> track, xsim, pose, hist, ref0, lCiLX, lSimX, lU, lREF, lDBG;
     DevBuf<int> closest, err, step_counter;
     DevBuf<double> dw, de; int dist_len = 0;          // (tum_sim_set_disturbances)
+    // the track set (tum_sim_create_tracks): `track` holds the tables one behind the other, rows[t] is the first row of track t
+    // (n_tracks + 1 entries), track_of[b] the track of instance b. One track (tum_sim_create): rows = {0, n_track}, track_of all 0 and
+    // NO device copies -- the kernels take their single-track path on the null pointers. n_track is the row count of the whole table.
+    int n_tracks = 1; std::vector<int> rows, track_of; DevBuf<int> d_rows, d_track_of;
+    int rows_of(size_t b) const { const int t = track_of[b]; return rows[t + 1] - rows[t]; }          // length of instance b's own track
 };
 // segment scoring (tum_sim_segments_attach): end index and accumulators per instance, groups of contiguous instances
 struct SimSegments {
@@ -140,8 +145,24 @@ static int env_get(tum_sim *s, const std::string &f, double *out, long long len)
     return fetch_ints(src, B, out);
 }
 
-extern "C" int tum_planner_emulate(const double *track, int n_track, const double *pose, int P, int n_points, double Tp,
-                                   int loop_circuit, double *ref_out, int *closest_out, int device)
+// what a track set must satisfy (tum_sim_create_tracks, tum_planner_emulate_tracks): ascending offsets from 0, at least 2 rows per
+// track, one track id in 0 .. n_tracks - 1 per instance, in any order
+static int track_set_check(const std::string &w, const int *track_rows, int n_tracks, const int *track_of, size_t count)
+{
+    if (!track_rows || !track_of) return fail("null argument");
+    if (n_tracks < 1) return fail(w + ": n_tracks < 1");
+    if (track_rows[0] != 0) return fail(w + ": track_rows must start at 0");
+    for (int t = 0; t < n_tracks; t++)
+        if (track_rows[t + 1] - track_rows[t] < 2)
+            return fail(w + ": track_rows must ascend and every track needs at least 2 rows (track " + std::to_string(t) + ")");
+    for (size_t b = 0; b < count; b++)
+        if (track_of[b] < 0 || track_of[b] >= n_tracks)
+            return fail(w + ": track_of[" + std::to_string(b) + "] = " + std::to_string(track_of[b]) + " is outside 0.." + std::to_string(n_tracks - 1));
+    return 0;
+}
+
+static int planner_emulate(const double *track, int n_track, const int *track_rows, int n_tracks, const int *track_of, const double *pose, int P,
+                           int n_points, double Tp, int loop_circuit, double *ref_out, int *closest_out, int device)
 {
     if (!track || !pose || !ref_out) return fail("null argument");
     if (n_track < 2 || P < 1 || n_points < 2) return fail("planner_emulate: bad sizes");
@@ -149,14 +170,19 @@ extern "C" int tum_planner_emulate(const double *track, int n_track, const doubl
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device: libtumnmpc has no CPU fallback");
     if (device < 0 || device >= ndev) return fail("planner_emulate: device ordinal out of range");
     DevGuard guard(device); GUARD_OK(guard);
-    DevBuf<double> tt, tp, tout; DevBuf<int> tcl, terr;
+    DevBuf<double> tt, tp, tout; DevBuf<int> tcl, terr, tof, trows;
+    if (track_of) {
+        HIPCHK(tof.alloc(P, false)); HIPCHK(trows.alloc((size_t)n_tracks + 1, false));
+        HIPCHK(hipMemcpy(tof.get(), track_of, sizeof(int) * P, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(trows.get(), track_rows, sizeof(int) * ((size_t)n_tracks + 1), hipMemcpyHostToDevice));
+    }
     HIPCHK(tt.alloc((size_t)4 * n_track, false)); HIPCHK(tp.alloc((size_t)2 * P, false));
     HIPCHK(tout.alloc((size_t)4 * P * n_points, false)); HIPCHK(tcl.alloc(P, false)); HIPCHK(terr.alloc(1, false));
     HIPCHK(hipMemset(terr.get(), 0, sizeof(int)));
     HIPCHK(hipMemcpy(tt.get(), track, sizeof(double) * 4 * n_track, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(tp.get(), pose, sizeof(double) * 2 * P, hipMemcpyHostToDevice));
     LAUNCH(planner_kernel, dim3(P), dim3(64), 0, 0, tt.get(), n_track, tp.get(), 2, n_points, Tp, loop_circuit, tout.get(), 4, (double *)nullptr,
-           tcl.get(), terr.get(), P, (int *)nullptr);
+           tcl.get(), terr.get(), P, (int *)nullptr, (const int *)tof.get(), (const int *)trows.get());
     HIPCHK(hipDeviceSynchronize());
     int err = 0;
     HIPCHK(hipMemcpy(&err, terr.get(), sizeof(int), hipMemcpyDeviceToHost));
@@ -164,6 +190,19 @@ extern "C" int tum_planner_emulate(const double *track, int n_track, const doubl
     if (closest_out) HIPCHK(hipMemcpy(closest_out, tcl.get(), sizeof(int) * P, hipMemcpyDeviceToHost));
     if (err) return fail("planner_emulate: extracted segment longer than PLAN_MAXM points");
     return 0;
+}
+extern "C" int tum_planner_emulate(const double *track, int n_track, const double *pose, int P, int n_points, double Tp,
+                                   int loop_circuit, double *ref_out, int *closest_out, int device)
+{
+    return planner_emulate(track, n_track, nullptr, 1, nullptr, pose, P, n_points, Tp, loop_circuit, ref_out, closest_out, device);
+}
+extern "C" int tum_planner_emulate_tracks(const double *tracks, const int *track_rows, int n_tracks, const int *track_of, const double *pose,
+                                          int P, int n_points, double Tp, int loop_circuit, double *ref_out, int *closest_out, int device)
+{
+    if (P < 1) return fail("planner_emulate: bad sizes");
+    if (track_set_check("planner_emulate_tracks", track_rows, n_tracks, track_of, P)) return 1;
+    return planner_emulate(tracks, track_rows[n_tracks], track_rows, n_tracks, track_of, pose, P, n_points, Tp, loop_circuit, ref_out,
+                           closest_out, device);
 }
 
 // (the owners free with the loop: all of it under the capsule's device)
@@ -176,8 +215,9 @@ extern "C" void tum_sim_free(tum_sim *s)
     delete s;
 }
 
-extern "C" tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track, double Tp, int loop_circuit, double Ts, int n_elem,
-                                   const int *windows, int log_capacity)
+// track_of == NULL: one track of n_track rows (tum_sim_create); else the set (checked by the caller), n_track = track_rows[n_tracks]
+static tum_sim *sim_create(tum_ocp *c, const double *track, int n_track, const int *track_rows, int n_tracks, const int *track_of, double Tp,
+                           int loop_circuit, double Ts, int n_elem, const int *windows, int log_capacity)
 {
     if (!c || !track || !windows) { fail("null argument"); return nullptr; }
     if (n_track < 2 || !(Tp > 0) || !(Ts > 0) || n_elem < 1 || log_capacity < 0) { fail("sim_create: bad arguments"); return nullptr; }
@@ -195,6 +235,12 @@ extern "C" tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track,
     for (int i = 0; i < 8; i++) k.win[i] = windows[i];
     const size_t B = c->batch, L = log_capacity;
     bool ok = true;
+    if (track_of) {
+        k.n_tracks = n_tracks; k.rows.assign(track_rows, track_rows + n_tracks + 1); k.track_of.assign(track_of, track_of + B);
+        ok &= k.d_rows.alloc(k.rows.size()) == hipSuccess && k.d_track_of.alloc(B) == hipSuccess;
+        ok = ok && hipMemcpy(k.d_rows.get(), k.rows.data(), sizeof(int) * k.rows.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(k.d_track_of.get(), k.track_of.data(), sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
+    } else { k.rows = {0, n_track}; k.track_of.assign(B, 0); }
     ok &= k.track.alloc((size_t)4 * n_track) == hipSuccess;
     ok &= k.xsim.alloc(B * 7) == hipSuccess && k.pose.alloc(B * 2) == hipSuccess && k.hist.alloc(B * 32) == hipSuccess;
     ok &= k.ref0.alloc(B * 4) == hipSuccess && k.closest.alloc(B) == hipSuccess && k.err.alloc(1) == hipSuccess && k.step_counter.alloc(2) == hipSuccess;
@@ -205,6 +251,18 @@ extern "C" tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track,
     ok = ok && hipMemcpy(k.track.get(), track, sizeof(double) * 4 * n_track, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) { fail("sim_create: device allocation failed"); tum_sim_free(s); return nullptr; }
     return s;
+}
+extern "C" tum_sim *tum_sim_create(tum_ocp *c, const double *track, int n_track, double Tp, int loop_circuit, double Ts, int n_elem,
+                                   const int *windows, int log_capacity)
+{
+    return sim_create(c, track, n_track, nullptr, 1, nullptr, Tp, loop_circuit, Ts, n_elem, windows, log_capacity);
+}
+extern "C" tum_sim *tum_sim_create_tracks(tum_ocp *c, const double *tracks, const int *track_rows, int n_tracks, const int *track_of, double Tp,
+                                          int loop_circuit, double Ts, int n_elem, const int *windows, int log_capacity)
+{
+    if (!c) { fail("null argument"); return nullptr; }
+    if (track_set_check("sim_create_tracks", track_rows, n_tracks, track_of, c->batch)) return nullptr;
+    return sim_create(c, tracks, track_rows[n_tracks], track_rows, n_tracks, track_of, Tp, loop_circuit, Ts, n_elem, windows, log_capacity);
 }
 
 // initial plant state (batch x 7) and controller state (batch x 8): X0_sim / X0_MPC of SimulationMode_main_class.py:60-75
@@ -241,7 +299,8 @@ extern "C" int tum_sim_plan(tum_sim *s)
     if (flush_inputs(c)) return 1;
     invalidate(c, CH_REF);
     LAUNCH(planner_kernel, dim3(c->batch), dim3(64), 0, c->stream, k.track.get(), k.n_track, k.pose.get(), 2, c->N + 1, k.Tp,
-           k.loop_circuit, c->dyref, 6, k.ref0.get(), k.closest.get(), k.err.get(), c->batch, (int *)nullptr);
+           k.loop_circuit, c->dyref, 6, k.ref0.get(), k.closest.get(), k.err.get(), c->batch, (int *)nullptr,
+           (const int *)k.d_track_of.get(), (const int *)k.d_rows.get());
     return 0;
 }
 
@@ -413,6 +472,13 @@ extern "C" int tum_sim_segments_attach(tum_sim *s, const int *end_idx, const int
     if (end_idx && s->env.on) return fail("segments_attach: this loop is an RL environment (tum_sim_env_attach): an instance is scored by one set of rules; detach the environment first");
     if (end_idx) {
         if (max_lat_dev != max_lat_dev || max_a_comb != max_a_comb) return fail("segments_attach: a threshold is NaN (an infinite one disables its crash test)");
+        // on a track set an end index is a waypoint of the instance's OWN track: one past it (valid on a longer track of the set, say)
+        // could never be reached. A single-track loop keeps taking any index, as it always has (one it cannot reach: never done)
+        if (s->core.d_track_of.get())
+            for (int b = 0; b < B; b++)
+                if (end_idx[b] >= s->core.rows_of(b))
+                    return fail("segments_attach: end index " + std::to_string(end_idx[b]) + " of instance " + std::to_string(b) + " is outside its own track (track " +
+                                std::to_string(s->core.track_of[b]) + ", " + std::to_string(s->core.rows_of(b)) + " rows)");
         if (group_offsets) {
             if (n_groups < 1) return fail("segments_attach: n_groups < 1");
             if (group_offsets[0] != 0 || group_offsets[n_groups] != B) return fail("segments_attach: group_offsets must start at 0 and end at batch");
@@ -517,6 +583,16 @@ extern "C" int tum_sim_get(tum_sim *s, const char *field, double *out, long long
         return 0;
     }
     if (f == "closest") return len != B ? fail("sim_get closest: len != batch") : fetch_ints(k.closest.get(), B, out);
+    if (f == "track_of") {          // the track of every instance (all 0 on a single-track loop)
+        if (len != B) return fail("sim_get track_of: len != batch");
+        for (long long i = 0; i < B; i++) out[i] = k.track_of[i];
+        return 0;
+    }
+    if (f == "track_rows") {        // first row of every track in the concatenated table, then the total: n_tracks + 1 values
+        if (len != k.n_tracks + 1) return fail("sim_get track_rows: len != n_tracks + 1");
+        for (long long i = 0; i <= k.n_tracks; i++) out[i] = k.rows[i];
+        return 0;
+    }
     const struct { const char *name; const double *src; long long want; } arrays[] = {
         {"x_sim", k.xsim.get(), B * 7}, {"x_mpc", c->dx0, B * 8}, {"pose", k.pose.get(), B * 2}, {"ref0", k.ref0.get(), B * 4},
         {"CiLX", k.lCiLX.get(), (L + 1) * B * 7}, {"MPC_SimX", k.lSimX.get(), (L + 1) * B * 8}, {"simU", k.lU.get(), L * B * 2},

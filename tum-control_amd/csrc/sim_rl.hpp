@@ -80,7 +80,7 @@ extern "C" int tum_sim_env_attach(tum_sim *s, const double *table, int n_actions
     a.max_lat_dev = max_lat_dev; a.Ts = k.Ts;
     for (int i = 0; i < 2; i++) a.sig[i] = sigmas[i];
     for (int i = 0; i < 4; i++) a.lim[i] = lims[i];
-    a.track = k.track.get(); a.table = v.table.get(); a.in = v.in.get(); a.obs_idx = v.idx.get(); a.obs_bounds = v.bounds.get();
+    a.track = k.track.get(); a.track_of = k.d_track_of.get(); a.track_rows = k.d_rows.get(); a.table = v.table.get(); a.in = v.in.get(); a.obs_idx = v.idx.get(); a.obs_bounds = v.bounds.get();
     a.x_sim = k.xsim.get(); a.pose = k.pose.get(); a.hist = k.hist.get(); a.ref0 = k.ref0.get(); a.closest = k.closest.get();
     a.step_counter = k.step_counter.get(); a.err = k.err.get(); a.lCiLX = k.lCiLX.get(); a.lSimX = k.lSimX.get();
     a.ep_steps = v.ep.get(); a.count = v.count.get(); a.flags = v.flags.get(); a.qpf = v.qpf.get(); a.samples = v.samples.get();
@@ -114,6 +114,13 @@ static int env_enqueue_step(tum_sim *s, unsigned changed)
     return 0;
 }
 
+// on a track set an index is held against the instance's own track: the tail of a refusal that says which one that is
+static std::string env_own_track(const tum_sim *s, size_t b)
+{
+    const SimCore &k = s->core;
+    if (!k.d_track_of.get()) return "";
+    return " it drives on (track " + std::to_string(k.track_of[b]) + " of the set, " + std::to_string(k.rows_of(b)) + " rows)";
+}
 // checks and uploads actions | reset mask | start indices (any may be null: none) of a host-driven step or reset; *changed: what the
 // begin kernel behind it will write. The caller holds the device guard.
 static int env_stage(tum_sim *s, const int *actions, const int *reset_mask, const int *start_idx, const char *who, unsigned *changed)
@@ -124,7 +131,7 @@ static int env_stage(tum_sim *s, const int *actions, const int *reset_mask, cons
     for (int b = 0; b < B; b++) {
         const bool r = reset_mask && reset_mask[b] == 1, go_on = reset_mask && reset_mask[b] == 2;
         if (reset_mask && !r && !go_on && reset_mask[b] != 0) return fail(w + ": a reset mask holds 0 (nothing), 1 (reset) or 2 (an ended episode drives on)");
-        if (r && (!start_idx || start_idx[b] < 0 || start_idx[b] >= s->core.n_track)) return fail(w + ": start index of instance " + std::to_string(b) + " is outside the track");
+        if (r && (!start_idx || start_idx[b] < 0 || start_idx[b] >= s->core.rows_of(b))) return fail(w + ": start index of instance " + std::to_string(b) + " is outside the track" + env_own_track(s, b));
         if (actions && (actions[b] < 0 || actions[b] >= v.a.n_actions))
             return fail(w + ": action " + std::to_string(actions[b]) + " of instance " + std::to_string(b) + " is outside the table of " + std::to_string(v.a.n_actions) + " rows");
         if (actions && v.ended[b] && !r && !go_on) return fail(w + ": the episode of instance " + std::to_string(b) + " has ended and it is not marked for reset");
@@ -306,8 +313,8 @@ static int env_check_start_table(const tum_sim *s, const char *who, const int *s
 {
     const size_t B = s->c->batch;
     for (size_t i = 0; i < E * B; i++)
-        if (start_table[i] < 0 || start_table[i] >= s->core.n_track)
-            return fail(std::string(who) + ": start index of instance " + std::to_string(i % B) + " at step " + std::to_string(i / B) + " is outside the track");
+        if (start_table[i] < 0 || start_table[i] >= s->core.rows_of(i % B))
+            return fail(std::string(who) + ": start index of instance " + std::to_string(i % B) + " at step " + std::to_string(i / B) + " is outside the track" + env_own_track(s, i % B));
     return 0;
 }
 // step 0, what the host knows: an instance whose episode has ended is reset to start_table[0][b] (reset_ended) and the policy sees zeros

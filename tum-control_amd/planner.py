@@ -61,6 +61,18 @@ def planner_emulator(track, pose_xy, n_points, Tp, loop_circuit=True):
     return i0, out
 
 
+def planner_emulator_tracks(table, track_rows, track_of, poses, n_points, Tp, loop_circuit=True):
+    """planner_emulator over a track set as the device holds it (solver.track_set): `table` the race lines one behind the other,
+    track_rows their n_tracks + 1 row offsets, pose p on track track_of[p]. The rows of the pose's own track are cut out before
+    anything else, so the index returned, the walk past the last waypoint and the resampling are local to that track.
+    Returns (closest_index (P,), ref (P, n_points, 4))."""
+    poses = np.atleast_2d(np.asarray(poses, dtype=float))
+    idx = np.empty(len(poses), dtype=np.int64); ref = np.empty((len(poses), n_points, 4))
+    for p, t in enumerate(np.asarray(track_of)):
+        idx[p], ref[p] = planner_emulator(table[track_rows[t]:track_rows[t + 1]], poses[p], n_points, Tp, loop_circuit)
+    return idx, ref
+
+
 def yref_from_ref(ref, N):
     """(N+1, 6) yref block for the solver: [x, y, yaw, v, 0, 0] (NMPC_class.py:169-180)."""
     y = np.zeros((N + 1, 6))

@@ -74,7 +74,7 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_ocp_set_x0_fanout", "tum_pce_moments", "tum_pce_attach", "tum_pce_moments_device",
              "tum_ocp_bounds_snapshot", "tum_ocp_bounds_restore", "tum_ocp_r2_backoff", "tum_ocp_r2_attach", "tum_ocp_constraints_get",
              "tum_ocp_snmpc_attach", "tum_ocp_snmpc_samples", "tum_ocp_snmpc_set_offsets",
-             "tum_planner_emulate", "tum_sim_create", "tum_sim_free", "tum_sim_set_state", "tum_sim_plan", "tum_sim_advance",
+             "tum_planner_emulate", "tum_planner_emulate_tracks", "tum_sim_create", "tum_sim_create_tracks", "tum_sim_free", "tum_sim_set_state", "tum_sim_plan", "tum_sim_advance",
              "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
              "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step",
              "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout",
@@ -160,6 +160,9 @@ def load_library(path=None):
     ip = ctypes.POINTER(ctypes.c_int); cd = ctypes.c_double
     L.tum_planner_emulate.argtypes = [dp, ci, dp, ci, ci, cd, ci, dp, ip, ci]
     L.tum_sim_create.restype = vp; L.tum_sim_create.argtypes = [vp, dp, ci, cd, ci, cd, ci, ip, ci]
+    if hasattr(L, "tum_sim_create_tracks"):
+        L.tum_planner_emulate_tracks.argtypes = [dp, ip, ci, ip, dp, ci, ci, cd, ci, dp, ip, ci]
+        L.tum_sim_create_tracks.restype = vp; L.tum_sim_create_tracks.argtypes = [vp, dp, ip, ci, ip, cd, ci, cd, ci, ip, ci]
     L.tum_sim_free.restype = None; L.tum_sim_free.argtypes = [vp]
     L.tum_sim_set_state.argtypes = [vp, dp, dp, ci]
     L.tum_sim_plan.argtypes = [vp]; L.tum_sim_advance.argtypes = [vp]; L.tum_sim_run.argtypes = [vp, ci]
@@ -831,16 +834,80 @@ def planner_emulate(track, poses, n_points, Tp, loop_circuit=True, device=0):
     return idx, ref
 
 
+def track_set(tracks, track_of, count, track_rows=None):
+    """A track set as the C-ABI takes it (tum_sim_create_tracks, tum_planner_emulate_tracks), checked on the host: `tracks` a sequence
+    of (n_t, 4) tables -- or, with track_rows, ONE table of all of them one behind the other and its n_tracks + 1 ascending row offsets
+    (0 first, at least 2 rows per track); track_of: `count` track ids in 0 .. n_tracks - 1 in any order (None: i % n_tracks).
+    Returns (table (sum n_t, 4) float64, track_rows (n_tracks + 1,) int32, track_of (count,) int32)."""
+    if track_rows is None:
+        tabs = [np.asarray(t, dtype=np.float64) for t in tracks]
+        if not tabs or any(t.ndim != 2 or t.shape[1] != 4 for t in tabs):
+            raise ValueError("track_set: tracks is a non-empty sequence of (n, 4) tables")
+        table = np.ascontiguousarray(np.concatenate(tabs))
+        rows = np.concatenate([[0], np.cumsum([len(t) for t in tabs])])
+    else:
+        table = np.ascontiguousarray(tracks, dtype=np.float64)
+        rows = np.asarray(track_rows)
+        if table.ndim != 2 or table.shape[1] != 4:
+            raise ValueError("track_set: with track_rows, tracks is one (sum n_t, 4) table")
+        if rows.ndim != 1 or len(rows) < 2 or not np.issubdtype(rows.dtype, np.integer) or rows[0] != 0 or rows[-1] != len(table):
+            raise ValueError("track_set: track_rows is n_tracks + 1 integer offsets from 0 to the length of the table")
+    if (np.diff(rows) < 2).any():
+        raise ValueError("track_set: track_rows must ascend and every track needs at least 2 rows")
+    T = len(rows) - 1
+    if track_of is None:
+        track_of = np.arange(int(count)) % T
+    of = np.asarray(track_of)
+    if of.shape != (int(count),) or not np.issubdtype(of.dtype, np.integer):
+        raise ValueError(f"track_set: track_of is one integer track id per instance ({int(count)})")
+    if ((of < 0) | (of >= T)).any():
+        raise ValueError(f"track_set: track_of holds ids outside 0..{T - 1}")
+    return table, np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(of, dtype=np.int32)
+
+
+def planner_emulate_tracks(tracks, track_of, poses, n_points, Tp, loop_circuit=True, device=0, track_rows=None):
+    """planner_emulate on a track set (track_set): pose p is planned on tracks[track_of[p]], its index is local to that track.
+    Returns (closest_index (P,), ref (P, n_points, 4))."""
+    L = load_library()
+    poses = np.ascontiguousarray(np.atleast_2d(poses), dtype=np.float64)
+    if poses.shape[1] != 2:
+        raise Exception("planner_emulate_tracks: poses (P,2)")
+    P = poses.shape[0]
+    table, rows, of = track_set(tracks, track_of, P, track_rows)
+    ref = np.empty((P, n_points, 4)); idx = np.empty(P, dtype=np.int32)
+    ip = ctypes.POINTER(ctypes.c_int)
+    rc = L.tum_planner_emulate_tracks(_dp(table), rows.ctypes.data_as(ip), len(rows) - 1, of.ctypes.data_as(ip), _dp(poses), P, int(n_points),
+                                      float(Tp), int(bool(loop_circuit)), _dp(ref), idx.ctypes.data_as(ip), int(device))
+    if rc != 0:
+        raise Exception("planner_emulate_tracks: " + L.tum_ocp_last_error().decode())
+    return idx, ref
+
+
 class DeviceClosedLoop:
     """Closed loops of every instance of a solver kept on the GPU: planner -> SQP-RTI -> plant + estimator
-    (main.py:48-78, SimulationMode_main_class.py:106-156). The logs use the reference's npz field names."""
+    (main.py:48-78, SimulationMode_main_class.py:106-156). The logs use the reference's npz field names.
+    One race line `track` (n, 4) for all instances, or (track=None) a track set: tracks, a sequence of (n_t, 4) tables, and track_of,
+    the track of every instance (None: i % n_tracks) -- every index of an instance is then local to its own track (track_set)."""
 
-    def __init__(self, solver, track, Tp, Ts=0.02, n_elem=4, windows=(1, 1, 4, 2, 2, 3, 4, 2), loop_circuit=True, log_capacity=0):
+    def __init__(self, solver, track, Tp, Ts=0.02, n_elem=4, windows=(1, 1, 4, 2, 2, 3, 4, 2), loop_circuit=True, log_capacity=0,
+                 tracks=None, track_of=None):
         self.solver, self._L = solver, solver._L
-        track = np.ascontiguousarray(track, dtype=np.float64)
         win = (ctypes.c_int * 8)(*[int(w) for w in windows])
-        self._s = self._L.tum_sim_create(solver._h, _dp(track), track.shape[0], float(Tp), int(bool(loop_circuit)), float(Ts),
-                                         int(n_elem), win, int(log_capacity))
+        if tracks is None:
+            if track_of is not None:
+                raise ValueError("DeviceClosedLoop: track_of goes with tracks=[...]")
+            track = np.ascontiguousarray(track, dtype=np.float64)
+            self.track_rows, self.track_of = np.array([0, track.shape[0]]), np.zeros(solver.batch, dtype=np.int64)
+            self._s = self._L.tum_sim_create(solver._h, _dp(track), track.shape[0], float(Tp), int(bool(loop_circuit)), float(Ts),
+                                             int(n_elem), win, int(log_capacity))
+        else:
+            if track is not None:
+                raise ValueError("DeviceClosedLoop: one track or tracks=[...], not both")
+            table, rows, of = track_set(tracks, track_of, solver.batch)
+            ip = ctypes.POINTER(ctypes.c_int)
+            self.track_rows, self.track_of = rows.astype(np.int64), of.astype(np.int64)
+            self._s = self._L.tum_sim_create_tracks(solver._h, _dp(table), rows.ctypes.data_as(ip), len(rows) - 1, of.ctypes.data_as(ip), float(Tp),
+                                                    int(bool(loop_circuit)), float(Ts), int(n_elem), win, int(log_capacity))
         if not self._s:
             raise Exception("tum_sim_create: " + self._L.tum_ocp_last_error().decode())
         self.B = solver.batch
@@ -888,6 +955,10 @@ class DeviceClosedLoop:
     _DIMS = dict(x_sim=7, x_mpc=8, pose=2, ref0=4, closest=1, CiLX=7, MPC_SimX=8, simU=2, simREF=4, simSolverDebug=5)
 
     def get(self, field):
+        if field in ("track_of", "track_rows"):          # the loop's track set as the library holds it (one track: zeros, [0, n])
+            out = np.empty(self.B if field == "track_of" else len(self.track_rows))
+            self._chk(self._L.tum_sim_get(self._s, field.encode(), _dp(out), out.size), "sim_get " + field)
+            return out.astype(np.int64)
         d = self._DIMS[field]
         if field in ("x_sim", "x_mpc", "pose", "ref0", "closest"):
             shape = (self.B, d)
