@@ -453,6 +453,39 @@ int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *x_mpc, int 
  * disturbed state before the estimator. n_steps x batch x 7 doubles each (host, step-major), either may be null; control steps beyond
  * n_steps run undisturbed; n_steps = 0 removes the realisation. tum_sim_set_state restarts the playback. */
 int tum_sim_set_disturbances(tum_sim *s, const double *w_deriv, const double *e_est, int n_steps);
+/* ---- Disturbance draws: the same realisation DRAWN on the device, one launch per control step in front of the plant, instead of
+ * played back from a table. The distributions are the reference's (Utils/MPC_sim_utils.py:54-86); the random stream is this
+ * project's own. A draw depends on (seed, instance b, global control step t, stream s, kind, bounds) alone -- not on the batch, the
+ * window, the launch shape or the path that asks for it -- so every realisation can be regenerated after the fact without being stored.
+ *
+ * Key and counter. Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32). Block j of stream s (s = 0: derivative disturbance,
+ * s = 1: state estimation error) for instance b at step t has the counter (b, t & 0xffffffff, t >> 32, 0x100 * (1 + s) + j). The last
+ * word is never 0: these draws never meet the policy's (last word 0) under the same seed.
+ * Uniforms from a block. Its four words x0..x3 give uA = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 and uB likewise from (x2, x3): both in
+ * [0, 1), integer work plus an exact conversion.
+ * Normals. Block j = 0..3 gives z[2j] = R cos(theta) and z[2j+1] = R sin(theta) with R = sqrt(-2 ln(1 - uA)), theta = 2 pi uB;
+ * 1 - uA is exact and lies in (0, 1], so the logarithm never sees 0. Channel i = 0..6 uses z[i]; z[7] is unused.
+ * Kinds, with the bounds w[i] >= 0 (the seven magnitudes of the stream):
+ *   1 'uniform'   the reference's ellipsoid with shape matrix diag(w): sqrt(w[i]) * r * z[i] / |z|, |z| the 2-norm of z[0..6] summed
+ *                 in index order, r = uA(block 4) ** (1/7); a zero norm gives zeros
+ *   2 'gaussian'  w[i] * z[i]
+ *   3 'absolute'  w[i]
+ *   4 the box     -w[i] + u_i * (2 w[i]), u_i = uA (i even) or uB (i odd) of block i >> 1
+ * All kinds: fp contract(off), sums in index order. 'absolute' and the box are exact statements (device and host agree to the bit);
+ * the two normal kinds go through log, sqrt, sin, cos and a power, whose last bits are the math library's.
+ * Difference from the reference: it draws from numpy's legacy Mersenne-Twister stream (one rand(), then randn()s), which no counter
+ * reproduces; closed_loop.DisturbanceModel.draw keeps doing that on the host for playback.
+ *
+ * kind_w / kind_e: 0 switches a stream off, 1..4 as above; both 0 detaches. bound_w / bound_e: 7 doubles each (may be null for a stream
+ * that is off), negative or non-finite ones are refused. Attaching waits for the loop's stream, drops the captured chunk of the run
+ * function (it holds the extra launch, or lacks it) and removes a played-back table; the table setter above, given a table, removes
+ * the generator. The draws are indexed by the loop's GLOBAL control step, as playback is: the state function restarts them at step 0
+ * with the counter, an environment reset or a per-instance restart does not touch them. */
+int tum_sim_disturbances_attach(tum_sim *s, int kind_w, const double *bound_w, int kind_e, const double *bound_e, unsigned long long seed);
+/* The realisation of the control steps first_step .. first_step + n_steps - 1 as the attached generator draws it (the same device
+ * function as the live draw: equal to the bit), n_steps x batch x 7 doubles per stream (host, step-major). Either output may be null;
+ * a stream that is off gives zeros. Read-only for the loop: step counter, slab and captured chunk are untouched. */
+int tum_sim_disturbances_table(tum_sim *s, long long first_step, int n_steps, double *w_out, double *e_out);
 int tum_sim_plan(tum_sim *s);        /* yref of every instance from its pose (async on the capsule's stream) */
 /* plant step with (x1[7], u0[1]) of the iterate, estimator -> next x0 (async). An instance whose solve FAILED (status != 0)
  * is then treated as main.py:59-61 treats it (MPC.reintialize_solver(x_next)): its iterate is cold-started at the state the

@@ -130,6 +130,69 @@ class DisturbanceModel:
                     e[i, b] = generate_disturbances(self.bounds_state_estimation, self.types[1], rng)
         return w, e
 
+    def draw_counter(self, n_steps, batch=1, seed=0, first_step=0, first_instance=0):
+        """(w_deriv, e_est) like `draw`, from the project's COUNTER-BASED stream (include/tum_nmpc.h, "Disturbance draws"): row
+        [i, k] is the realisation of instance first_instance + k at global control step first_step + i, and depends on (seed,
+        instance, step, stream, kind, bounds) alone -- any window and any batch that contain a row return the same bits for it.
+        The host statement of what disturbance_draw_kernel draws on the device (DeviceClosedLoop.attach_disturbances): the box
+        and 'absolute' kinds agree with it to the bit, the two normal kinds to the math library's last bits. Vectorised over steps
+        and vehicles (windows of more than 2^16 rows are drawn in slabs of steps, to bound the memory of the Philox words). NOT
+        numpy's Mersenne-Twister stream of `draw`: the distributions are the same, the numbers are not."""
+        n_steps, batch, first_step = int(n_steps), int(batch), int(first_step)
+        seed = int(seed) & (2 ** 64 - 1)
+        key = np.array([seed & 0xffffffff, seed >> 32], dtype=np.uint64)
+        b = ((int(first_instance) + np.arange(batch)) & 0xffffffff).astype(np.uint64)
+        out = []
+        for s, (on, kind, bounds) in enumerate(((self.derivatives, self.types[0], self.bounds_derivatives),
+                                                (self.state_estimation, self.types[1], self.bounds_state_estimation))):
+            if not on:
+                out.append(None)
+                continue
+            w = np.asarray(bounds, dtype=float)[:, 1]
+            res = np.zeros((n_steps, batch, 7))
+            slab = max(1, (1 << 16) // max(batch, 1))
+            for i0 in range(0, n_steps, slab):
+                t = np.uint64(first_step + i0) + np.arange(min(slab, n_steps - i0), dtype=np.uint64)
+                ctr = np.zeros((len(t), batch, DISTURBANCE_BLOCKS, 4), dtype=np.uint64)
+                ctr[..., 0] = b[None, :, None]
+                ctr[..., 1] = (t & np.uint64(0xffffffff))[:, None, None]
+                ctr[..., 2] = (t >> np.uint64(32))[:, None, None]
+                ctr[..., 3] = np.uint64(0x100 * (1 + s)) + np.arange(DISTURBANCE_BLOCKS, dtype=np.uint64)
+                x = philox4x32(ctr, key)
+                res[i0:i0 + len(t)] = disturbance_from_uniforms(kind, w, uniform_from_words(x[..., 0], x[..., 1]),
+                                                                uniform_from_words(x[..., 2], x[..., 3]))
+            out.append(res)
+        return out[0], out[1]
+
+
+DISTURBANCE_BLOCKS = 5          # Philox blocks of one draw: four of normals / box uniforms, one for the ellipsoid's radius
+
+
+def disturbance_from_uniforms(kind, w, uA, uB):
+    """One draw per leading index from the uniforms of its Philox blocks: uA, uB (..., 5) in [0, 1), w (7,) bounds >= 0 -> (..., 7).
+    The statement of include/tum_nmpc.h in plain binary64 numpy, in the device function's order of operations (products and sums
+    rounded one by one, the norm summed in index order)."""
+    w = np.asarray(w, dtype=float)
+    uA, uB = np.asarray(uA, dtype=float), np.asarray(uB, dtype=float)
+    lead = uA.shape[:-1]
+    if kind == 'absolute':
+        return np.broadcast_to(w, lead + (7,)).copy()
+    if kind in ('uniform', 'gaussian'):
+        R = np.sqrt(-2.0 * np.log(1.0 - uA[..., :4]))
+        th = (2.0 * np.pi) * uB[..., :4]
+        z = np.stack([R * np.cos(th), R * np.sin(th)], axis=-1).reshape(lead + (8,))[..., :7]
+        if kind == 'gaussian':
+            return w * z
+        n2 = z[..., 0] * z[..., 0]
+        for i in range(1, 7):
+            n2 = n2 + z[..., i] * z[..., i]
+        nz = np.sqrt(n2)[..., None]
+        r = (uA[..., 4] ** (1.0 / 7.0))[..., None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(nz == 0.0, 0.0, np.sqrt(w) * r * z / nz)
+    u = np.stack([uA[..., :4], uB[..., :4]], axis=-1).reshape(lead + (8,))[..., :7]
+    return -w + u * (2.0 * w)
+
 
 def lon_lat_deviations(ego_yaw, ego_x, ego_y, ref_x, ref_y):
     """Utils/MPC_sim_utils.py:103-112: the deviation vector rotated into the vehicle frame"""
@@ -252,7 +315,13 @@ class ClosedLoopBatch:
 
     def __init__(self, track_name, batch=1, params=None, N=38, Tp=3.04, Ts=0.02, idx_start=0, cfg=None, device=0,
                  on_device=False, log_capacity=0, controller="nominal", disturbances=None, disturbance_steps=0, seed=0,
-                 qp_warm_start=None, qp_tol=None, track_of=None):
+                 qp_warm_start=None, qp_tol=None, track_of=None, draw="legacy"):
+        if draw not in ("legacy", "counter", "device"):
+            raise ValueError("ClosedLoopBatch: draw must be 'legacy', 'counter' or 'device'")
+        if draw != "legacy" and disturbances is not None and not isinstance(disturbances, DisturbanceModel):
+            raise ValueError(f"ClosedLoopBatch: draw='{draw}' draws from a DisturbanceModel; a (w_deriv, e_est) pair is played back (draw='legacy')")
+        if draw == "device" and disturbances is not None and not on_device:
+            raise ValueError("ClosedLoopBatch: draw='device' draws inside the device loop (on_device=True); draw='counter' plays the same stream back on the host")
         self.cfg = cfg or _config.default_config()
         kw = {} if qp_tol is None else dict(qp_tol=tuple(qp_tol))          # (termination tolerances of the interior point method; default: the solver's 1e-8)
         self.track_names, self.tracks, self.track_of = resolve_tracks(track_name, batch, track_of)
@@ -298,13 +367,21 @@ class ClosedLoopBatch:
             self.dev.set_state(self.x_sim, self.x_mpc, cold_start=True)
         self.log = dict(CiLX=[self.x_sim.copy()], MPC_SimX=[self.x_mpc.copy()], simU=[], simREF=[], simSolverDebug=[])
         # disturbance realisation (sim_step's simulate_disturbances / simulate_state_estimation): a DisturbanceModel -- `disturbance_steps`
-        # control steps are drawn with `seed` -- or a (w_deriv, e_est) pair of (n_steps, B, 7) arrays / None to play back
+        # control steps are drawn with `seed` -- or a (w_deriv, e_est) pair of (n_steps, B, 7) arrays / None to play back.
+        # draw: which stream a DisturbanceModel is drawn from -- "legacy": numpy's Mersenne-Twister, the reference's (draw);
+        # "counter": the project's counter-based stream, drawn on the host and played back (draw_counter); "device": the same stream
+        # drawn by the device loop itself, one launch per control step, for as long as the loop runs (disturbance_steps is ignored)
         self.w_deriv = self.e_est = None
         self._i = 0
         self._last_logs = None
+        self.draw = draw
         if disturbances is not None:
-            w, e = disturbances.draw(disturbance_steps, batch, seed) if isinstance(disturbances, DisturbanceModel) else disturbances
-            self.set_disturbances(w, e)
+            if draw == "device":
+                self.dev.attach_disturbances(disturbances, seed)
+            else:
+                w, e = disturbances if not isinstance(disturbances, DisturbanceModel) else \
+                    (disturbances.draw if draw == "legacy" else disturbances.draw_counter)(disturbance_steps, batch, seed)
+                self.set_disturbances(w, e)
 
     def set_disturbances(self, w_deriv=None, e_est=None):
         self.w_deriv = None if w_deriv is None else np.ascontiguousarray(w_deriv, dtype=float).reshape(-1, self.B, 7)
@@ -407,9 +484,13 @@ class ClosedLoopBatch:
         if logs is None:
             raise Exception("ClosedLoopBatch.save: no logs (run() first; a device loop needs log_capacity > 0)")
         out = []
+        w_deriv, e_est = self.w_deriv, self.e_est
+        if self.dev is not None and any(getattr(self.dev, "disturbance_streams", ())):
+            # a realisation drawn on the device is not stored anywhere: the logged steps' rows are regenerated (the same bits)
+            w_deriv, e_est = self.dev.disturbance_table(0, len(logs["simU"]))
         for b in (range(self.B) if instance is None else [int(instance)]):
             f = path.format(b) if instance is None else path
-            np.savez(f, **log_file_arrays(logs, b, self.w_deriv, self.e_est, T=T, Ts=self.Ts, drop_last_step=drop_last_step))
+            np.savez(f, **log_file_arrays(logs, b, w_deriv, e_est, T=T, Ts=self.Ts, drop_last_step=drop_last_step))
             out.append(f)
         return out
 
@@ -544,7 +625,7 @@ def train_segments(curv_threshold_lo=2e-5, curv_threshold_hi=1e-3, overlap=10, t
 
 
 def evaluate_segments(track_name, params, segment_groups, max_lat_dev, max_a_comb, max_steps, N=38, Tp=3.04, controller="nominal",
-                      check_every=0, **loop_kw):
+                      check_every=0, disturbances=None, seed=0, draw="legacy", **loop_kw):
     """objective_function (BO_WMPC/objective_function.py:57-175) for P candidate weight sets at once: params (P, 7) as in
     update_cost_function_weights, segment_groups a list of groups of (start, end) waypoint index pairs on the one track track_name, or
     -- the reference's structure, train_segments() -- of dicts with start, end and trajectory, every segment on its own track
@@ -553,7 +634,9 @@ def evaluate_segments(track_name, params, segment_groups, max_lat_dev, max_a_com
     its segment's start and scored until the planner's index equals its end, it crashes, or max_steps have run. Returns (objectives
     (P, n_groups, 2), feasible (P,), per-segment dict).
     A candidate with a crashed or timed-out segment is infeasible and all its objectives are NaN. (The reference stops a candidate
-    at its first crash; here all its segments run, the returned values are the same.)"""
+    at its first crash; here all its segments run, the returned values are the same.)
+    disturbances, seed, draw: as ClosedLoopBatch takes them -- draw="device" disturbs every segment for as long as it runs, with no
+    disturbance_steps to guess (the other two need it among loop_kw)."""
     params = np.asarray(params, dtype=float).reshape(-1, 7)
     P = len(params)
     flat = [p for grp in segment_groups for p in grp]
@@ -573,7 +656,7 @@ def evaluate_segments(track_name, params, segment_groups, max_lat_dev, max_a_com
     off = np.concatenate([[0], np.cumsum(sizes)])
     offsets = np.concatenate([c * S + off[:-1] for c in range(P)] + [[P * S]])
     cl = ClosedLoopBatch(track_name, batch=P * S, params=np.repeat(params, S, axis=0), N=N, Tp=Tp, idx_start=np.tile(pairs[:, 0], P),
-                         on_device=True, controller=controller, **set_kw, **loop_kw)
+                         on_device=True, controller=controller, disturbances=disturbances, seed=seed, draw=draw, **set_kw, **loop_kw)
     cl.dev.attach_segments(np.tile(pairs[:, 1], P), max_lat_dev, max_a_comb, group_offsets=offsets)
     cl.dev.run_segments(max_steps, check_every)
     objectives, feasible = _objectives_from_groups(cl.dev.segment_groups().reshape(P, len(sizes), 4))
@@ -708,7 +791,7 @@ class WeightScheduleEnv:
 
     def __init__(self, track_name, n_envs, actions, n_mpc_steps=20, max_lat_dev=2.0, episode_length=128, rew_sigmas=RL_SIGMAS,
                  rew_lims=RL_LIMS, obs_n_anticipation_points=10, full_lap=False, restart_indices=(0,), auto_reset=True, seed=0,
-                 obs_states="reference", track_of=None, **loop_kw):
+                 obs_states="reference", track_of=None, disturbances=None, draw="legacy", disturbance_seed=None, **loop_kw):
         self.table = np.ascontiguousarray(actions, dtype=float).reshape(-1, 7)
         self.n_envs, self.n_actions, self.n_mpc_steps = int(n_envs), len(self.table), int(n_mpc_steps)
         self.n_observations = 2 + 2 * int(obs_n_anticipation_points)
@@ -727,7 +810,10 @@ class WeightScheduleEnv:
                            np.array([self.restart_lists[t][0] for t in self.track_of], dtype=np.int64))
         if n_tracks > 1:
             loop_kw["track_of"] = self.track_of
-        self.loop = ClosedLoopBatch(track_name, batch=self.n_envs, on_device=True, controller="nominal", **loop_kw)
+        # disturbances / draw: as ClosedLoopBatch takes them, drawn with disturbance_seed (None: `seed`). draw="device" is what a
+        # training run needs: the environment's global step only grows, and no table has a last step to be sized for
+        self.loop = ClosedLoopBatch(track_name, batch=self.n_envs, on_device=True, controller="nominal", disturbances=disturbances, draw=draw,
+                                    seed=int(seed if disturbance_seed is None else disturbance_seed), **loop_kw)
         self.dev = self.loop.dev
         self.dev.attach_env(self.table, n_mpc_steps, max_lat_dev, episode_length, rew_sigmas, rew_lims, obs_n_anticipation_points,
                             full_lap=full_lap, obs_states=obs_states)

@@ -218,7 +218,9 @@ struct SimArgs {
     const double *ref0;                               // [b][4] first reference point of this step (planner output)
     // disturbance realisation played back by the loop (Utils/SimulationMode_main_class.py:121-143; nullable): additive disturbance of
     // the state DERIVATIVES, constant over a control step, and additive STATE ESTIMATION error, [step][b][7] each, dist_len steps
-    const double *dist_w, *dist_e; int dist_len;
+    // dist_live: the realisation is DRAWN, not played back (disturbance_kernels.hpp): dist_w / dist_e are the one-step slab that
+    // disturbance_draw_kernel filled in front of this launch -- row 0 whatever the step, dist_len is not consulted
+    const double *dist_w, *dist_e; int dist_len, dist_live;
     double *lCiLX, *lSimX, *lU, *lREF, *lDBG;         // logs (nullable): (cap+1,B,7) (cap+1,B,8) (cap,B,2) (cap,B,4) (cap,B,5)
     // samples the estimator of instance b has seen ([b], nullable: the global step counter, every instance started together). The RL
     // environment restarts single instances (env_kernels.hpp: env_begin_kernel zeroes the word): read and incremented here. Disturbance
@@ -280,12 +282,14 @@ __global__ void __launch_bounds__(64) plant_advance_kernel(const SimArgs sa)
     // keeps as CiLX and what the next step starts from); with a disturbance of the state derivatives a SECOND step from the same
     // state, xdot + w (sim_model_dynamic_stm_pacejka.py:196), gives the state the estimator is fed, and the state estimation error is
     // added to that. Both passes share one copy of the integrator (pass loop not unrolled, see below).
-    const bool have_w = sa.dist_w && step < sa.dist_len, have_e = sa.dist_e && step < sa.dist_len;
+    const bool in_len = sa.dist_live || step < sa.dist_len;
+    const bool have_w = sa.dist_w && in_len, have_e = sa.dist_e && in_len;
+    const size_t drow = sa.dist_live ? 0 : (size_t)step;
 #pragma unroll 1
     for (int pass = 0; pass < (have_w ? 2 : 1); pass++) {
         if (pass == 1) {
 #pragma unroll
-            for (int i = 0; i < 7; i++) { xd[i] = x[i]; x[i] = xs[i]; wv[i] = sa.dist_w[((size_t)step * B + b) * 7 + i]; }
+            for (int i = 0; i < 7; i++) { xd[i] = x[i]; x[i] = xs[i]; wv[i] = sa.dist_w[(drow * B + b) * 7 + i]; }
         }
     for (int e = 0; e < sa.n_elem; e++) {
         // The four RK stages share ONE inlined copy of the model (stage loop not unrolled): this kernel runs its code
@@ -323,7 +327,7 @@ __global__ void __launch_bounds__(64) plant_advance_kernel(const SimArgs sa)
     }
     if (have_e) {
 #pragma unroll
-        for (int i = 0; i < 7; i++) xd[i] = xd[i] + sa.dist_e[((size_t)step * B + b) * 7 + i];
+        for (int i = 0; i < 7; i++) xd[i] = xd[i] + sa.dist_e[(drow * B + b) * 7 + i];
     }
     if (live) {
         if (role == 0) {

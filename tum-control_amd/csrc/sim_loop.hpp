@@ -1,5 +1,5 @@
 // sim_loop.hpp -- host side of the device closed loop (K8 / K9) and of segment scoring: tum_sim, the owners of its memory, the control
-// step, tum_sim_run, the segments and the getters. Host code only, included by tum_nmpc.hip behind the capsule it drives (tum_ocp,
+// step, tum_sim_run, the disturbance generator (K18), the segments and the getters. Host code only, included by tum_nmpc.hip behind the capsule it drives (tum_ocp,
 // invalidate, flush_inputs, launch ...): the library stays one translation unit. The RL layers on top of it are sim_rl.hpp.
 #pragma once
 
@@ -52,6 +52,9 @@ struct SimCore {
     DevBuf<double> track, xsim, pose, hist, ref0, lCiLX, lSimX, lU, lREF, lDBG;
     DevBuf<int> closest, err, step_counter;
     DevBuf<double> dw, de; int dist_len = 0;          // (tum_sim_set_disturbances)
+    // the generator that draws the realisation instead (tum_sim_disturbances_attach): kinds, magnitudes and seed as the kernel takes
+    // them, and the one-step slab (batch x 7 per stream that is on) a control step draws into and its plant step reads
+    bool gen_on = false; DistArgs gen{}; DevBuf<double> slab_w, slab_e;
     // the track set (tum_sim_create_tracks): `track` holds the tables one behind the other, rows[t] is the first row of track t
     // (n_tracks + 1 entries), track_of[b] the track of instance b. One track (tum_sim_create): rows = {0, n_track}, track_of all 0 and
     // NO device copies -- the kernels take their single-track path on the null pointers. n_track is the row count of the whole table.
@@ -322,6 +325,15 @@ extern "C" int tum_sim_advance(tum_sim *s)
     sa.x_sim = k.xsim.get(); sa.x0 = c->dx0; sa.pose = k.pose.get(); sa.hist = k.hist.get(); sa.ref0 = k.ref0.get();
     sa.lCiLX = k.lCiLX.get(); sa.lSimX = k.lSimX.get(); sa.lU = k.lU.get(); sa.lREF = k.lREF.get(); sa.lDBG = k.lDBG.get();
     sa.dist_w = k.dw.get(); sa.dist_e = k.de.get(); sa.dist_len = k.dist_len;
+    if (k.gen_on) {
+        // the realisation of THIS step, drawn into the slab in front of the plant: the step comes from the loop's counter on the
+        // device (a captured chunk replays with constant arguments). Here, not in sim_enqueue_step_body, so that a loop driven by
+        // tum_sim_plan / solve / tum_sim_advance draws as well
+        DistArgs da = k.gen;
+        da.batch = c->batch; da.n_steps = 1; da.step_counter = k.step_counter.get(); da.out[0] = k.slab_w.get(); da.out[1] = k.slab_e.get();
+        LAUNCH(disturbance_draw_kernel, dim3((c->batch + 63) / 64, 2), dim3(64), 0, c->stream, da);
+        sa.dist_w = k.slab_w.get(); sa.dist_e = k.slab_e.get(); sa.dist_len = 0; sa.dist_live = 1;
+    }
     sa.samples = s->env.samples.get();          // (null without an environment)
     LAUNCH(plant_advance_kernel, dim3((c->batch * PLANT_LANES + 63) / 64), dim3(64), 0, c->stream, sa);
     k.step++;
@@ -443,6 +455,8 @@ extern "C" int tum_sim_run(tum_sim *s, int nsteps)
 
 extern "C" int tum_sim_steps(const tum_sim *s) { return s ? s->core.step : -1; }
 
+static void gen_release(SimCore &k) { k.gen_on = false; k.gen = DistArgs{}; k.slab_w.reset(); k.slab_e.reset(); }
+
 // Disturbance realisation of the loop (Utils/SimulationMode_main_class.py:121-143 with disturbance_playback, and what
 // Utils/MPC_sim_utils.py:54-67 generate_disturbances draws otherwise -- drawn on the host, closed_loop.DisturbanceModel): w_deriv
 // (additive on the state derivatives, constant over a control step) and e_est (additive state estimation error), n_steps x batch x 7
@@ -455,11 +469,82 @@ extern "C" int tum_sim_set_disturbances(tum_sim *s, const double *w_deriv, const
     HIPCHK(hipStreamSynchronize(c->stream));
     k.dw.reset(); k.de.reset(); k.dist_len = 0;
     graph_drop(s);          // (the pointers are kernel arguments of a captured chunk)
+    if (n_steps > 0 && (w_deriv || e_est)) gen_release(k);          // (a table takes the generator's place)
     if (n_steps == 0 || (!w_deriv && !e_est)) return 0;
     const size_t n = (size_t)n_steps * c->batch * 7;
     if (w_deriv) { HIPCHK(k.dw.alloc(n, false)); HIPCHK(hipMemcpy(k.dw.get(), w_deriv, sizeof(double) * n, hipMemcpyHostToDevice)); }
     if (e_est) { HIPCHK(k.de.alloc(n, false)); HIPCHK(hipMemcpy(k.de.get(), e_est, sizeof(double) * n, hipMemcpyHostToDevice)); }
     k.dist_len = n_steps;
+    return 0;
+}
+
+// The same realisation DRAWN on the device (disturbance_kernels.hpp; the definition of a draw: include/tum_nmpc.h): kind 0 switches a
+// stream off, 1..4 are 'uniform' (the ellipsoid), 'gaussian', 'absolute' and the box; both 0 detaches. A generator and a played-back
+// table exclude each other: attaching one removes the other.
+extern "C" int tum_sim_disturbances_attach(tum_sim *s, int kind_w, const double *bound_w, int kind_e, const double *bound_e, unsigned long long seed)
+{
+    if (!s) return fail("null argument");
+    const int kinds[2] = {kind_w, kind_e}; const double *bounds[2] = {bound_w, bound_e};
+    for (int q = 0; q < 2; q++) {
+        const std::string who = q ? "state estimation error" : "derivative disturbance";
+        if (kinds[q] < DIST_OFF || kinds[q] > DIST_BOX)
+            return fail("disturbances_attach: kind " + std::to_string(kinds[q]) + " of the " + who + " is outside 0..4 (off, uniform, gaussian, absolute, box)");
+        if (kinds[q] == DIST_OFF) continue;
+        if (!bounds[q]) return fail("disturbances_attach: the " + who + " is on and has no bounds");
+        for (int i = 0; i < 7; i++)
+            if (!(bounds[q][i] >= 0.0) || std::isinf(bounds[q][i]))
+                return fail("disturbances_attach: bound " + std::to_string(i) + " of the " + who + " is negative or not finite");
+    }
+    tum_ocp *c = s->c; SimCore &k = s->core; const size_t B = c->batch;
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    graph_drop(s);          // (a captured chunk holds the extra launch, or lacks it)
+    gen_release(k);
+    if (kind_w == DIST_OFF && kind_e == DIST_OFF) return 0;
+    k.dw.reset(); k.de.reset(); k.dist_len = 0;          // (the generator takes a table's place)
+    bool ok = true;
+    if (kind_w != DIST_OFF) ok &= k.slab_w.alloc(B * 7) == hipSuccess;
+    if (kind_e != DIST_OFF) ok &= k.slab_e.alloc(B * 7) == hipSuccess;
+    if (!ok) { gen_release(k); (void)hipGetLastError(); return fail("disturbances_attach: device allocation failed"); }
+    k.gen.seed = seed;
+    for (int q = 0; q < 2; q++) {
+        k.gen.kind[q] = kinds[q];
+        for (int i = 0; i < 7 && kinds[q] != DIST_OFF; i++) { k.gen.bound[q][i] = bounds[q][i]; k.gen.root[q][i] = std::sqrt(bounds[q][i]); }
+    }
+    k.gen_on = true;
+    return 0;
+}
+
+// The realisation of the control steps first_step .. first_step + n_steps - 1 as the attached generator draws it, n_steps x batch x 7
+// doubles per stream (host, step-major), either output may be null; a stream that is off gives zeros. Drawn into a temporary table in
+// chunks: the loop's step counter, slab and captured chunk are not touched.
+extern "C" int tum_sim_disturbances_table(tum_sim *s, long long first_step, int n_steps, double *w_out, double *e_out)
+{
+    if (!s) return fail("null argument");
+    if (first_step < 0 || n_steps < 0) return fail("disturbances_table: first_step < 0 or n_steps < 0");
+    tum_ocp *c = s->c; const SimCore &k = s->core; const size_t B = c->batch;
+    if (!k.gen_on) return fail("disturbances_table: no generator attached (tum_sim_disturbances_attach)");
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    double *outs[2] = {w_out, e_out};
+    const int chunk = (int)std::max<size_t>(1, ((size_t)1 << 22) / (B * 7));          // steps per launch: 32 MB of table per stream
+    DevBuf<double> tmp[2];
+    for (int q = 0; q < 2; q++) {
+        if (!outs[q]) continue;
+        if (k.gen.kind[q] == DIST_OFF) { std::fill(outs[q], outs[q] + (size_t)n_steps * B * 7, 0.0); outs[q] = nullptr; continue; }
+        HIPCHK(tmp[q].alloc((size_t)std::min(chunk, std::max(n_steps, 1)) * B * 7, false));
+    }
+    if (!outs[0] && !outs[1]) return 0;
+    for (int done = 0; done < n_steps; done += chunk) {
+        const int n = std::min(chunk, n_steps - done);
+        DistArgs da = k.gen;
+        da.batch = c->batch; da.n_steps = n; da.first_step = first_step + done; da.step_counter = nullptr;
+        da.out[0] = outs[0] ? tmp[0].get() : nullptr; da.out[1] = outs[1] ? tmp[1].get() : nullptr;
+        const size_t rows = (size_t)n * B;
+        LAUNCH(disturbance_draw_kernel, dim3((unsigned)((rows + 63) / 64), 2), dim3(64), 0, c->stream, da);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int q = 0; q < 2; q++)
+            if (outs[q]) HIPCHK(hipMemcpy(outs[q] + (size_t)done * B * 7, tmp[q].get(), sizeof(double) * rows * 7, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

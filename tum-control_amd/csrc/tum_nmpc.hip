@@ -24,6 +24,7 @@
 #include "policy_kernels.hpp"
 #include "collect_kernels.hpp"
 #include "ppo_kernels.hpp"
+#include "disturbance_kernels.hpp"
 #include "sqp_kernels.hpp"
 #include "rti_kernels.hpp"
 #include "bo_kernels.hpp"
@@ -2361,7 +2362,7 @@ extern "C" int tum_ocp_constraints_get(tum_ocp *c, int stage, const char *field,
 }
 
 // the device closed loop on the capsule above, host code like the rest of this file in headers of its own
-#include "sim_loop.hpp"          // K8 / K9: tum_sim, the control step, segment scoring, the getters
+#include "sim_loop.hpp"          // K8 / K9 / K18: tum_sim, the control step, the disturbance generator, segment scoring, the getters
 #include "sim_rl.hpp"            // K11 to K14: the RL environment, the agent, collection, the trainer
 #include "bo.hpp"                // K15: tum_bo, the acquisition value of the Bayesian-optimisation step
 #include "gp.hpp"                // K16: tum_gp, the marginal log-likelihood of a surrogate and its factor

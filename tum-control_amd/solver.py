@@ -76,6 +76,7 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_ocp_snmpc_attach", "tum_ocp_snmpc_samples", "tum_ocp_snmpc_set_offsets",
              "tum_planner_emulate", "tum_planner_emulate_tracks", "tum_sim_create", "tum_sim_create_tracks", "tum_sim_free", "tum_sim_set_state", "tum_sim_plan", "tum_sim_advance",
              "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
+             "tum_sim_disturbances_attach", "tum_sim_disturbances_table",
              "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step",
              "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout",
              "tum_sim_policy_attach_value", "tum_sim_policy_eval_ac", "tum_sim_gae", "tum_sim_env_collect",
@@ -170,6 +171,9 @@ def load_library(path=None):
     L.tum_sim_get.argtypes = [vp, cs, dp, ctypes.c_longlong]
     if hasattr(L, "tum_sim_set_disturbances"):
         L.tum_sim_set_disturbances.argtypes = [vp, dp, dp, ci]
+    if hasattr(L, "tum_sim_disturbances_attach"):
+        L.tum_sim_disturbances_attach.argtypes = [vp, ci, dp, ci, dp, ctypes.c_ulonglong]
+        L.tum_sim_disturbances_table.argtypes = [vp, ctypes.c_longlong, ci, dp, dp]
     if hasattr(L, "tum_sim_segments_attach"):
         L.tum_sim_segments_attach.argtypes = [vp, ip, ip, ci, cd, cd]
         L.tum_sim_run_segments.argtypes = [vp, ci, ci]
@@ -936,8 +940,36 @@ class DeviceClosedLoop:
                 if a.ndim != 3 or a.shape[1:] != (self.B, 7) or (n and a.shape[0] != n):
                     raise Exception("DeviceClosedLoop.set_disturbances: expected (n_steps, batch, 7) arrays of equal length")
                 n = a.shape[0]
+        if n:
+            self.disturbance_streams = (False, False)          # (a table takes an attached generator's place)
         self._chk(self._L.tum_sim_set_disturbances(self._s, None if arrs[0] is None else _dp(arrs[0]), None if arrs[1] is None else _dp(arrs[1]), n),
                   "sim_set_disturbances")
+
+    DIST_KINDS = dict(uniform=1, gaussian=2, absolute=3)          # (anything else: 4, the box -- generate_disturbances' last branch)
+
+    def attach_disturbances(self, model, seed=0):
+        """Draw the realisation ON THE DEVICE from now on, one launch per control step (disturbance_draw_kernel): `model` a
+        closed_loop.DisturbanceModel -- its switches, kinds and magnitudes --, `seed` the key of the counter-based draws
+        (DisturbanceModel.draw_counter is the host statement; include/tum_nmpc.h the definition). Removes a played-back table;
+        model=None (or a model with both switches off) detaches. The attached streams are kept in .disturbance_streams."""
+        on = [False, False] if model is None else [bool(model.derivatives), bool(model.state_estimation)]
+        kinds = [self.DIST_KINDS.get(model.types[q], 4) if on[q] else 0 for q in range(2)]
+        bounds = [None, None]
+        if model is not None:
+            bounds = [np.ascontiguousarray(np.asarray(b, dtype=np.float64)[:, 1]) for b in (model.bounds_derivatives, model.bounds_state_estimation)]
+        self._chk(self._L.tum_sim_disturbances_attach(self._s, kinds[0], None if not on[0] else _dp(bounds[0]), kinds[1],
+                                                      None if not on[1] else _dp(bounds[1]), int(seed) & (2 ** 64 - 1)), "sim_disturbances_attach")
+        self.disturbance_streams = tuple(on)
+
+    def disturbance_table(self, first_step, n_steps):
+        """(w_deriv, e_est) of the control steps first_step .. first_step + n_steps - 1 as the attached generator draws them:
+        (n_steps, B, 7) arrays, None for a stream that is off -- what set_disturbances plays back. Regenerated on the device by the
+        function the live draw uses (equal to the bit); the loop is not touched."""
+        on = getattr(self, "disturbance_streams", (False, False))
+        out = [np.empty((int(n_steps), self.B, 7)) if f else None for f in on]
+        self._chk(self._L.tum_sim_disturbances_table(self._s, int(first_step), int(n_steps), None if out[0] is None else _dp(out[0]),
+                                                     None if out[1] is None else _dp(out[1])), "sim_disturbances_table")
+        return out[0], out[1]
 
     def plan(self):
         self._chk(self._L.tum_sim_plan(self._s), "sim_plan")
