@@ -586,6 +586,34 @@ int tum_sim_policy_eval(tum_sim *s, const double *obs, int n, double *logits, do
 int tum_sim_env_rollout(tum_sim *s, int n_env_steps, const double *first_obs, int on_end, const int *start_table,
                         int check_every, double *out, int *actions_out, int *live_out, int *steps_run);
 
+/* --- K19: the learned weight schedule INSIDE the loop: enable_WMPC of the reference's controller classes (NMPC_class.py:120-160,208-239,
+ * SNMPC_class.py:224-255, Reduced_Robustified_NMPC_class.py:206-245,373-404) with the attached policy as the agent. One more kernel
+ * per control step between the solve and the plant step (wmpc_schedule_kernel), inside captured chunks too. Per instance, with a
+ * counter c that is 0 at attach time: after the solve of a control step, if c >= period then c = 0, DECIDE and INSTALL; then, in every
+ * case, c += 1. period 20: decisions after the solves of the steps 20, 40, 60 counted from attach time; 1: from step 1 on; 0: every
+ * step; negative: refused. Until the first decision the loop keeps the weights it has.
+ * DECIDE: the observation of tum_sim_env_attach (2 + 2 n_samples entries, idx_v / idx_yawrate / obs_lo / obs_hi as there) with
+ * lat_dev the lateral deviation of the state the solve STARTED at (x0) from the first point of this step's reference and
+ * vel_dev = x0[3] - ref_v[0], rounded to float32, through the policy net; the first index of the largest logit.
+ * INSTALL: row `action` of table (n_actions x 7), the words tum_sim_env_step writes.
+ * on_failure 1 ("base"): an instance whose solve failed (status != 0) gets back, behind the decision logic of that step, the W and the
+ * slack penalties it held when the schedule was attached -- the reference builds a fresh solver from the YAML weights then
+ * (main.py:59-61), so a row decided at that very step is lost; the counter is not touched. 0 ("keep"): the weights stay.
+ * The first log_capacity decisions of every instance are stored (step, action, observation before the rounding); later ones are counted.
+ * Needs an attached policy whose input width is 2 + 2 n_samples and whose action count is n_actions, and 10 <= N <= 127. Runs on
+ * nominal, coupled SNMPC and R2 capsules, beside segments and drawn disturbances. Refused, each with its own message: a loop that is
+ * an RL environment (and an environment on a loop with a schedule), a full-W capsule, SQP mode, rti_phase 1 / 2, the development
+ * kernel 'fused', bad indices or bounds. table == NULL detaches: the weights stay as last installed. Attaching again takes a new
+ * snapshot and starts counters and log afresh; detaching the policy detaches the schedule; the state function (set_state) zeroes
+ * counters and log. Either way a captured chunk of the run function is dropped. Only the run function launches the kernel: a loop
+ * driven by tum_sim_plan / solve / tum_sim_advance is not scheduled. */
+int tum_sim_wmpc_attach(tum_sim *s, const double *table, int n_actions, int period, int on_failure, int n_samples,
+                        const int *idx_v, const int *idx_yawrate, const double *obs_lo, const double *obs_hi, int log_capacity);
+/* "counter" (B: c as the next control step tests it), "n_decisions" (B), "steps" and "actions" (B x log_capacity, -1 where none),
+ * "observations" (B x log_capacity x (2 + 2 n_samples)), the snapshot "base_W" (B x (N + 1) x 6: the diagonal of W per stage) and
+ * "base_pen" (B x 36), and the same arrays as the capsule holds them now: "W", "pen". */
+int tum_sim_wmpc_get(tum_sim *s, const char *field, double *out, long long len);
+
 /* --- K13: collecting PPO training rollouts on the device (stable_baselines3 collect_rollouts + compute_returns_and_advantage as
  * rl_training.py's model.learn drives them). The PPO update is not here.
  * The value net of the agent beside the attached policy (mlp_extractor.value_net.<i>, value_net): widths[n_layers + 1] = inputs,

@@ -315,7 +315,14 @@ class ClosedLoopBatch:
 
     def __init__(self, track_name, batch=1, params=None, N=38, Tp=3.04, Ts=0.02, idx_start=0, cfg=None, device=0,
                  on_device=False, log_capacity=0, controller="nominal", disturbances=None, disturbance_steps=0, seed=0,
-                 qp_warm_start=None, qp_tol=None, track_of=None, draw="legacy"):
+                 qp_warm_start=None, qp_tol=None, track_of=None, draw="legacy", wmpc=None, weights_update_period=20,
+                 wmpc_on_failure="base", wmpc_log_capacity=0):
+        """wmpc = (policy, table): the learned weight schedule of the reference's controller classes (enable_WMPC) -- a WeightPolicy
+        and the (A, 7) parameter table it picks rows of; after the solve of every control step the rule of WmpcSchedule, with
+        weights_update_period control steps between decisions. on_device=True: inside the device loop (DeviceClosedLoop.attach_wmpc);
+        on_device=False: in step(), the host statement the device is held to. wmpc_on_failure "base": an instance whose solve failed
+        gets the weights of this constructor back (`params`, or the YAML's x 0.01); "keep": it keeps what it has.
+        wmpc_log_capacity: decisions stored per instance (wmpc_decisions)."""
         if draw not in ("legacy", "counter", "device"):
             raise ValueError("ClosedLoopBatch: draw must be 'legacy', 'counter' or 'device'")
         if draw != "legacy" and disturbances is not None and not isinstance(disturbances, DisturbanceModel):
@@ -354,8 +361,14 @@ class ClosedLoopBatch:
         else:
             raise ValueError("controller must be 'nominal', 'snmpc' or 'r2'")
         self.solver.install_reference_ocp()
+        # the weights the solver holds, per instance: diag W of the stages < N, diag W_e, [L1, L2] (install_reference_ocp's defaults)
+        m = self.cfg["mpc"]
+        w6 = 0.01 * np.array([m["q_lon"] / m["s_lon"] ** 2, m["q_lat"] / m["s_lat"] ** 2, m["q_yaw"] / m["s_yaw"] ** 2, m["q_vel"] / m["s_vel"] ** 2,
+                              m["r_jerk"] / m["s_jerk"] ** 2, m["r_steering_rate"] / m["s_steering_rate"] ** 2])
+        self._weights = [np.tile(w6, (batch, 1)), np.tile(w6[:4], (batch, 1)), np.tile([float(m["L1_pen"]), float(m["L2_pen"])], (batch, 1))]
         if params is not None:
             self.set_weights(np.asarray(params, dtype=float).reshape(batch, 7))
+        self._base_weights = [a.copy() for a in self._weights]          # (what wmpc_on_failure="base" goes back to)
         self.solver.set_x0(self.x_mpc)
         self.solver.cold_start()
         self.est = MovingAverageEstimator(batch)
@@ -382,6 +395,55 @@ class ClosedLoopBatch:
                 w, e = disturbances if not isinstance(disturbances, DisturbanceModel) else \
                     (disturbances.draw if draw == "legacy" else disturbances.draw_counter)(disturbance_steps, batch, seed)
                 self.set_disturbances(w, e)
+        self.wmpc = None
+        if wmpc is not None:
+            policy, table = wmpc
+            self.wmpc = WmpcSchedule(policy, table, weights_update_period, batch, Ts=Ts, log_capacity=wmpc_log_capacity)
+            if wmpc_on_failure not in ("base", "keep"):
+                raise ValueError("ClosedLoopBatch: wmpc_on_failure must be 'base' or 'keep'")
+            self.wmpc_on_failure = wmpc_on_failure
+            if self.dev is not None:
+                self.dev.attach_policy(policy)
+                self.dev.attach_wmpc(self.wmpc.table, weights_update_period, wmpc_on_failure, self.wmpc.n_samples, wmpc_log_capacity)
+
+    def wmpc_decisions(self):
+        """the decisions of the learned weight schedule so far: dict of n_decisions (B,), and of the first wmpc_log_capacity of every
+        instance steps, actions (B, capacity; -1 where none) and observations (B, capacity, n_obs) -- on either path"""
+        if self.wmpc is None:
+            raise Exception("ClosedLoopBatch.wmpc_decisions: no weight schedule (wmpc=(policy, table))")
+        if self.dev is not None:
+            return {k: self.dev.wmpc_get(k) for k in ("n_decisions", "steps", "actions", "observations")}
+        w = self.wmpc
+        return dict(n_decisions=w.n_decisions.copy(), steps=w.steps.copy(), actions=w.actions.copy(), observations=w.observations.copy())
+
+    def _put_weights(self):
+        """self._weights through the cost setters (the calls of set_weights)"""
+        s, B, N = self.solver, self.B, self.N
+        w6, we, L = self._weights
+        W = np.zeros((B, 6, 6)); We = np.zeros((B, 4, 4))
+        for j in range(B):
+            W[j] = np.diag(w6[j]); We[j] = np.diag(we[j])
+        s.cost_set(-1, "W", W if B > 1 else W[0])
+        s.cost_set(N, "W", We if B > 1 else We[0])
+        for st, n in ((0, 1), (1, 3), (N, 2)):
+            for f, col in (("zl", 0), ("zu", 0), ("Zl", 1), ("Zu", 1)):
+                v = np.repeat(L[:, col:col + 1], n, axis=1)
+                s.cost_set(st, f, v if B > 1 else v[0])
+
+    def _wmpc_after_solve(self, yref, ref0, status):
+        """the WMPC branch at the end of the controller classes' solve(), for every instance, and main.py:59-61 behind it"""
+        due, actions = self.wmpc.after_solve(self._i, self.x_mpc, ref0, yref)
+        changed = len(due) > 0
+        for b, a in zip(due, actions):
+            p = self.wmpc.table[a]
+            self._weights[0][b] = [p[0], p[0], p[1], p[2], p[3], p[4]]; self._weights[1][b] = [p[0], p[0], p[1], p[2]]; self._weights[2][b] = p[5:7]
+        failed = np.nonzero(np.asarray(status) != 0)[0]
+        if self.wmpc_on_failure == "base" and len(failed):
+            for cur, base in zip(self._weights, self._base_weights):
+                cur[failed] = base[failed]
+            changed = True
+        if changed:
+            self._put_weights()
 
     def set_disturbances(self, w_deriv=None, e_est=None):
         self.w_deriv = None if w_deriv is None else np.ascontiguousarray(w_deriv, dtype=float).reshape(-1, self.B, 7)
@@ -391,6 +453,9 @@ class ClosedLoopBatch:
 
     def set_weights(self, p):
         s, B, N = self.solver, self.B, self.N
+        p = np.asarray(p, dtype=float).reshape(-1, 7)          # (one row for all, or one per instance)
+        p = np.broadcast_to(p, (B, 7))
+        self._weights = [p[:, [0, 0, 1, 2, 3, 4]].copy(), p[:, [0, 0, 1, 2]].copy(), p[:, 5:7].copy()]
         W = np.zeros((B, 6, 6))
         for j in range(B):
             W[j] = np.diag([p[j, 0], p[j, 0], p[j, 1], p[j, 2], p[j, 3], p[j, 4]])
@@ -415,6 +480,8 @@ class ClosedLoopBatch:
                           s.get_stats("qp_iter").astype(float), s.get_stats("status").astype(float)], axis=1)
         # sim_step, simMode 0: the plant takes the predicted acceleration of stage 1 and the steering rate
         a_in, sr_in = x1[:, 7].copy(), u0[:, 1].copy()
+        if self.wmpc is not None:
+            self._wmpc_after_solve(yref, ref0, stats[:, 4])
         failed = np.nonzero(stats[:, 4] != 0)[0]
         if len(failed):
             self._reinitialise(failed, X, U)
@@ -636,7 +703,9 @@ def evaluate_segments(track_name, params, segment_groups, max_lat_dev, max_a_com
     A candidate with a crashed or timed-out segment is infeasible and all its objectives are NaN. (The reference stops a candidate
     at its first crash; here all its segments run, the returned values are the same.)
     disturbances, seed, draw: as ClosedLoopBatch takes them -- draw="device" disturbs every segment for as long as it runs, with no
-    disturbance_steps to guess (the other two need it among loop_kw)."""
+    disturbance_steps to guess (the other two need it among loop_kw).
+    wmpc=(policy, table), weights_update_period, wmpc_on_failure among loop_kw: every segment drives under the learned weight
+    schedule from the candidate's weights on (ClosedLoopBatch) -- a schedule scored on the training segments."""
     params = np.asarray(params, dtype=float).reshape(-1, 7)
     P = len(params)
     flat = [p for grp in segment_groups for p in grp]
@@ -681,6 +750,66 @@ def rl_observation(ref_yaw, ref_v, Ts, n_samples, lat_dev, vel_dev):
     obs = np.concatenate((np.array([lat_dev, vel_dev]), ref_v[iv], yaw_rate[ir]))
     b = env_observation_bounds(n_samples)
     return (obs - b[0]) / (b[1] - b[0])
+
+
+def wmpc_observation(x0, ref0, ref_yaw, ref_v, Ts, n_samples):
+    """The observation the controller classes form for their agent at the end of solve() (NMPC_class.py:213-222, the same lines in the
+    SNMPC and R2NMPC classes): lat_dev the lateral component of LonLatDeviations of the state the solve STARTED at (x0, what
+    set_initial_state was handed) against the first point of this step's reference, vel_dev = x0[3] - ref_v[0], then
+    rl_observation of the step's window (N + 1 points). Unlike the RL environment's, whose first two entries are always 0."""
+    _, lat_dev = lon_lat_deviations(x0[2], x0[0], x0[1], ref0[0], ref0[1])
+    vel_dev = x0[3] - ref_v[0]
+    return rl_observation(ref_yaw, ref_v, Ts, n_samples, lat_dev, vel_dev)
+
+
+class WmpcSchedule:
+    """The learned weight schedule of the reference's controller classes (enable_WMPC; NMPC_class.py:208-239 and the same branch of
+    the SNMPC and R2NMPC classes), stated once for `batch` instances: a counter c per instance, 0 at the start. After the solve of
+    control step k: `if c >= period: c = 0; decide`, then -- in every case -- c += 1. period 20 decides after the solves of the steps
+    20, 40, 60 (0-based); 1 from step 1 on; 0 at every step; a negative period is refused. Decide is policy.predict (deterministic:
+    the first index of the largest logit, the observation rounded to float32) on wmpc_observation; the caller installs
+    table[action] (update_cost_function_weights). A failed solve does not touch the counter. The first log_capacity decisions of
+    every instance are stored (steps, actions, observations), every decision is counted: what wmpc_schedule_kernel keeps on the device.
+    n_obs_stack > 1 of rl_config.yaml is not supported: the policy takes one observation of 2 + 2 n_samples entries."""
+
+    def __init__(self, policy, table, period, batch=1, Ts=0.02, log_capacity=0):
+        self.policy = policy
+        self.table = np.ascontiguousarray(table, dtype=float)
+        if self.table.ndim != 2 or self.table.shape[1] != 7:
+            raise ValueError("WmpcSchedule: table must be (n_actions, 7)")
+        if int(period) < 0:
+            raise ValueError("WmpcSchedule: weights_update_period is negative (0 decides at every control step)")
+        if policy.n_actions != len(self.table):
+            raise ValueError(f"WmpcSchedule: the policy has {policy.n_actions} actions, the table {len(self.table)} rows")
+        if policy.n_observations < 4 or policy.n_observations % 2:
+            raise ValueError(f"WmpcSchedule: the policy takes {policy.n_observations} inputs; an observation has 2 + 2 n_samples entries")
+        self.period, self.B, self.Ts = int(period), int(batch), float(Ts)
+        self.n_samples = (policy.n_observations - 2) // 2
+        self.counter = np.zeros(self.B, dtype=np.int64)
+        L = int(log_capacity)
+        self.n_decisions = np.zeros(self.B, dtype=np.int64)
+        self.steps = np.full((self.B, L), -1, dtype=np.int64); self.actions = np.full((self.B, L), -1, dtype=np.int64)
+        self.observations = np.zeros((self.B, L, policy.n_observations))
+        self.current_action = [None] * self.B          # (self.current_action of the controller classes)
+
+    def after_solve(self, k, x0, ref0, yref):
+        """the branch behind the solve of control step k: x0 (B, 8) the states the solves started at, ref0 (B, 4) and yref
+        (B, N + 1, 6) this step's reference (columns 2, 3 of yref: ref_yaw, ref_v). Returns (due instances, their actions)."""
+        x0, ref0, yref = np.reshape(x0, (self.B, -1)), np.reshape(ref0, (self.B, -1)), np.asarray(yref).reshape(self.B, -1, 6)
+        due = np.nonzero(self.counter >= self.period)[0]
+        self.counter[due] = 0
+        actions = []
+        for b in due:
+            obs = wmpc_observation(x0[b], ref0[b], yref[b, :, 2], yref[b, :, 3], self.Ts, self.n_samples)
+            a = int(self.policy.predict(obs))
+            n = self.n_decisions[b]
+            if n < self.steps.shape[1]:
+                self.steps[b, n], self.actions[b, n], self.observations[b, n] = k, a, obs
+            self.n_decisions[b] += 1
+            self.current_action[b] = a
+            actions.append(a)
+        self.counter += 1
+        return due, np.array(actions, dtype=np.int64)
 
 
 def rl_reward(lat_devs, vel_devs, sigmas, lims):

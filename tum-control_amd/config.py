@@ -59,6 +59,12 @@ def load_reference_config(config_path, sim_main_params=None, mpc_params_file="ED
     # which OCP the controller classes build (NMPC_class.py:90-94): the NONLINEAR_LS formulation is the one that exists here;
     # the value is carried so that the controller mirrors can refuse anything else instead of silently assuming it
     cfg["mpc"]["costfunction_type"] = mp.get("costfunction_type", "NONLINEAR_LS")
+    # the learned weight schedule of the controller classes (NMPC_class.py:120-160): carried as the YAML states it; a relative
+    # WMPC_model is a path from the directory the reference is started in, the parent of Config/ (wmpc_root)
+    for k in ("enable_WMPC", "WMPC_model", "weights_update_period"):
+        if k in mp:
+            cfg["mpc"][k] = mp[k]
+    cfg["mpc"]["wmpc_root"] = os.path.dirname(os.path.abspath(os.path.normpath(config_path)))
     with open(os.path.join(config_path, mp["lookuptable_gg_limits"])) as f:
         rows = list(csv.DictReader(f))
     cfg["ggv"] = dict(v=[float(r["vel_max_mps"]) for r in rows], ax=[float(r["ax_max_mps2"]) for r in rows],

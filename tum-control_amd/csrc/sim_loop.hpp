@@ -96,6 +96,14 @@ struct SimTrainer {
     DevBuf<float> theta; DevBuf<double> m, v, G, part, advstat, rowrec, stats, data; DevBuf<int> idx;
 };
 
+// the learned weight schedule (tum_sim_wmpc_attach): the settings as the kernel takes them, the table / indices / bounds, the snapshot of
+// W and the penalties, and per instance the step of the last decision, the decision count and the decision log
+struct SimWmpc {
+    bool on = false; int n_obs = 0; size_t lds = 0; WmpcArgs a{};
+    DevBuf<double> table, bounds, base_W, base_pen, log_obs;
+    DevBuf<int> idx, since, n_dec, log_step, log_act, act;
+};
+
 struct tum_sim {
     tum_ocp *c = nullptr;
     SimCore core;
@@ -104,6 +112,7 @@ struct tum_sim {
     hipStream_t s2 = nullptr; hipEvent_t evF = nullptr, evJ = nullptr;          // side stream of the linearisation that runs beside the planner, fork / join events
     SimSegments seg; SimEnv env;
     SimNet pol, val; SimRollout roll; SimCollect col; SimTrainer ppo;          // (env_release and the chain behind it: sim_rl.hpp)
+    SimWmpc wm;                                                                // (stands on the policy: policy_release drops it)
 };
 
 // a captured chunk holds kernel arguments and launches by value: whoever changes one of them drops it (the loop's stream is idle)
@@ -146,6 +155,40 @@ static int env_get(tum_sim *s, const std::string &f, double *out, long long len)
                      f == "env_qp_failures" ? v.qpf.get() : f == "env_samples" ? v.samples.get() : nullptr;
     if (!src) return fail("sim_get: unknown field '" + f + "'");
     return fetch_ints(src, B, out);
+}
+
+// What the loop does for an attached weight schedule (sim_rl.hpp): it refuses what the schedule cannot run on, at attach time and
+// again at every run (a capsule can change behind an attached schedule), and launches its kernel behind every solve.
+static int wmpc_refuse(const tum_sim *s, const char *who)
+{
+    const tum_ocp *c = s->c;
+    const std::string w(who);
+    if (s->env.on) return fail(w + ": this loop is an RL environment (tum_sim_env_attach), which installs the weights by its own rules; detach it first");
+    if (c->dWf) return fail(w + ": the weight schedule installs a diagonal W (update_cost_function_weights); this capsule keeps a full W");
+    if (c->nlp_type) return fail(w + ": the weight schedule runs behind one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
+    if (c->rti_phase) return fail(w + ": the weight schedule runs behind whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
+    if (c->kmode == KMode::FUSED || (c->ka.flags & KF_DEBUG)) return fail(w + ": the weight schedule runs on the pipeline, not on the development kernel 'fused'");
+    return 0;
+}
+// the schedule's kernel behind the solve that is on the stream (the capsule's arrays as they are NOW, as env_bind takes them)
+static int wmpc_enqueue(tum_sim *s)
+{
+    tum_ocp *c = s->c; SimWmpc &m = s->wm; WmpcArgs &a = m.a;
+    invalidate(c, CH_W | CH_BOUNDS);          // (what the kernel may write: W and the slack penalties)
+    a.x0 = c->dx0; a.yref = c->dyref; a.status = c->dstatus; a.W = c->dW; a.pen = c->dpen;
+    LAUNCH(wmpc_schedule_kernel, dim3((c->batch + POL_TILE - 1) / POL_TILE), dim3(64 * POL_WAVES), m.lds, c->stream, a);
+    return 0;
+}
+// a new run of the loop (tum_sim_set_state zeroes the step counter): no decision yet, the counters at 0, an empty log
+static int wmpc_zero(tum_sim *s)
+{
+    const size_t B = s->c->batch; SimWmpc &m = s->wm; const size_t L = (size_t)m.a.log_cap * B;
+    HIPCHK(hipMemset(m.since.get(), 0, sizeof(int) * B)); HIPCHK(hipMemset(m.n_dec.get(), 0, sizeof(int) * B));
+    if (L) {
+        HIPCHK(hipMemset(m.log_step.get(), 0xff, sizeof(int) * L)); HIPCHK(hipMemset(m.log_act.get(), 0xff, sizeof(int) * L));
+        HIPCHK(hipMemset(m.log_obs.get(), 0, sizeof(double) * L * m.n_obs));
+    }
+    return 0;
 }
 
 // what a track set must satisfy (tum_sim_create_tracks, tum_planner_emulate_tracks): ascending offsets from 0, at least 2 rows per
@@ -284,6 +327,7 @@ extern "C" int tum_sim_set_state(tum_sim *s, const double *x_sim, const double *
     HIPCHK(hipMemset(k.step_counter.get(), 0, 2 * sizeof(int)));
     if (s->seg.on && seg_zero(s)) return 1;
     if (s->env.on && env_zero(s)) return 1;
+    if (s->wm.on && wmpc_zero(s)) return 1;
     HIPCHK(hipDeviceSynchronize());          // (the fills run on the NULL stream, the loop on the capsule's non-blocking one)
     k.step = 0;
     if (k.log_cap > 0) {
@@ -374,6 +418,7 @@ static int sim_enqueue_step_body(tum_sim *s, bool events)
         env_bind(s);
         LAUNCH(env_score_kernel, dim3(c->batch), dim3(64), 0, c->stream, s->env.a);
     }
+    if (s->wm.on && wmpc_enqueue(s)) return 1;          // the learned weight schedule, in the same place (tum_sim_wmpc_attach)
     return tum_sim_advance(s);
 }
 static int sim_enqueue_step(tum_sim *s, bool events)
@@ -396,6 +441,7 @@ static int sim_run_enqueue(tum_sim *s, int nsteps)
     tum_ocp *c = s->c;
     if (c->nlp_type) return fail("sim_run: the device closed loop runs one SQP-RTI iteration per control step; this capsule is in SQP mode (nlp_solver_type 1)");
     if (c->rti_phase) return fail("sim_run: the device closed loop runs whole SQP-RTI steps; this capsule splits them (rti_phase 1 / 2): set rti_phase 0");
+    if (s->wm.on && wmpc_refuse(s, "sim_run")) return 1;
     DevGuard guard(c->d.device); GUARD_OK(guard);
     invalidate(c, CH_ITERATE);          // (the closed loop keeps the general linearisation: its chunks are captured and replayed)
     if (flush_inputs(c)) return 1;            // (pending host setters go up before anything is captured)
@@ -680,6 +726,7 @@ extern "C" int tum_sim_get(tum_sim *s, const char *field, double *out, long long
     }
     const struct { const char *name; const double *src; long long want; } arrays[] = {
         {"x_sim", k.xsim.get(), B * 7}, {"x_mpc", c->dx0, B * 8}, {"pose", k.pose.get(), B * 2}, {"ref0", k.ref0.get(), B * 4},
+        {"yref", c->dyref, B * (c->N + 1) * 6},          // (the reference window of the last planned step, [x, y, yaw, v, 0, 0] per point)
         {"CiLX", k.lCiLX.get(), (L + 1) * B * 7}, {"MPC_SimX", k.lSimX.get(), (L + 1) * B * 8}, {"simU", k.lU.get(), L * B * 2},
         {"simREF", k.lREF.get(), L * B * 4}, {"simSolverDebug", k.lDBG.get(), L * B * 5}};
     for (const auto &a : arrays) {

@@ -6,7 +6,8 @@
 // policy's inputs, the trainer updates both nets. Detaching one detaches what stands on it, in this order.
 static void ppo_release(tum_sim *s) { s->ppo = SimTrainer{}; }
 static void value_release(tum_sim *s) { ppo_release(s); s->val = SimNet{}; s->col = SimCollect{}; }
-static void policy_release(tum_sim *s) { value_release(s); s->pol = SimNet{}; s->roll = SimRollout{}; }
+static void wmpc_release(tum_sim *s) { s->wm = SimWmpc{}; }          // (the weight schedule of the controller classes runs the policy net)
+static void policy_release(tum_sim *s) { value_release(s); wmpc_release(s); s->pol = SimNet{}; s->roll = SimRollout{}; }
 static void env_release(tum_sim *s) { policy_release(s); s->env = SimEnv{}; }
 
 // ---------------------------------------------------------------------------------------------- K11: RL environment
@@ -34,6 +35,7 @@ extern "C" int tum_sim_env_attach(tum_sim *s, const double *table, int n_actions
     if (table) {
         if (!sigmas || !lims || !obs_lo || !obs_hi || !idx_v || !idx_yawrate) return fail("null argument");
         if (env_refuse(s, "env_attach")) return 1;
+        if (s->wm.on) return fail("env_attach: this loop runs a learned weight schedule (tum_sim_wmpc_attach), which installs the weights by its own rule; detach it first");
         if (n_actions < 1 || n_mpc_steps < 1 || episode_length < 1 || n_samples < 1) return fail("env_attach: n_actions, n_mpc_steps, episode_length and n_samples must be >= 1");
         if (N < ENV_MA || N + 1 > ENV_MAXPTS) return fail("env_attach: the observation's 10-tap moving average of the yaw rate needs 10 <= N <= 127");
         if (max_lat_dev != max_lat_dev) return fail("env_attach: max_lat_dev is NaN (an infinite one disables the crash test)");
@@ -265,6 +267,7 @@ extern "C" int tum_sim_policy_attach(tum_sim *s, int n_layers, const int *widths
     }
     DevGuard guard(c->d.device); GUARD_OK(guard);
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (s->wm.on) graph_drop(s);          // (a captured chunk holds the schedule's launch, which goes with the policy)
     policy_release(s);
     if (!W) return 0;
     const size_t B = c->batch; SimRollout &r = s->roll;
@@ -306,6 +309,107 @@ extern "C" int tum_sim_policy_eval(tum_sim *s, const double *obs, int n, double 
     if (probs) HIPCHK(hipMemcpy(probs, tp.get(), sizeof(double) * na, hipMemcpyDeviceToHost));
     if (actions) HIPCHK(hipMemcpy(actions, ta.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- K19: the learned weight schedule
+// enable_WMPC of the reference's controller classes inside the loop (wmpc_kernels.hpp; the rule: include/tum_nmpc.h). The kernel's
+// launch is part of every control step from here on (wmpc_enqueue of sim_loop.hpp), of a captured chunk too.
+extern "C" int tum_sim_wmpc_attach(tum_sim *s, const double *table, int n_actions, int period, int on_failure, int n_samples,
+                                   const int *idx_v, const int *idx_yawrate, const double *obs_lo, const double *obs_hi, int log_capacity)
+{
+    if (!s) return fail("null argument");
+    tum_ocp *c = s->c; const size_t B = c->batch; const int N = c->N;
+    if (table) {
+        if (!idx_v || !idx_yawrate || !obs_lo || !obs_hi) return fail("null argument");
+        if (!s->pol.on) return fail("wmpc_attach: no policy attached (tum_sim_policy_attach)");
+        if (wmpc_refuse(s, "wmpc_attach")) return 1;
+        if (n_actions < 1 || n_samples < 1) return fail("wmpc_attach: n_actions and n_samples must be >= 1");
+        if (period < 0) return fail("wmpc_attach: weights_update_period is negative (0 decides at every control step)");
+        if (on_failure != 0 && on_failure != 1) return fail("wmpc_attach: on_failure is 0 (keep the weights) or 1 (back to the weights held at attach time)");
+        if (log_capacity < 0) return fail("wmpc_attach: log_capacity < 0");
+        if (N < ENV_MA || N + 1 > ENV_MAXPTS) return fail("wmpc_attach: the observation's 10-tap moving average of the yaw rate needs 10 <= N <= 127");
+        if (s->pol.a.n_in != 2 + 2 * n_samples)
+            return fail("wmpc_attach: the policy takes " + std::to_string(s->pol.a.n_in) + " inputs, the observation has " + std::to_string(2 + 2 * n_samples) + " entries");
+        if (s->pol.a.n_act != n_actions)
+            return fail("wmpc_attach: the policy has " + std::to_string(s->pol.a.n_act) + " actions, the table has " + std::to_string(n_actions) + " rows");
+        for (int i = 0; i < n_samples; i++) {
+            if (idx_v[i] < 0 || idx_v[i] > N) return fail("wmpc_attach: a velocity sample index is outside 0..N");
+            if (idx_yawrate[i] < 0 || idx_yawrate[i] > N - ENV_MA) return fail("wmpc_attach: a yaw rate sample index is outside 0..N-10");
+        }
+        for (int i = 0; i < 2 + 2 * n_samples; i++)
+            if (!(obs_hi[i] != obs_lo[i])) return fail("wmpc_attach: an observation bound has no width");
+    }
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    if (flush_inputs(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    graph_drop(s);          // (a captured chunk holds the extra launch, or lacks it)
+    wmpc_release(s);
+    if (!table) return 0;
+    const int no = 2 + 2 * n_samples; const size_t L = (size_t)log_capacity * B, recW = (size_t)(N + 1) * 6;
+    std::vector<double> bounds(2 * (size_t)no);
+    for (int i = 0; i < no; i++) { bounds[i] = obs_lo[i]; bounds[no + i] = obs_hi[i]; }
+    std::vector<int> idx(2 * (size_t)n_samples), since(B, s->core.step);
+    for (int i = 0; i < n_samples; i++) { idx[i] = idx_v[i]; idx[n_samples + i] = idx_yawrate[i]; }
+    SimWmpc &m = s->wm; const SimCore &k = s->core;
+    m.lds = sizeof(double) * wmpc_lds_doubles(s->pol.a.rows, N);
+    bool ok = true;
+    ok &= m.table.alloc((size_t)n_actions * 7) == hipSuccess && m.bounds.alloc(bounds.size()) == hipSuccess && m.idx.alloc(idx.size()) == hipSuccess;
+    ok &= m.base_W.alloc(B * recW) == hipSuccess && m.base_pen.alloc(B * 36) == hipSuccess;
+    ok &= m.since.alloc(B) == hipSuccess && m.n_dec.alloc(B) == hipSuccess && m.act.alloc(B) == hipSuccess;
+    if (L) ok &= m.log_step.alloc(L) == hipSuccess && m.log_act.alloc(L) == hipSuccess && m.log_obs.alloc(L * no) == hipSuccess;
+    ok = ok && hipMemcpy(m.table.get(), table, sizeof(double) * 7 * n_actions, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(m.bounds.get(), bounds.data(), sizeof(double) * bounds.size(), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(m.idx.get(), idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice) == hipSuccess;
+    // the snapshot a failed solve goes back to: W and the penalties as the loop holds them now
+    ok = ok && hipMemcpy(m.base_W.get(), c->dW, sizeof(double) * B * recW, hipMemcpyDeviceToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(m.base_pen.get(), c->dpen, sizeof(double) * B * 36, hipMemcpyDeviceToDevice) == hipSuccess;
+    // the counter of every instance is 0 at the step the loop stands at
+    ok = ok && hipMemcpy(m.since.get(), since.data(), sizeof(int) * B, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && L) {
+        ok = hipMemset(m.log_step.get(), 0xff, sizeof(int) * L) == hipSuccess && hipMemset(m.log_act.get(), 0xff, sizeof(int) * L) == hipSuccess;
+    }
+    ok = ok && hipFuncSetAttribute((const void *)wmpc_schedule_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m.lds) == hipSuccess;
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { wmpc_release(s); (void)hipGetLastError(); return fail("wmpc_attach: allocation failed"); }
+    WmpcArgs &a = m.a;
+    a.N = N; a.batch = c->batch; a.n_actions = n_actions; a.n_samples = n_samples; a.period = period; a.restore = on_failure; a.log_cap = log_capacity;
+    a.Ts = k.Ts;
+    a.table = m.table.get(); a.obs_idx = m.idx.get(); a.obs_bounds = m.bounds.get(); a.base_W = m.base_W.get(); a.base_pen = m.base_pen.get();
+    a.ref0 = k.ref0.get(); a.step_counter = k.step_counter.get();
+    a.since = m.since.get(); a.n_dec = m.n_dec.get(); a.log_step = m.log_step.get(); a.log_act = m.log_act.get(); a.log_obs = m.log_obs.get();
+    a.pol = s->pol.a;
+    a.pol.n = c->batch; a.pol.obs = nullptr; a.pol.obs_stride = 0; a.pol.logits = a.pol.probs = nullptr; a.pol.actions = m.act.get();
+    m.n_obs = no; m.on = true;
+    return 0;
+}
+
+// counter (B: the reference's self.counter as the next control step will test it), n_decisions (B), the first log_capacity decisions
+// of every instance -- steps, actions (B x log_capacity, -1 where none), observations (B x log_capacity x n_obs) --, the snapshot
+// base_W (B x (N + 1) x 6) and base_pen (B x 36), and the weights as they are now: W, pen (the same shapes)
+extern "C" int tum_sim_wmpc_get(tum_sim *s, const char *field, double *out, long long len)
+{
+    if (!s || !field || !out) return fail("null argument");
+    tum_ocp *c = s->c; const long long B = c->batch, recW = (long long)(c->N + 1) * 6; const SimWmpc &m = s->wm;
+    const std::string f(field);
+    if (!m.on) return fail("wmpc_get " + f + ": no weight schedule attached (tum_sim_wmpc_attach)");
+    DevGuard guard(c->d.device); GUARD_OK(guard);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const long long L = (long long)m.a.log_cap * B;
+    const struct { const char *name; const int *isrc; const double *dsrc; long long want; } arrays[] = {
+        {"counter", m.since.get(), nullptr, B}, {"n_decisions", m.n_dec.get(), nullptr, B},
+        {"steps", m.log_step.get(), nullptr, L}, {"actions", m.log_act.get(), nullptr, L}, {"observations", nullptr, m.log_obs.get(), L * m.n_obs},
+        {"base_W", nullptr, m.base_W.get(), B * recW}, {"base_pen", nullptr, m.base_pen.get(), B * 36},
+        {"W", nullptr, c->dW, B * recW}, {"pen", nullptr, c->dpen, B * 36}};
+    for (const auto &a : arrays) {
+        if (f != a.name) continue;
+        if (len != a.want) return fail("wmpc_get " + f + ": len mismatch");
+        if (a.want == 0) return 0;
+        if (a.isrc) { if (fetch_ints(a.isrc, (size_t)a.want, out)) return 1; }
+        else HIPCHK(hipMemcpy(out, a.dsrc, sizeof(double) * a.want, hipMemcpyDeviceToHost));
+        if (f == "counter") for (long long b = 0; b < B; b++) out[b] = (double)s->core.step - out[b];
+        return 0;
+    }
+    return fail("wmpc_get: unknown field '" + f + "'");
 }
 
 // what tum_sim_env_rollout and tum_sim_env_collect share beside env_enqueue_step: every entry of a start table (E x B) is a point of the track

@@ -22,6 +22,7 @@
 #include "loop_kernels.hpp"
 #include "env_kernels.hpp"
 #include "policy_kernels.hpp"
+#include "wmpc_kernels.hpp"
 #include "collect_kernels.hpp"
 #include "ppo_kernels.hpp"
 #include "disturbance_kernels.hpp"

@@ -3,10 +3,11 @@ nmpc.py -- host-side mirror of the reference's nominal NMPC controller interface
 HIP solver. Same names, argument meaning and return values as
   Model_Predictive_Controller/Nominal_NMPC/NMPC_STM_acados_settings.py:16,245   acados_settings(...)
   Model_Predictive_Controller/Nominal_NMPC/NMPC_class.py:34-317                 Nonlinear_Model_Predictive_Controller
-so that main.py / Utils/SimulationMode_main_class.py drive it unchanged. (The RL weight-switching
-branch, NMPC_class.py:120-160,208-239, is out of scope: it needs stable_baselines3 and is ML around
-the controller, not the solve.)
+so that main.py / Utils/SimulationMode_main_class.py drive it unchanged. The weights-varying branch
+(enable_WMPC, NMPC_class.py:120-160,208-239) runs at the end of solve() as in the reference, with the
+agent read as data (closed_loop.WeightPolicy): wmpc_setup / wmpc_branch below, shared by the three mirrors.
 """
+import os
 import types
 
 import numpy as np
@@ -140,6 +141,60 @@ def one_call_step(ctl, current_ref_traj):
     return u0, ctl.pred_X, ctl.stats
 
 
+def wmpc_setup(ctl, wmpc=None):
+    """NMPC_class.py:120-160 (the same lines of the SNMPC and R2NMPC classes): with MPC_params['enable_WMPC'] the trained agent, its
+    parameter table and the update period. The agent is <WMPC_model>/best_model/best_model.zip read with
+    WeightPolicy.from_sb3_zip (no stable_baselines3), the table the lines of rl_config.yaml's actions_file -- rounded to float32, the
+    reference keeps them in a float32 tensor --, the observation has obs_n_anticipation_points samples; relative paths are taken from
+    the directory the reference is started in (the parent of its Config/). wmpc = (policy, table, n_samples) hands the three over
+    instead, for callers without those files; the table is used as given. n_obs_stack > 1 is refused."""
+    ctl.WMPC = False
+    ctl.current_action = None
+    m = ctl.MPC_params
+    if not m.get("enable_WMPC", False):
+        return
+    from .closed_loop import WeightPolicy, WmpcSchedule
+    if wmpc is None:
+        import yaml
+        root = m.get("wmpc_root", "")
+        if "WMPC_model" not in m:
+            raise ValueError("enable_WMPC: MPC_params has no WMPC_model (and no agent was handed over: wmpc=(policy, table, n_samples))")
+        base = m["WMPC_model"] if os.path.isabs(m["WMPC_model"]) else os.path.join(root, m["WMPC_model"])
+        policy = WeightPolicy.from_sb3_zip(os.path.join(base, "best_model", "best_model.zip"))
+        with open(os.path.join(base, "rl_config.yaml")) as f:
+            config = yaml.safe_load(f)
+        if int(config.get("n_obs_stack", 1)) > 1:
+            raise NotImplementedError("enable_WMPC: n_obs_stack > 1 (stacked observations) is not supported")
+        actions_file = config["actions_file"] if os.path.isabs(config["actions_file"]) else os.path.join(root, config["actions_file"])
+        with open(actions_file) as f:
+            rows = [[float(p) for p in line.strip().split(",")] for line in f if line.strip()]
+        table = np.array(rows, dtype=np.float32).astype(np.float64)
+        n_samples = int(config["obs_n_anticipation_points"])
+    else:
+        policy, table, n_samples = wmpc
+    ctl._wmpc = WmpcSchedule(policy, table, int(m.get("weights_update_period", 20)), batch=1, Ts=ctl.Ts)
+    if ctl._wmpc.n_samples != int(n_samples):
+        raise ValueError(f"enable_WMPC: the policy takes {policy.n_observations} inputs, an observation of {n_samples} samples has {2 + 2 * int(n_samples)}")
+    ctl.WMPC_parameter_sets = ctl._wmpc.table
+    ctl.weight_update_period = ctl._wmpc.period
+    ctl.steps_since_weight_update = 0
+    ctl.WMPC = True
+
+
+def wmpc_branch(ctl, current_ref_traj):
+    """NMPC_class.py:208-239, at the end of solve(): the counter rule of closed_loop.WmpcSchedule on the state this solve started at
+    (ctl.x0) and this step's reference; a decision goes through update_cost_function_weights"""
+    if not ctl.WMPC:
+        return
+    y = ref_rows(current_ref_traj, ctl.N)
+    due, actions = ctl._wmpc.after_solve(ctl._wmpc_step, np.asarray(ctl.x0, dtype=float).reshape(1, -1)[:, :8], y[:1, :4], y[None])
+    ctl._wmpc_step += 1
+    ctl.steps_since_weight_update = int(ctl._wmpc.counter[0])
+    if len(due):
+        ctl.current_action = int(actions[0])
+        ctl.update_cost_function_weights(ctl.WMPC_parameter_sets[ctl.current_action])
+
+
 class _SolverHandle:
     """`controller.acados_solver`: reading the attribute from OUTSIDE the class first flushes an initial state that still waits for the
     next one-call step (set_initial_state of call_pattern "step"), so code that follows the reference's other pattern --
@@ -163,7 +218,9 @@ class Nonlinear_Model_Predictive_Controller(_SolverHandle):
     literal per-stage set / solve / get sequence (acados_call_sequence), eager setters; identical results."""
 
     def __init__(self, config_path=None, MPC_params_file=None, sim_main_params=None, X0_MPC=None, device=0,
-                 store_qp_in=False, call_pattern="step"):
+                 store_qp_in=False, call_pattern="step", wmpc=None, mpc_params=None):
+        """wmpc = (policy, table, n_samples): the agent of enable_WMPC handed over as data (wmpc_setup); mpc_params: entries of
+        MPC_params set on top of the file's (enable_WMPC, weights_update_period, ...)."""
         if call_pattern not in CALL_PATTERNS:
             raise ValueError(f"call_pattern must be one of {CALL_PATTERNS}")
         self.call_pattern = call_pattern
@@ -172,6 +229,7 @@ class Nonlinear_Model_Predictive_Controller(_SolverHandle):
             self.cfg = _config.load_reference_config(config_path, sim_main_params, MPC_params_file)
         else:
             self.cfg = _config.default_config()
+        self.cfg["mpc"].update(mpc_params or {})
         sim = dict(self.cfg["sim"])
         if sim_main_params:
             sim.update({k: sim_main_params[k] for k in ("Tp", "Ts", "Ts_MPC") if k in sim_main_params})
@@ -199,13 +257,15 @@ class Nonlinear_Model_Predictive_Controller(_SolverHandle):
         self.stats = np.zeros(5)
         self.pred_X = np.empty((0, self.nx))
         self.nh, self.nh_e = 1, 1
-        self.WMPC = False
+        self._wmpc_step = 0
+        wmpc_setup(self, wmpc)
 
     def solve(self, current_ref_traj):
-        """NMPC_class.py:163-241: set yref on every stage, one SQP-RTI step, read u0 / predictions / stats."""
-        if self.call_pattern == "acados":
-            return acados_call_sequence(self, current_ref_traj)
-        return one_call_step(self, current_ref_traj)
+        """NMPC_class.py:163-241: set yref on every stage, one SQP-RTI step, read u0 / predictions / stats; then the
+        weights-varying branch (:208-239)."""
+        out = acados_call_sequence(self, current_ref_traj) if self.call_pattern == "acados" else one_call_step(self, current_ref_traj)
+        wmpc_branch(self, current_ref_traj)
+        return out
 
     def set_initial_state(self, x0):
         """NMPC_class.py:243-246 (lbx_0 = ubx_0 = x0). call_pattern "step": the state rides with the next solve() -- it goes up in the

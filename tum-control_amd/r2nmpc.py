@@ -46,10 +46,13 @@ class Reduced_Robustified_Nonlinear_Model_Predictive_Controller:
     `store_qp_in`, plus -- after every successful solve -- the covariance propagation and constraint tightening for the next
     one (:276-378; `ZoRo: False`, the shipped setting) as one device kernel (K7)."""
 
-    def __init__(self, config_path=None, MPC_params_file=None, sim_main_params=None, X0_MPC=None, device=0, call_pattern="step"):
+    def __init__(self, config_path=None, MPC_params_file=None, sim_main_params=None, X0_MPC=None, device=0, call_pattern="step",
+                 wmpc=None, mpc_params=None):
+        """wmpc, mpc_params: as the nominal mirror takes them. The weights-varying branch (enable_WMPC, :206-245 and :373-404) runs at
+        the end of the nominal mirror's solve(), behind the tightening that is attached to the solve itself."""
         from .nmpc import Nonlinear_Model_Predictive_Controller as _Nominal
         self._nom = _Nominal(config_path, MPC_params_file, sim_main_params, X0_MPC, device=device, store_qp_in=True,
-                             call_pattern=call_pattern)
+                             call_pattern=call_pattern, wmpc=wmpc, mpc_params=mpc_params)
         n = self._nom
         m, veh = n.cfg["mpc"], n.cfg["veh"]
         self.cfg, self.MPC_params = n.cfg, n.MPC_params
@@ -60,7 +63,7 @@ class Reduced_Robustified_Nonlinear_Model_Predictive_Controller:
         self.delta_f_min, self.delta_f_max = veh["delta_f_min"], veh["delta_f_max"]
         self.acc_max = 1.0
         self.stats, self.pred_X = n.stats, n.pred_X
-        self.WMPC = False
+        self.WMPC = n.WMPC
         self._attach()
 
     def _attach(self):
@@ -69,6 +72,15 @@ class Reduced_Robustified_Nonlinear_Model_Predictive_Controller:
         (`if status == 0:` at :276) -- instead of a call and a round trip of its own after solve()."""
         self._nom._solver.r2_attach(self.Sigma0, self.BWB, self.uncertainty_propagation_horizon,
                                      self.delta_f_min, self.delta_f_max, self.acc_max)
+
+    @property
+    def current_action(self):
+        """the row the agent chose last (None before the first decision)"""
+        return self._nom.current_action
+
+    @property
+    def steps_since_weight_update(self):
+        return self._nom.steps_since_weight_update
 
     @property
     def acados_solver(self):

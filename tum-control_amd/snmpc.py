@@ -16,7 +16,7 @@ import numpy as np
 from scipy.special import ndtri
 
 from . import config as _config
-from .nmpc import CALL_PATTERNS, _SolverHandle, acados_call_sequence, one_call_step
+from .nmpc import CALL_PATTERNS, _SolverHandle, acados_call_sequence, one_call_step, wmpc_branch, wmpc_setup
 from .solver import BatchedOcpSolver, CoupledSnmpcSolver
 
 
@@ -132,11 +132,13 @@ class Stochastic_Nonlinear_Model_Predictive_Controller(_SolverHandle):
     """Host-side mirror of the reference's SNMPC controller on the coupled OCP:
     Model_Predictive_Controller/Stochastic_NMPC/SNMPC_class.py:38-349, same method names, arguments and returns
     (`solve` -> u0, pred_X of the nominal copy, stats = [cost, time_tot, sqp_iter, max qp_iter, status]).
-    The RL weight-switching branch (SNMPC_class.py:134-177,215-246) is out of scope as in nmpc.py.
+    The weights-varying branch (enable_WMPC, SNMPC_class.py:134-177,215-246 and :224-255) runs at the end of solve() as in nmpc.py.
     call_pattern as in nmpc.py: "step" (default, one enqueue and one wait per control step) or "acados" (the reference's literal
     sequence, SNMPC_class.py:181-214: set(j, "yref") AND set(j, "p") per stage, stacked 88-value lbx_0 / ubx_0 set at once)."""
 
-    def __init__(self, config_path=None, MPC_params_file=None, sim_main_params=None, X0_MPC=None, device=0, call_pattern="step"):
+    def __init__(self, config_path=None, MPC_params_file=None, sim_main_params=None, X0_MPC=None, device=0, call_pattern="step",
+                 wmpc=None, mpc_params=None):
+        """wmpc, mpc_params: as nmpc.Nonlinear_Model_Predictive_Controller takes them"""
         if call_pattern not in CALL_PATTERNS:
             raise ValueError(f"call_pattern must be one of {CALL_PATTERNS}")
         self.call_pattern = call_pattern
@@ -145,6 +147,7 @@ class Stochastic_Nonlinear_Model_Predictive_Controller(_SolverHandle):
             self.cfg = _config.load_reference_config(config_path, sim_main_params, MPC_params_file)
         else:
             self.cfg = _config.default_config()
+        self.cfg["mpc"].update(mpc_params or {})
         sim = dict(self.cfg["sim"])
         if sim_main_params:
             sim.update({k: sim_main_params[k] for k in ("Tp", "Ts", "Ts_MPC") if k in sim_main_params})
@@ -185,7 +188,8 @@ class Stochastic_Nonlinear_Model_Predictive_Controller(_SolverHandle):
         self.acados_solver = self._build_solver(X0_MPC)
         self.stats = np.zeros(5)
         self.pred_X = np.empty((0, self.nx))
-        self.WMPC = False
+        self._wmpc_step = 0
+        wmpc_setup(self, wmpc)
 
     def _build_solver(self, X0_MPC):
         """acados_settings(self.Tp, self.N, x0_samples.flatten(), self.Q, self.R, self.Qe, self.L1_pen, self.L2_pen, ...)
@@ -209,10 +213,13 @@ class Stochastic_Nonlinear_Model_Predictive_Controller(_SolverHandle):
         return np.concatenate((self.A.flatten(), self.risk_parameter, self.stop_flags[j].reshape(1)))
 
     def solve(self, current_ref_traj):
-        """SNMPC_class.py:179-257"""
+        """SNMPC_class.py:179-257; the weights-varying branch (:224-255) behind the solve"""
         if self.call_pattern == "acados":
-            return acados_call_sequence(self, current_ref_traj, stage_parameter=self._stage_parameter)
-        return one_call_step(self, current_ref_traj)
+            out = acados_call_sequence(self, current_ref_traj, stage_parameter=self._stage_parameter)
+        else:
+            out = one_call_step(self, current_ref_traj)
+        wmpc_branch(self, current_ref_traj)
+        return out
 
     def set_initial_state(self, x0):
         """SNMPC_class.py:259-264 (lbx_0 = ubx_0 = compute_x0dist(x0)). The estimated state rides with the next solve()

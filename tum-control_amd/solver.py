@@ -78,7 +78,7 @@ C_SYMBOLS = ["tum_ocp_create", "tum_ocp_free", "tum_ocp_last_error", "tum_ocp_ba
              "tum_sim_run", "tum_sim_steps", "tum_sim_get", "tum_sim_set_disturbances",
              "tum_sim_disturbances_attach", "tum_sim_disturbances_table",
              "tum_sim_segments_attach", "tum_sim_run_segments", "tum_sim_env_attach", "tum_sim_env_reset", "tum_sim_env_step",
-             "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout",
+             "tum_sim_policy_attach", "tum_sim_policy_eval", "tum_sim_env_rollout", "tum_sim_wmpc_attach", "tum_sim_wmpc_get",
              "tum_sim_policy_attach_value", "tum_sim_policy_eval_ac", "tum_sim_gae", "tum_sim_env_collect",
              "tum_sim_ppo_attach", "tum_sim_ppo_detach", "tum_sim_ppo_step", "tum_sim_ppo_update", "tum_sim_ppo_params", "tum_sim_ppo_state"]
 # the entry points of the Bayesian-optimisation step (bo.py), declared in the same header; a list of their own because
@@ -185,6 +185,9 @@ def load_library(path=None):
         L.tum_sim_policy_attach.argtypes = [vp, ci, ip, ctypes.POINTER(vp), ctypes.POINTER(vp)]
         L.tum_sim_policy_eval.argtypes = [vp, dp, ci, dp, dp, ip]
         L.tum_sim_env_rollout.argtypes = [vp, ci, dp, ci, ip, ci, dp, ip, ip, ip]
+    if hasattr(L, "tum_sim_wmpc_attach"):
+        L.tum_sim_wmpc_attach.argtypes = [vp, dp, ci, ci, ci, ci, ip, ip, dp, dp, ci]
+        L.tum_sim_wmpc_get.argtypes = [vp, cs, dp, ctypes.c_longlong]
     if hasattr(L, "tum_sim_env_collect"):
         u64 = ctypes.c_ulonglong
         L.tum_sim_policy_attach_value.argtypes = [vp, ci, ip, ctypes.POINTER(vp), ctypes.POINTER(vp)]
@@ -991,6 +994,10 @@ class DeviceClosedLoop:
             out = np.empty(self.B if field == "track_of" else len(self.track_rows))
             self._chk(self._L.tum_sim_get(self._s, field.encode(), _dp(out), out.size), "sim_get " + field)
             return out.astype(np.int64)
+        if field == "yref":          # the reference window of the last planned control step: (B, N + 1, 6)
+            out = np.empty((self.B, self.solver.N + 1, 6))
+            self._chk(self._L.tum_sim_get(self._s, b"yref", _dp(out), out.size), "sim_get yref")
+            return out
         d = self._DIMS[field]
         if field in ("x_sim", "x_mpc", "pose", "ref0", "closest"):
             shape = (self.B, d)
@@ -1167,8 +1174,55 @@ class DeviceClosedLoop:
             self.attach_value(policy.value_weights, policy.value_biases)
 
     def detach_policy(self):
+        """(an attached weight schedule goes with it)"""
         self._chk(self._L.tum_sim_policy_attach(self._s, 0, None, None, None), "sim_policy_attach")
         self.policy_widths = self.value_widths = None
+
+    # ---- the learned weight schedule inside the loop (enable_WMPC of the controller classes)
+    _ON_FAILURE = {"keep": 0, "base": 1}
+
+    def attach_wmpc(self, table, period=20, on_failure="base", n_samples=10, log_capacity=0, obs_bounds=None):
+        """Let the attached policy (attach_policy) replace the cost weights inside the loop, as enable_WMPC does in the reference's
+        controller classes: per instance a counter c, 0 now; after the solve of every control step `if c >= period: c = 0, decide,
+        install`, then c += 1 (closed_loop.WmpcSchedule is the host statement). The observation is closed_loop.wmpc_observation of the
+        state the solve started at and the step's reference window, the row installed is table[action] ((A, 7), as attach_env takes
+        it). on_failure "base": an instance whose solve failed gets back the weights the loop holds NOW (the reference builds a fresh
+        solver from the YAML weights; a row decided at that step is lost); "keep": nothing. log_capacity: decisions stored per instance
+        (wmpc_get). Runs on nominal, SNMPC and R2 loops, inside captured chunks, beside segments and drawn disturbances."""
+        if on_failure not in self._ON_FAILURE:
+            raise Exception("attach_wmpc: on_failure must be 'base' or 'keep'")
+        N, n = self.solver.N, int(n_samples)
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 7:
+            raise Exception("attach_wmpc: table must be (n_actions, 7)")
+        if N < 10 or n < 1:
+            raise Exception("attach_wmpc: the observation's 10-tap moving average of the yaw rate needs N >= 10 (and n_samples >= 1)")
+        if obs_bounds is None:
+            obs_bounds = env_observation_bounds(n)
+        ob = np.ascontiguousarray(obs_bounds, dtype=np.float64).reshape(2, 2 + 2 * n)
+        iv = np.ascontiguousarray(np.linspace(0, N, n, dtype=int), dtype=np.int32)
+        ir = np.ascontiguousarray(np.linspace(0, N - 10, n, dtype=int), dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        self._chk(self._L.tum_sim_wmpc_attach(self._s, _dp(table), table.shape[0], int(period), self._ON_FAILURE[on_failure], n,
+                                              iv.ctypes.data_as(ip), ir.ctypes.data_as(ip), _dp(ob[0]), _dp(ob[1]), int(log_capacity)), "sim_wmpc_attach")
+        self.wmpc_log_capacity, self.wmpc_n_obs = int(log_capacity), 2 + 2 * n
+
+    def detach_wmpc(self):
+        """the loop goes on as a plain loop with the weights last installed"""
+        self._chk(self._L.tum_sim_wmpc_attach(self._s, None, 0, 0, 0, 0, None, None, None, None, 0), "sim_wmpc_attach")
+
+    def wmpc_get(self, field):
+        """of the attached schedule: counter, n_decisions (B,) ints; steps, actions (B, log_capacity) ints, -1 where none; observations
+        (B, log_capacity, n_obs); base_W / W (B, N + 1, 6) the diagonal of W per stage at attach time / now (stage N: its first four
+        entries); base_pen / pen (B, 36) the slack penalties"""
+        B, N, L, no = self.B, self.solver.N, getattr(self, "wmpc_log_capacity", 0), getattr(self, "wmpc_n_obs", 0)
+        shapes = dict(counter=(B,), n_decisions=(B,), steps=(B, L), actions=(B, L), observations=(B, L, no),
+                      base_W=(B, N + 1, 6), W=(B, N + 1, 6), base_pen=(B, 36), pen=(B, 36))
+        if field not in shapes:
+            raise Exception(f"wmpc_get: unknown field '{field}'")
+        out = np.zeros(shapes[field])
+        self._chk(self._L.tum_sim_wmpc_get(self._s, field.encode(), _dp(out), out.size), "sim_wmpc_get " + field)
+        return out.astype(np.int64) if field in ("counter", "n_decisions", "steps", "actions") else out
 
     # ---- collecting PPO training rollouts (stable_baselines3 collect_rollouts + compute_returns_and_advantage)
     COLLECT_FIELDS = ("actions", "values", "log_probs", "rewards", "rewards_raw", "episode_starts", "advantages", "returns",
